@@ -235,7 +235,7 @@ def _ptr(a):
 
 
 def device_init(index=0, hw_queues=None):
-    """p25_device_init / p25_device_init_ex: hw_queues None = the library's default (24), 0 = leave GPU_MAX_HW_QUEUES alone.
+    """p25_device_init / p25_device_init_ex: hw_queues None = the library's default (2, the most it accepts), 0 = leave GPU_MAX_HW_QUEUES alone.
     Returns True when the hardware-queue request probably came too late to have an effect (P25_WARN_HW_QUEUES_LATE: the process
     had the GPU runtime open already and GPU_MAX_HW_QUEUES was not exported) -- also readable from runtime_info()."""
     if hw_queues is None:

@@ -9,7 +9,7 @@
 namespace p25 {
 
 // Proving streams come from ONE pool per device, shared by every circuit of the process.  HIP streams are multiplexed
-// onto GPU_MAX_HW_QUEUES hardware queues (24, capi.hip), and two streams in one hardware queue run in order: with a
+// onto GPU_MAX_HW_QUEUES hardware queues (P25_DEFAULT_HW_QUEUES), and two streams in one hardware queue run in order: with a
 // stream set per circuit, a second circuit that is merely ALIVE (the leaf circuit's 9 idle streams beside an
 // aggregation circuit's 17) cost the active one 9 % (120.7 against 131.8 aggregate proofs/s, round 4,
 // profiles/r04_stream_pool.txt), and more hardware queues cost more than they return.  Context i of a circuit takes

@@ -63,4 +63,4 @@ def test_bench_dist_native_gathers_through_the_librarys_own_communicator():
     assert d["config"]["gathered_complete_and_ok"] and d["config"]["oracle_verifier_accepts"]
     assert "p25_gather_proofs" in d["config"]["workload"]
     assert d["per_rank"][0]["proofs_per_step"] == 24 and d["per_rank"][0]["gather_ms_per_step"] > 0
-    assert d["config"]["runtime"]["hw_queues_env"] == 24 and d["config"]["runtime"]["hw_queues_setting_late"] == 0
+    assert d["config"]["runtime"]["hw_queues_env"] == 2 and d["config"]["runtime"]["hw_queues_setting_late"] == 0

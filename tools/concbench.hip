@@ -1,7 +1,7 @@
 // How many kernels does the MI355X keep ACTIVE at once?  K streams, each M launches of a one-wave kernel that spins for T us
 // of the constant-rate wall clock; wall time of the whole lot -> concurrency = K * M * T / wall.  (Round 5: the kernel trace of
 // the 16-stream proving pipeline never shows more than 5-7 kernels executing together; is that the hardware?)
-// usage: concbench [T_us=200] [M=20]      (GPU_MAX_HW_QUEUES from the environment, as the library sets it: 24)
+// usage: concbench [T_us=200] [M=20]      (GPU_MAX_HW_QUEUES from the environment, as the library sets it: 2)
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>

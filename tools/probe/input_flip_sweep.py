@@ -1,6 +1,6 @@
 import os, sys, time
 import numpy as np
-ROOT='/root/repo'
+ROOT=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as ge
 p25 = ge.load_package(); p25.device_init(0)

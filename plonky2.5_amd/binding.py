@@ -234,6 +234,22 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _sized(call, dtype):
+    """The ABI's two-call pattern over call(buf, cap, len_ref): query the length (buf NULL), then fill a `dtype` array."""
+    n = sz(0)
+    _check(call(None, 0, C.byref(n)))
+    out = np.zeros(n.value, dtype=dtype)
+    _check(call(_ptr(out), out.size, C.byref(n)))
+    return out
+
+
+def _new_circuit(fn, *args):
+    """A Circuit from a constructor entry point, which takes the p25_circuit** after `args`."""
+    h = vp()
+    _check(fn(*args, C.byref(h)))
+    return Circuit(h.value)
+
+
 def device_init(index=0, hw_queues=None):
     """p25_device_init / p25_device_init_ex: hw_queues None = the library's default (2, the most it accepts), 0 = leave GPU_MAX_HW_QUEUES alone.
     Returns True when the hardware-queue request probably came too late to have an effect (P25_WARN_HW_QUEUES_LATE: the process
@@ -395,11 +411,8 @@ def p3_proof_from_json(text):
     serde_json::from_str::<P3ProofField> + Proof::set_witness (src/p3/mod.rs:233-234, 254-257)."""
     if isinstance(text, str):
         text = text.encode()
-    n = sz(0)
     cfg = P3Config()
-    _check(lib().p25_p3_proof_from_json(text, len(text), None, 0, C.byref(n), C.byref(cfg)))
-    out = np.zeros(n.value, dtype=np.uint64)
-    _check(lib().p25_p3_proof_from_json(text, len(text), _ptr(out), out.size, C.byref(n), C.byref(cfg)))
+    out = _sized(lambda buf, cap, n: lib().p25_p3_proof_from_json(text, len(text), buf, cap, n, C.byref(cfg)), np.uint64)
     return out, cfg
 
 
@@ -407,12 +420,9 @@ def p3_prove_fibonacci(log_n=6, num_queries=100, pow_bits=16, pow_start=0, threa
     """Native plonky3 proof of the Fibonacci AIR with 2^log_n rows -> (inputs uint64[n], P3Config).
     With the defaults it reproduces the reference's artifacts/proof_fibonacci.json bit for bit."""
     threads = threads or min(16, os.cpu_count() or 1)
-    n = sz(0)
     cfg = P3Config()
-    _check(lib().p25_p3_prove_fibonacci(log_n, num_queries, pow_bits, pow_start, threads, None, 0, C.byref(n), C.byref(cfg)))
-    out = np.zeros(n.value, dtype=np.uint64)
-    _check(lib().p25_p3_prove_fibonacci(log_n, num_queries, pow_bits, pow_start, threads, _ptr(out), out.size,
-                                        C.byref(n), C.byref(cfg)))
+    out = _sized(lambda buf, cap, n: lib().p25_p3_prove_fibonacci(log_n, num_queries, pow_bits, pow_start, threads, buf, cap,
+                                                                  n, C.byref(cfg)), np.uint64)
     return out, cfg
 
 
@@ -425,23 +435,16 @@ def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=
         raise ValueError("trace must be [2^log_n][air.width]")
     log_n = int(t.shape[0]).bit_length() - 1
     ac = air.to_c()
-    n = sz(0)
     cfg = P3Config()
-    _check(lib().p25_p3_prove_air_ex(C.byref(ac), None, log_n, log_blowup, num_queries, pow_bits, pow_start, threads, None, 0,
-                                     C.byref(n), C.byref(cfg)))
-    out = np.zeros(n.value, dtype=np.uint64)
-    _check(lib().p25_p3_prove_air_ex(C.byref(ac), _ptr(t), log_n, log_blowup, num_queries, pow_bits, pow_start, threads, _ptr(out),
-                                     out.size, C.byref(n), C.byref(cfg)))
+    out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_ex(C.byref(ac), _ptr(t), log_n, log_blowup, num_queries, pow_bits,
+                                                               pow_start, threads, buf, cap, n, C.byref(cfg)), np.uint64)
     return out, cfg
 
 
 def p3_inputs_to_json(inputs, cfg):
     a = _u64(inputs)
-    n = sz(0)
-    _check(lib().p25_p3_inputs_to_json(_ptr(a), a.size, C.byref(cfg), None, 0, C.byref(n)))
-    buf = C.create_string_buffer(n.value)
-    _check(lib().p25_p3_inputs_to_json(_ptr(a), a.size, C.byref(cfg), buf, n.value, C.byref(n)))
-    return buf.raw[:n.value].decode()
+    return _sized(lambda buf, cap, n: lib().p25_p3_inputs_to_json(_ptr(a), a.size, C.byref(cfg), buf, cap, n),
+                  np.uint8).tobytes().decode()
 
 
 class Circuit:
@@ -452,52 +455,39 @@ class Circuit:
         self._h = vp(handle)
         self._info = None
 
-    @classmethod
-    def build_p3_verifier(cls, cfg=None, air=0):
-        cfg = cfg or P3Config.fib64()
-        h = vp()
-        _check(lib().p25_circuit_build_p3_verifier(C.byref(cfg), air, C.byref(h)))
-        return cls(h.value)
+    @staticmethod
+    def build_p3_verifier(cfg=None, air=0):
+        return _new_circuit(lib().p25_circuit_build_p3_verifier, C.byref(cfg or P3Config.fib64()), air)
 
-    @classmethod
-    def build_p3_verifier_air(cls, cfg, air):
+    @staticmethod
+    def build_p3_verifier_air(cfg, air):
         """`builder.p3_verify_proof::<H>(proof, &air, fri_config)` for a user AIR (binding.Air)."""
-        h = vp()
         ac = air.to_c()
-        _check(lib().p25_circuit_build_p3_verifier_air(C.byref(cfg), C.byref(ac), C.byref(h)))
-        return cls(h.value)
+        return _new_circuit(lib().p25_circuit_build_p3_verifier_air, C.byref(cfg), C.byref(ac))
 
-    @classmethod
-    def build_gadget(cls, kind, param=0):
+    @staticmethod
+    def build_gadget(kind, param=0):
         """kind: 0 and, 1 xor, 2 lsh, 3 rsh, 4 reverse_bits_len, 5 compress, 6 exp, 7 hash_iter_slices,
         8 two connected inputs (include/p25.h)."""
-        h = vp()
-        _check(lib().p25_circuit_build_gadget(kind, param, C.byref(h)))
-        return cls(h.value)
+        return _new_circuit(lib().p25_circuit_build_gadget, kind, param)
 
-    @classmethod
-    def build_gate_eval(cls, kind):
+    @staticmethod
+    def build_gate_eval(kind):
         """Gate-level test circuit: evaluates gate `kind` in-circuit (eval_unfiltered_circuit) against expectations."""
-        h = vp()
-        _check(lib().p25_circuit_build_gate_eval(kind, C.byref(h)))
-        return cls(h.value)
+        return _new_circuit(lib().p25_circuit_build_gate_eval, kind)
 
     def build_recursive_verifier(self, n_proofs=1, digest=None, cs_cap=None):
         """A circuit verifying `n_proofs` proofs of this circuit (upstream builder.verify_proof).  digest / cs_cap:
         this circuit's verifier data (default: computed on the GPU)."""
-        h = vp()
-        d = _u64(digest) if digest is not None else None
-        cap = _u64(cs_cap) if cs_cap is not None else None
-        _check(lib().p25_circuit_build_recursive_verifier(self._h, _ptr(d), _ptr(cap), n_proofs, C.byref(h)))
-        return Circuit(h.value)
+        return self._build_recursive(lib().p25_circuit_build_recursive_verifier, n_proofs, digest, cs_cap)
 
     def build_aggregator(self, n_proofs=2, digest=None, cs_cap=None):
         """build_recursive_verifier whose circuit registers 4 public inputs committing to the proofs it verifies."""
-        h = vp()
-        d = _u64(digest) if digest is not None else None
-        cap = _u64(cs_cap) if cs_cap is not None else None
-        _check(lib().p25_circuit_build_aggregator(self._h, _ptr(d), _ptr(cap), n_proofs, C.byref(h)))
-        return Circuit(h.value)
+        return self._build_recursive(lib().p25_circuit_build_aggregator, n_proofs, digest, cs_cap)
+
+    def _build_recursive(self, fn, n_proofs, digest, cs_cap):
+        d, cap = (_u64(a) if a is not None else None for a in (digest, cs_cap))
+        return _new_circuit(fn, self._h, _ptr(d), _ptr(cap), n_proofs)
 
     def public_inputs(self, proof):
         """The public inputs of a flat proof (its last num_public_inputs words)."""
@@ -505,12 +495,10 @@ class Circuit:
         p = _u64(proof)
         return p[p.size - n:].copy() if n else np.zeros(0, dtype=np.uint64)
 
-    @classmethod
-    def from_blob(cls, blob):
-        h = vp()
+    @staticmethod
+    def from_blob(blob):
         buf = np.frombuffer(blob, dtype=np.uint8)
-        _check(lib().p25_circuit_import(_ptr(buf), buf.size, C.byref(h)))
-        return cls(h.value)
+        return _new_circuit(lib().p25_circuit_import, _ptr(buf), buf.size)
 
     def to_bytes(self):
         """upstream CircuitData::to_bytes (needs the GPU: the constants/sigmas commitment is part of the data)."""
@@ -522,28 +510,18 @@ class Circuit:
             lib().p25_free(p)
 
     def input_target_indices(self):
-        n = sz(0)
-        _check(lib().p25_circuit_input_targets(self._h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, dtype=np.uint32)
-        _check(lib().p25_circuit_input_targets(self._h, _ptr(out), out.size, C.byref(n)))
-        return out
+        return _sized(lambda buf, cap, n: lib().p25_circuit_input_targets(self._h, buf, cap, n), np.uint32)
 
-    @classmethod
-    def from_bytes(cls, data, input_targets):
+    @staticmethod
+    def from_bytes(data, input_targets):
         """upstream CircuitData::from_bytes + the per-proof input targets.  Returns (circuit, stored circuit digest)."""
-        h = vp()
         buf = np.frombuffer(data, dtype=np.uint8)
         it = np.ascontiguousarray(input_targets, dtype=np.uint32)
         dg = np.zeros(4, dtype=np.uint64)
-        _check(lib().p25_circuit_from_bytes(_ptr(buf), buf.size, _ptr(it), it.size, _ptr(dg), C.byref(h)))
-        return cls(h.value), dg
+        return _new_circuit(lib().p25_circuit_from_bytes, _ptr(buf), buf.size, _ptr(it), it.size, _ptr(dg)), dg
 
     def to_blob(self):
-        n = sz(0)
-        _check(lib().p25_circuit_export(self._h, None, 0, C.byref(n)))
-        buf = np.zeros(n.value, dtype=np.uint8)
-        _check(lib().p25_circuit_export(self._h, _ptr(buf), buf.size, C.byref(n)))
-        return buf.tobytes()
+        return _sized(lambda buf, cap, n: lib().p25_circuit_export(self._h, buf, cap, n), np.uint8).tobytes()
 
     def close(self):
         if self._h:
@@ -678,11 +656,7 @@ class Circuit:
     def proof_to_bytes(self, proof):
         """upstream ProofWithPublicInputs::to_bytes() of a flat proof."""
         p = _u64(proof)
-        n = sz(0)
-        _check(lib().p25_proof_to_bytes(self._h, _ptr(p), None, 0, C.byref(n)))
-        buf = np.zeros(n.value, dtype=np.uint8)
-        _check(lib().p25_proof_to_bytes(self._h, _ptr(p), _ptr(buf), buf.size, C.byref(n)))
-        return buf.tobytes()
+        return _sized(lambda buf, cap, n: lib().p25_proof_to_bytes(self._h, _ptr(p), buf, cap, n), np.uint8).tobytes()
 
     def proof_from_bytes(self, data):
         buf = np.frombuffer(data, dtype=np.uint8)
@@ -692,8 +666,4 @@ class Circuit:
 
     def proof_to_json(self, proof):
         p = _u64(proof)
-        n = sz(0)
-        _check(lib().p25_proof_to_json(self._h, _ptr(p), None, 0, C.byref(n)))
-        buf = C.create_string_buffer(n.value)
-        _check(lib().p25_proof_to_json(self._h, _ptr(p), buf, n.value, C.byref(n)))
-        return buf.raw[:n.value].decode()
+        return _sized(lambda buf, cap, n: lib().p25_proof_to_json(self._h, _ptr(p), buf, cap, n), np.uint8).tobytes().decode()

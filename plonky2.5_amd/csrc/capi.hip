@@ -1,4 +1,13 @@
 // C ABI of libp25 (declared in include/p25.h).  Thin: argument checks, device buffers, launches.
+//
+// The conventions every entry point follows, each written once in namespace p25 below:
+//   guard       the body runs under guarded() (device entry points: ensure_device() first, then the argument checks) or
+//               host_guarded() (host-only entry points); status_of_current_exception() turns what the body throws into the
+//               status and the p25_last_error() text.
+//   handle      new_circuit() makes every p25_circuit: *out is written only once the circuit is built, nothing leaks.
+//   size query  "buf may be NULL to query the length" is copy_out(); every capacity check is check_cap(), with its one message.
+//   lock        an entry point that touches one circuit holds that circuit's mutex (P25_LOCK): with_circuit() (host tables) and
+//               with_device() (device state) are the null check, the lock and the circuit for the entry points that need no more.
 #include <stdlib.h>
 #include <dirent.h>
 #include <unistd.h>
@@ -8,6 +17,13 @@
 #include <mutex>
 #include "../../include/p25.h"
 #include "kernels.h"
+#include "circuit_io.h"
+#include "circuit_bytes.h"
+#include "json_io.h"
+#include "p3_circuit.h"
+#include "p3_prover.h"
+#include "prover.h"
+#include "recursion.h"
 
 namespace p25 {
 thread_local std::string g_last_error;
@@ -100,24 +116,11 @@ p25_status ensure_device() {
   return P25_OK;
 }
 
-struct DevBuf {
-  u64* p = nullptr;
-  explicit DevBuf(size_t words) {
-    if (words) P25_HIP(hipMalloc(&p, words * sizeof(u64)));
-  }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
-template <class F>
-p25_status guarded(F&& f) {
+// The one exception -> status mapping of the ABI (comm.cpp's guard adds RCCL's in front of it).  Call it inside a
+// catch (...): it rethrows the exception in flight, records its text for p25_last_error() and returns its status.
+p25_status status_of_current_exception() {
   try {
-    p25_status s = ensure_device();
-    if (s != P25_OK) return s;
-    return f();
+    throw;
   } catch (const HipError& e) {
     g_last_error = e.what();
     return P25_ERR_HIP;
@@ -129,8 +132,6 @@ p25_status guarded(F&& f) {
     return P25_ERR_INTERNAL;
   }
 }
-
-static bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 
 void lde_commit_dev(const u64* d_polys, unsigned log_n, size_t n_polys, bool from_coeffs,
                     unsigned rate_bits, unsigned cap_height, u64* d_coeffs, u64* d_tmp, u64* d_lde,
@@ -146,10 +147,257 @@ void lde_commit_dev(const u64* d_polys, unsigned log_n, size_t n_polys, bool fro
 }
 }  // namespace p25
 
+struct p25_circuit {
+  p25::Circuit circuit;                       // host tables (moved into dev on first device use)
+  std::unique_ptr<p25::DeviceCircuit> dev;
+  std::unique_ptr<p25::WitnessProgram> wp_info;
+  bool moved = false;
+  int streams = 16;  // proofs in flight (p25_circuit_set_streams)
+  // Entry points that touch the device state of ONE circuit are serialised: upstream's `prove(&self)` is re-entrant,
+  // so a host with a thread pool may call into the same circuit concurrently; here those calls queue up instead of
+  // racing for the circuit's streams and contexts.  Different circuits never contend.
+  mutable std::recursive_mutex mu;   // mutable: the read-only entry points (const handles) lock too
+  const p25::Circuit& c() const { return dev ? dev->circuit() : circuit; }
+  p25::DeviceCircuit& device() {
+    if (!dev) {
+      dev.reset(new p25::DeviceCircuit(std::move(circuit)));
+      dev->set_streams(streams);
+      moved = true;
+    }
+    return *dev;
+  }
+};
+#define P25_LOCK(c) std::lock_guard<std::recursive_mutex> p25_lock_((c)->mu)
+
+namespace p25 {
+namespace {
+struct DevBuf {
+  u64* p = nullptr;
+  explicit DevBuf(size_t words) {
+    if (words) P25_HIP(hipMalloc(&p, words * sizeof(u64)));
+  }
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+};
+
+// guard: host-only entry points
+template <class F>
+p25_status host_guarded(F&& f) {
+  try {
+    return f();
+  } catch (...) {
+    return status_of_current_exception();
+  }
+}
+// guard: device entry points (the device is selected before the body checks its arguments)
+template <class F>
+p25_status guarded(F&& f) {
+  return host_guarded([&]() -> p25_status {
+    const p25_status s = ensure_device();
+    return s != P25_OK ? s : f();
+  });
+}
+
+// handle: *out receives the circuit only once build() has returned it
+template <class F>
+p25_status new_circuit(p25_circuit** out, F&& build) {
+  std::unique_ptr<p25_circuit> h(new p25_circuit());
+  h->circuit = build();
+  *out = h.release();
+  return P25_OK;
+}
+
+// size query: the one capacity check of the ABI
+void check_cap(size_t cap, size_t n) {
+  if (cap < n) throw std::invalid_argument("buffer too small");
+}
+// *len_out = n; with buf set, cap must hold the n elements, which are copied
+template <class T>
+p25_status copy_out(const T* src, size_t n, T* buf, size_t cap, size_t* len_out) {
+  *len_out = n;
+  if (buf) {
+    check_cap(cap, n);
+    memcpy(buf, src, n * sizeof(T));
+  }
+  return P25_OK;
+}
+
+// lock: a host-only entry point that reads circuit c's tables (args_ok: its other pointer arguments are set)
+template <class F>
+p25_status with_circuit(const p25_circuit* c, bool args_ok, F&& f) {
+  return host_guarded([&]() -> p25_status {
+    if (!c || !args_ok) throw std::invalid_argument("null argument");
+    P25_LOCK(c);
+    return f(c->c());
+  });
+}
+// lock: a device entry point that runs one method of circuit c's device state
+template <class F>
+p25_status with_device(p25_circuit* c, bool args_ok, F&& f) {
+  return guarded([&]() -> p25_status {
+    if (!c || !args_ok) throw std::invalid_argument("null argument");
+    P25_LOCK(c);
+    f(c->device());
+    return P25_OK;
+  });
+}
+template <class F>
+p25_status with_device(p25_circuit* c, F&& f) { return with_device(c, true, f); }
+
+bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
+
+// the host-buffer permutation entry points: states[n][12] in place
+p25_status permute_host(uint64_t* states, size_t n, void (*launch)(u64*, size_t, hipStream_t)) {
+  return guarded([&]() -> p25_status {
+    if (!states && n) throw std::invalid_argument("states is null");
+    DevBuf d(n * 12);
+    P25_HIP(hipMemcpy(d.p, states, n * 96, hipMemcpyHostToDevice));
+    launch(d.p, n, 0);
+    P25_HIP(hipGetLastError());
+    P25_HIP(hipMemcpy(states, d.p, n * 96, hipMemcpyDeviceToHost));
+    return P25_OK;
+  });
+}
+
+// p25_p3_config <-> P3Config: the same nine fields in the same order
+p25_p3_config to_c(const P3Config& pc) {
+  return {pc.fri_config.log_blowup, pc.fri_config.num_queries, pc.fri_config.proof_of_work_bits, pc.log_quotient_degree,
+          pc.log_trace_height, pc.trace_width, pc.opening_matrix_log_max_height,
+          pc.opening_proof_query_openings_opened_values_length, pc.degree_bits};
+}
+P3Config from_c(const p25_p3_config* c) {
+  return {{c->log_blowup, c->num_queries, c->proof_of_work_bits}, c->log_quotient_degree, c->log_trace_height, c->trace_width,
+          c->opening_matrix_log_max_height, c->quotient_opened_len, c->degree_bits};
+}
+P3Config checked_p3_config(const p25_p3_config* cfg) {
+  // one quotient chunk is the reference's proof model (proof.rs:41-48); two (constraint degree 3) is the round-5 extension,
+  // four / eight (degree 4-5 / 6-9, with log_blowup 2 / 3) round 6's
+  if (cfg->log_quotient_degree < 0 || cfg->log_quotient_degree > 3)
+    throw std::invalid_argument("1, 2, 4 or 8 quotient chunks are supported (log_quotient_degree 0..3)");
+  if (cfg->log_quotient_degree > cfg->log_blowup) throw std::invalid_argument("log_quotient_degree above log_blowup");
+  if (cfg->opening_matrix_log_max_height != cfg->log_trace_height + cfg->log_blowup)
+    throw std::invalid_argument("opening_matrix_log_max_height must be log_trace_height + log_blowup");
+  if (cfg->trace_width < 1 || cfg->trace_width > 64 || cfg->log_trace_height < 1 || cfg->log_trace_height > 24 ||
+      cfg->num_queries < 1 || cfg->num_queries > 1000 || cfg->degree_bits < 1 || cfg->degree_bits > cfg->log_trace_height ||
+      cfg->opening_matrix_log_max_height < 1 || cfg->opening_matrix_log_max_height > 30 || cfg->quotient_opened_len < 1 ||
+      cfg->log_blowup < 1 || cfg->log_blowup > 4 || cfg->proof_of_work_bits < 0 || cfg->proof_of_work_bits > 32)
+    throw std::invalid_argument("p25_p3_config out of range");
+  return from_c(cfg);
+}
+AirProgram air_from_c(const p25_air* air) {
+  if (!air || !air->nodes || !air->constraints) throw std::invalid_argument("null AIR");
+  if (air->n_nodes > (1u << 20) || air->n_constraints > (1u << 16)) throw std::invalid_argument("AIR too large");
+  AirProgram p;
+  p.width = (int)air->width;
+  for (uint32_t i = 0; i < air->n_nodes; i++)
+    p.nodes.push_back(AirProgram::Node{air->nodes[i].op, air->nodes[i].a, air->nodes[i].b, air->nodes[i].value});
+  for (uint32_t i = 0; i < air->n_constraints; i++)
+    p.constraints.push_back(AirProgram::Constraint{air->constraints[i].node, air->constraints[i].when});
+  p.validate();
+  return p;
+}
+
+// The native plonky3 provers (Fibonacci, AIR): the proof's shape their parameters imply for an AIR of P3Config's default
+// width and degree (the Fibonacci AIR's)
+P3Config p3_shape(const P3ProveParams& prm) {
+  P3Config pc;
+  pc.fri_config.log_blowup = prm.log_blowup;
+  pc.fri_config.num_queries = prm.num_queries;
+  pc.log_trace_height = pc.degree_bits = prm.log_n;
+  pc.opening_matrix_log_max_height = prm.log_n + prm.log_blowup;
+  return pc;
+}
+// Their output: a size query (inputs_out NULL) is answered from the shape pc alone, without proving; otherwise prove()
+// completes pc and returns the inputs.
+template <class F>
+p25_status p3_prove_out(const P3ProveParams& prm, P3Config& pc, F&& prove, uint64_t* inputs_out, size_t cap, size_t* n_out,
+                        p25_p3_config* cfg_out) {
+  if (!inputs_out) {
+    if (prm.log_n < 1 || prm.log_n > 22 || prm.num_queries < 1) throw std::invalid_argument("bad parameters");
+    *n_out = pc.num_inputs();
+    pc.fri_config.proof_of_work_bits = prm.pow_bits;
+  } else {
+    const std::vector<u64> v = prove();
+    copy_out(v.data(), v.size(), inputs_out, cap, n_out);
+  }
+  if (cfg_out) *cfg_out = to_c(pc);
+  return P25_OK;
+}
+
+p25_status build_verifier(const p25_p3_config* cfg, const Air& air, p25_circuit** out) {
+  const P3Config pc = checked_p3_config(cfg);
+  if (pc.trace_width != air.width()) throw std::invalid_argument("Invalid Proof Shape");
+  return new_circuit(out, [&] {
+    CircuitBuilder cb;
+    p3_verify_proof(cb, pc, air);
+    return cb.build();
+  });
+}
+p25_status build_recursive(p25_circuit* inner, const uint64_t* digest4, const uint64_t* cs_cap, int32_t n_proofs,
+                           bool expose_commitment, p25_circuit** out) {
+  auto body = [&]() -> p25_status {
+    if (!inner || !out) throw std::invalid_argument("null argument");
+    if ((digest4 == nullptr) != (cs_cap == nullptr)) throw std::invalid_argument("pass both digest4 and cs_cap, or neither");
+    P25_LOCK(inner);   // reads inner->c(): another thread's first device use moves the host tables
+    const Circuit& ic = inner->c();
+    uint64_t dg[4];
+    std::vector<u64> cap((size_t)4 << ic.cfg.cap_height);
+    if (digest4) {
+      memcpy(dg, digest4, 32);
+      memcpy(cap.data(), cs_cap, cap.size() * 8);
+      for (u64 v : cap)
+        if (v >= gl::P) throw std::invalid_argument("non-canonical cap word");
+      for (u64 v : dg)
+        if (v >= gl::P) throw std::invalid_argument("non-canonical digest word");
+    } else {
+      DeviceCircuit& d = inner->device();  // needs the GPU: commits the constants/sigmas polynomials
+      memcpy(dg, d.digest(), 32);
+      cap = d.cs_cap();
+    }
+    return new_circuit(out, [&] { return build_recursive_verifier(inner->c(), dg, cap, n_proofs, expose_commitment); });
+  };
+  return digest4 ? host_guarded(body) : guarded(body);
+}
+
+void fill_timings(p25_timings* t, const PhaseTimes& pt) {
+  if (!t) return;
+  t->witness_ms = pt.witness; t->wires_commit_ms = pt.wires_commit; t->partial_products_ms = pt.zs_pp;
+  t->zs_commit_ms = pt.zs_commit; t->quotient_ms = pt.quotient; t->quotient_commit_ms = pt.quotient_commit;
+  t->openings_ms = pt.openings; t->fri_ms = pt.fri; t->total_ms = pt.total;
+}
+
+bool fri_shape_from_c(unsigned log_n, unsigned rate_bits, unsigned cap_height, const int32_t* arity_bits, size_t n_layers,
+                      unsigned pow_bits, unsigned num_queries, FriShape& sh) {
+  if (log_n < 1 || log_n > 22 || rate_bits > 3 || cap_height > 16 || n_layers > 8 || (n_layers && !arity_bits) ||
+      num_queries < 1 || num_queries > 64 || pow_bits > 32)
+    return false;
+  sh.log_n = (int)log_n;
+  sh.rate_bits = (int)rate_bits;
+  sh.cap_height = cap_height;
+  sh.arity_bits.assign(arity_bits, arity_bits + n_layers);
+  sh.pow_bits = (int)pow_bits;
+  sh.num_queries = (int)num_queries;
+  int deg = (int)log_n, bits = (int)(log_n + rate_bits);
+  if (bits < (int)cap_height) return false;
+  for (int a : sh.arity_bits) {
+    if (a < 1 || a > 8) return false;
+    deg -= a;
+    bits -= a;
+    if (deg < 0 || bits < (int)cap_height) return false;
+  }
+  return true;
+}
+}  // namespace
+}  // namespace p25
+
 using namespace p25;
 
 extern "C" {
 
+// ---- library, device, runtime ---------------------------------------------------------------------------------------
 const char* p25_last_error(void) { return g_last_error.c_str(); }
 const char* p25_version(void) { return "libp25 0.1 (gfx950)"; }
 
@@ -214,42 +462,9 @@ p25_status p25_runtime_info(p25_runtime_info_t* out) {
   return P25_OK;
 }
 
-p25_status p25_shader_clock_hz(double* hz_out) {
-  return guarded([&]() -> p25_status {
-    if (!hz_out) throw std::invalid_argument("hz_out is null");
-    *hz_out = measure_shader_clock_hz(0);
-    return P25_OK;
-  });
-}
-
-p25_status p25_poseidon_permute(uint64_t* states, size_t n) {
-  return guarded([&]() -> p25_status {
-    if (!states && n) throw std::invalid_argument("states is null");
-    DevBuf d(n * 12);
-    P25_HIP(hipMemcpy(d.p, states, n * 96, hipMemcpyHostToDevice));
-    launch_poseidon_permute(d.p, n, 0);
-    P25_HIP(hipGetLastError());
-    P25_HIP(hipMemcpy(states, d.p, n * 96, hipMemcpyDeviceToHost));
-    return P25_OK;
-  });
-}
-
-p25_status p25_poseidon2_permute(uint64_t* states, size_t n) {
-  return guarded([&]() -> p25_status {
-    if (!states && n) throw std::invalid_argument("states is null");
-    DevBuf d(n * 12);
-    P25_HIP(hipMemcpy(d.p, states, n * 96, hipMemcpyHostToDevice));
-    launch_poseidon2_permute(d.p, n, 0);
-    P25_HIP(hipGetLastError());
-    P25_HIP(hipMemcpy(states, d.p, n * 96, hipMemcpyDeviceToHost));
-    return P25_OK;
-  });
-}
-
-size_t p25_merkle_tree_words(size_t n_leaves, unsigned cap_height) {
-  if (!is_pow2(n_leaves) || cap_height > 63 || n_leaves < ((size_t)1 << cap_height)) return 0;
-  return merkle_tree_words(n_leaves, cap_height);
-}
+// ---- primitives -----------------------------------------------------------------------------------------------------
+p25_status p25_poseidon_permute(uint64_t* states, size_t n) { return permute_host(states, n, launch_poseidon_permute); }
+p25_status p25_poseidon2_permute(uint64_t* states, size_t n) { return permute_host(states, n, launch_poseidon2_permute); }
 
 p25_status p25_merkle_commit(const uint64_t* leaves_cm, size_t n_leaves, size_t width,
                              unsigned cap_height, uint64_t* cap_out, uint64_t* tree_out) {
@@ -269,28 +484,10 @@ p25_status p25_merkle_commit(const uint64_t* leaves_cm, size_t n_leaves, size_t 
     return P25_OK;
   });
 }
-
-p25_status p25_merkle_commit_dev(const uint64_t* d_leaves_cm, size_t col_stride, size_t n_leaves,
-                                 size_t width, unsigned cap_height, uint64_t* d_tree, void* stream) {
-  return guarded([&]() -> p25_status {
-    if (!is_pow2(n_leaves) || cap_height > 40 || n_leaves < ((size_t)1 << cap_height) || !width ||
-        col_stride < n_leaves || !d_leaves_cm || !d_tree)
-      throw std::invalid_argument("p25_merkle_commit_dev: bad shape");
-    launch_merkle_tree(d_leaves_cm, col_stride, (int)width, n_leaves, cap_height, d_tree,
-                       (hipStream_t)stream);
-    P25_HIP(hipGetLastError());
-    return P25_OK;
-  });
+size_t p25_merkle_tree_words(size_t n_leaves, unsigned cap_height) {
+  if (!is_pow2(n_leaves) || cap_height > 63 || n_leaves < ((size_t)1 << cap_height)) return 0;
+  return merkle_tree_words(n_leaves, cap_height);
 }
-
-p25_status p25_poseidon_permute_dev(uint64_t* d_states, size_t n, void* stream) {
-  return guarded([&]() -> p25_status {
-    launch_poseidon_permute(d_states, n, (hipStream_t)stream);
-    P25_HIP(hipGetLastError());
-    return P25_OK;
-  });
-}
-
 p25_status p25_lde_commit(const uint64_t* polys, unsigned log_n, size_t n_polys, int from_coeffs,
                           unsigned rate_bits, unsigned cap_height, uint64_t* coeffs_out,
                           uint64_t* lde_out, uint64_t* cap_out) {
@@ -316,7 +513,18 @@ p25_status p25_lde_commit(const uint64_t* polys, unsigned log_n, size_t n_polys,
     return P25_OK;
   });
 }
-
+p25_status p25_merkle_commit_dev(const uint64_t* d_leaves_cm, size_t col_stride, size_t n_leaves,
+                                 size_t width, unsigned cap_height, uint64_t* d_tree, void* stream) {
+  return guarded([&]() -> p25_status {
+    if (!is_pow2(n_leaves) || cap_height > 40 || n_leaves < ((size_t)1 << cap_height) || !width ||
+        col_stride < n_leaves || !d_leaves_cm || !d_tree)
+      throw std::invalid_argument("p25_merkle_commit_dev: bad shape");
+    launch_merkle_tree(d_leaves_cm, col_stride, (int)width, n_leaves, cap_height, d_tree,
+                       (hipStream_t)stream);
+    P25_HIP(hipGetLastError());
+    return P25_OK;
+  });
+}
 p25_status p25_lde_commit_dev(const uint64_t* d_polys, unsigned log_n, size_t n_polys, int from_coeffs,
                               unsigned rate_bits, unsigned cap_height, uint64_t* d_coeffs,
                               uint64_t* d_tmp, uint64_t* d_lde, uint64_t* d_tree, void* stream) {
@@ -331,195 +539,90 @@ p25_status p25_lde_commit_dev(const uint64_t* d_polys, unsigned log_n, size_t n_
     return P25_OK;
   });
 }
-
-}  // extern "C"
-
-// ======================================================================================
-// circuits, proving, data formats
-// ======================================================================================
-#include "circuit_io.h"
-#include "circuit_bytes.h"
-#include "json_io.h"
-#include "p3_circuit.h"
-#include "p3_prover.h"
-#include "prover.h"
-#include "recursion.h"
-
-struct p25_circuit {
-  p25::Circuit circuit;                       // host tables (moved into dev on first device use)
-  std::unique_ptr<p25::DeviceCircuit> dev;
-  std::unique_ptr<p25::WitnessProgram> wp_info;
-  bool moved = false;
-  int streams = 16;  // proofs in flight (p25_circuit_set_streams)
-  // Entry points that touch the device state of ONE circuit are serialised: upstream's `prove(&self)` is re-entrant,
-  // so a host with a thread pool may call into the same circuit concurrently; here those calls queue up instead of
-  // racing for the circuit's streams and contexts.  Different circuits never contend.
-  mutable std::recursive_mutex mu;   // mutable: the read-only entry points (const handles) lock too
-  const p25::Circuit& c() const { return dev ? dev->circuit() : circuit; }
-  p25::DeviceCircuit& device() {
-    if (!dev) {
-      dev.reset(new p25::DeviceCircuit(std::move(circuit)));
-      dev->set_streams(streams);
-      moved = true;
-    }
-    return *dev;
-  }
-};
-#define P25_LOCK(c) std::lock_guard<std::recursive_mutex> p25_lock_((c)->mu)
-
-template <class F>
-static p25_status host_guarded(F&& f) {
-  try {
-    return f();
-  } catch (const p25::HipError& e) {
-    p25::g_last_error = e.what();
-    return P25_ERR_HIP;
-  } catch (const std::invalid_argument& e) {
-    p25::g_last_error = e.what();
-    return P25_ERR_INVALID_ARG;
-  } catch (const std::exception& e) {
-    p25::g_last_error = e.what();
-    return P25_ERR_INTERNAL;
-  }
+p25_status p25_poseidon_permute_dev(uint64_t* d_states, size_t n, void* stream) {
+  return guarded([&]() -> p25_status {
+    launch_poseidon_permute(d_states, n, (hipStream_t)stream);
+    P25_HIP(hipGetLastError());
+    return P25_OK;
+  });
 }
 
-extern "C" {
-
-static p25::P3Config checked_p3_config(const p25_p3_config* cfg) {
-  // one quotient chunk is the reference's proof model (proof.rs:41-48); two (constraint degree 3) is the round-5 extension,
-  // four / eight (degree 4-5 / 6-9, with log_blowup 2 / 3) round 6's
-  if (cfg->log_quotient_degree < 0 || cfg->log_quotient_degree > 3)
-    throw std::invalid_argument("1, 2, 4 or 8 quotient chunks are supported (log_quotient_degree 0..3)");
-  if (cfg->log_quotient_degree > cfg->log_blowup) throw std::invalid_argument("log_quotient_degree above log_blowup");
-  if (cfg->opening_matrix_log_max_height != cfg->log_trace_height + cfg->log_blowup)
-    throw std::invalid_argument("opening_matrix_log_max_height must be log_trace_height + log_blowup");
-  if (cfg->trace_width < 1 || cfg->trace_width > 64 || cfg->log_trace_height < 1 || cfg->log_trace_height > 24 ||
-      cfg->num_queries < 1 || cfg->num_queries > 1000 || cfg->degree_bits < 1 || cfg->degree_bits > cfg->log_trace_height ||
-      cfg->opening_matrix_log_max_height < 1 || cfg->opening_matrix_log_max_height > 30 || cfg->quotient_opened_len < 1 ||
-      cfg->log_blowup < 1 || cfg->log_blowup > 4 || cfg->proof_of_work_bits < 0 || cfg->proof_of_work_bits > 32)
-    throw std::invalid_argument("p25_p3_config out of range");
-  p25::P3Config pc;
-  pc.fri_config.log_blowup = cfg->log_blowup;
-  pc.fri_config.num_queries = cfg->num_queries;
-  pc.fri_config.proof_of_work_bits = cfg->proof_of_work_bits;
-  pc.log_quotient_degree = cfg->log_quotient_degree;
-  pc.log_trace_height = cfg->log_trace_height;
-  pc.trace_width = cfg->trace_width;
-  pc.opening_matrix_log_max_height = cfg->opening_matrix_log_max_height;
-  pc.opening_proof_query_openings_opened_values_length = cfg->quotient_opened_len;
-  pc.degree_bits = cfg->degree_bits;
-  return pc;
-}
-static p25::AirProgram air_from_c(const p25_air* air) {
-  if (!air || !air->nodes || !air->constraints) throw std::invalid_argument("null AIR");
-  if (air->n_nodes > (1u << 20) || air->n_constraints > (1u << 16)) throw std::invalid_argument("AIR too large");
-  p25::AirProgram p;
-  p.width = (int)air->width;
-  for (uint32_t i = 0; i < air->n_nodes; i++)
-    p.nodes.push_back(p25::AirProgram::Node{air->nodes[i].op, air->nodes[i].a, air->nodes[i].b, air->nodes[i].value});
-  for (uint32_t i = 0; i < air->n_constraints; i++)
-    p.constraints.push_back(p25::AirProgram::Constraint{air->constraints[i].node, air->constraints[i].when});
-  p.validate();
-  return p;
-}
-static p25_status build_verifier(const p25_p3_config* cfg, const p25::Air& air, p25_circuit** out) {
-  p25::P3Config pc = checked_p3_config(cfg);
-  if (pc.trace_width != air.width()) throw std::invalid_argument("Invalid Proof Shape");
-  p25::CircuitBuilder cb;
-  p25::p3_verify_proof(cb, pc, air);
-  auto* h = new p25_circuit();
-  h->circuit = cb.build();
-  *out = h;
-  return P25_OK;
-}
-
+// ---- circuits: the plonky3 verifier circuit, its native provers, gadgets --------------------------------------------
 p25_status p25_circuit_build_p3_verifier(const p25_p3_config* cfg, int32_t air, p25_circuit** out) {
   return host_guarded([&]() -> p25_status {
     if (!cfg || !out) throw std::invalid_argument("null argument");
     if (air != P25_AIR_FIBONACCI) throw std::invalid_argument("unknown AIR");
-    p25::FibonacciAir fib;
+    FibonacciAir fib;
     return build_verifier(cfg, fib, out);
   });
 }
 p25_status p25_circuit_build_p3_verifier_air(const p25_p3_config* cfg, const p25_air* air, p25_circuit** out) {
   return host_guarded([&]() -> p25_status {
     if (!cfg || !air || !out) throw std::invalid_argument("null argument");
-    p25::AirProgram prog = air_from_c(air);
+    AirProgram prog = air_from_c(air);
     // the chunk count follows from the AIR (uni-stark get_log_quotient_degree): the shape must say the same
     if (prog.log_quotient_degree() != cfg->log_quotient_degree)
       throw std::invalid_argument("an AIR of constraint degree " + std::to_string(prog.max_constraint_degree()) + " has 2^" +
                                   std::to_string(prog.log_quotient_degree()) + " quotient chunks: log_quotient_degree must say so");
-    p25::ProgramAir pa(std::move(prog));
+    ProgramAir pa(std::move(prog));
     return build_verifier(cfg, pa, out);
+  });
+}
+
+p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t num_queries,
+                            int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
+                            size_t* n_out, p25_p3_config* cfg_out) {
+  return p25_p3_prove_air_ex(air, trace, log_n, 1, num_queries, pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
+}
+p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t log_blowup, int32_t num_queries,
+                               int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
+                               size_t* n_out, p25_p3_config* cfg_out) {
+  return host_guarded([&]() -> p25_status {
+    if (!air || !n_out) throw std::invalid_argument("null argument");
+    AirProgram prog = air_from_c(air);
+    if (log_blowup < 1 || log_blowup > 4) throw std::invalid_argument("log_blowup must be 1..4");
+    if (prog.log_quotient_degree() > log_blowup)
+      throw std::invalid_argument("an AIR of constraint degree " + std::to_string(prog.max_constraint_degree()) + " needs log_blowup >= " +
+                                  std::to_string(prog.log_quotient_degree()));
+    const P3ProveParams prm{log_n, log_blowup, num_queries, pow_bits, pow_start, threads < 1 ? 1 : threads};
+    P3Config pc = p3_shape(prm);
+    pc.trace_width = prog.width;
+    pc.log_quotient_degree = prog.log_quotient_degree();   // the number of quotient chunks follows from the AIR's degree (p3_prove_air)
+    auto prove = [&]() -> std::vector<u64> {
+      if (!trace) throw std::invalid_argument("null trace");
+      if (log_n < 1 || log_n > 22) throw std::invalid_argument("bad parameters");
+      const size_t n = (size_t)1 << log_n;
+      std::vector<std::vector<u64>> col(prog.width, std::vector<u64>(n));
+      for (size_t r = 0; r < n; r++)
+        for (int c = 0; c < prog.width; c++) col[c][r] = trace[r * prog.width + c];
+      try {
+        return p3_prove_air(prog, col, prm, pc);
+      } catch (const std::logic_error& e) {  // "quotient identity does not hold": the trace violates the AIR
+        throw std::invalid_argument(e.what());
+      }
+    };
+    return p3_prove_out(prm, pc, prove, inputs_out, cap, n_out, cfg_out);
   });
 }
 
 p25_status p25_circuit_build_gadget(int32_t kind, int32_t param, p25_circuit** out) {
   return host_guarded([&]() -> p25_status {
     if (!out) throw std::invalid_argument("null argument");
-    auto* h = new p25_circuit();
-    try {
-      h->circuit = p25::build_gadget_circuit(kind, param);
-    } catch (...) {
-      delete h;
-      throw;
-    }
-    *out = h;
-    return P25_OK;
+    return new_circuit(out, [&] { return build_gadget_circuit(kind, param); });
   });
 }
 
-p25_status p25_circuit_build_gate_eval(int32_t kind, p25_circuit** out) {
-  return host_guarded([&]() -> p25_status {
-    if (!out) throw std::invalid_argument("null argument");
-    if (kind < 0 || kind >= p25::G_NUM_KINDS) throw std::invalid_argument("unknown gate kind");
-    auto* h = new p25_circuit();
-    try {
-      h->circuit = p25::build_gate_eval_circuit((p25::GateKind)kind);
-    } catch (...) {
-      delete h;
-      throw;
-    }
-    *out = h;
-    return P25_OK;
-  });
-}
-static p25_status build_recursive(p25_circuit* inner, const uint64_t* digest4, const uint64_t* cs_cap, int32_t n_proofs,
-                                  bool expose_commitment, p25_circuit** out) {
-  auto body = [&]() -> p25_status {
-    if (!inner || !out) throw std::invalid_argument("null argument");
-    if ((digest4 == nullptr) != (cs_cap == nullptr)) throw std::invalid_argument("pass both digest4 and cs_cap, or neither");
-    P25_LOCK(inner);   // reads inner->c(): another thread's first device use moves the host tables
-    const p25::Circuit& ic = inner->c();
-    uint64_t dg[4];
-    std::vector<u64> cap((size_t)4 << ic.cfg.cap_height);
-    if (digest4) {
-      memcpy(dg, digest4, 32);
-      memcpy(cap.data(), cs_cap, cap.size() * 8);
-      for (u64 v : cap)
-        if (v >= gl::P) throw std::invalid_argument("non-canonical cap word");
-      for (u64 v : dg)
-        if (v >= gl::P) throw std::invalid_argument("non-canonical digest word");
-    } else {
-      p25::DeviceCircuit& d = inner->device();  // needs the GPU: commits the constants/sigmas polynomials
-      memcpy(dg, d.digest(), 32);
-      cap = d.cs_cap();
-    }
-    auto* h = new p25_circuit();
-    try {
-      h->circuit = p25::build_recursive_verifier(inner->c(), dg, cap, n_proofs, expose_commitment);
-    } catch (...) {
-      delete h;
-      throw;
-    }
-    *out = h;
-    return P25_OK;
-  };
-  return digest4 ? host_guarded(body) : guarded(body);
-}
+// ---- recursion; circuit data: export / import, info, digest ---------------------------------------------------------
 p25_status p25_circuit_build_recursive_verifier(p25_circuit* inner, const uint64_t* digest4, const uint64_t* cs_cap,
                                                 int32_t n_proofs, p25_circuit** out) {
   return build_recursive(inner, digest4, cs_cap, n_proofs, false, out);
+}
+p25_status p25_circuit_build_gate_eval(int32_t kind, p25_circuit** out) {
+  return host_guarded([&]() -> p25_status {
+    if (!out) throw std::invalid_argument("null argument");
+    if (kind < 0 || kind >= G_NUM_KINDS) throw std::invalid_argument("unknown gate kind");
+    return new_circuit(out, [&] { return build_gate_eval_circuit((GateKind)kind); });
+  });
 }
 p25_status p25_circuit_build_aggregator(p25_circuit* inner, const uint64_t* digest4, const uint64_t* cs_cap,
                                         int32_t n_proofs, p25_circuit** out) {
@@ -527,96 +630,63 @@ p25_status p25_circuit_build_aggregator(p25_circuit* inner, const uint64_t* dige
 }
 
 p25_status p25_circuit_export(const p25_circuit* c, uint8_t* buf, size_t cap, size_t* len_out) {
-  return host_guarded([&]() -> p25_status {
-    if (!c || !len_out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    std::vector<uint8_t> b = p25::circuit_to_blob(c->c());
-    *len_out = b.size();
-    if (buf) {
-      if (cap < b.size()) throw std::invalid_argument("buffer too small");
-      memcpy(buf, b.data(), b.size());
-    }
-    return P25_OK;
-  });
-}
-p25_status p25_circuit_to_bytes(p25_circuit* c, uint8_t** bytes_out, size_t* len_out) {
-  return guarded([&]() -> p25_status {
-    if (!c || !bytes_out || !len_out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    p25::DeviceCircuit& d = c->device();   // the constants/sigmas commitment is computed on the GPU
-    std::vector<u64> coeffs, lde, tree;
-    d.commitment_to_host(coeffs, lde, tree);
-    p25::CircuitCommitment cm;
-    cm.coeffs = coeffs.data();
-    cm.lde = lde.data();
-    cm.tree = tree.data();
-    memcpy(cm.digest, d.digest(), 32);
-    cm.public_inputs = d.circuit().public_inputs;
-    std::vector<uint8_t> b = p25::circuit_data_to_bytes(d.circuit(), cm);
-    uint8_t* m = (uint8_t*)malloc(b.size() ? b.size() : 1);
-    if (!m) throw std::runtime_error("out of host memory");
-    memcpy(m, b.data(), b.size());
-    *bytes_out = m;
-    *len_out = b.size();
-    return P25_OK;
-  });
-}
-void p25_free(void* p) { free(p); }
-p25_status p25_circuit_from_bytes(const uint8_t* bytes, size_t len, const uint32_t* input_targets, size_t n_inputs,
-                                  uint64_t* digest4_out, p25_circuit** out) {
-  return host_guarded([&]() -> p25_status {
-    if (!bytes || !out || (!input_targets && n_inputs)) throw std::invalid_argument("null argument");
-    auto* h = new p25_circuit();
-    try {
-      u64 dg[4];
-      h->circuit = p25::circuit_data_from_bytes(bytes, len, input_targets, n_inputs, dg);
-      if (digest4_out) memcpy(digest4_out, dg, 32);
-    } catch (...) {
-      delete h;
-      throw;
-    }
-    *out = h;
-    return P25_OK;
-  });
-}
-p25_status p25_circuit_input_targets(const p25_circuit* c, uint32_t* targets_out, size_t cap, size_t* n_out) {
-  return host_guarded([&]() -> p25_status {
-    if (!c || !n_out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    const p25::Circuit& k = c->c();
-    *n_out = k.input_targets.size();
-    if (targets_out) {
-      if (cap < k.input_targets.size()) throw std::invalid_argument("buffer too small");
-      for (size_t i = 0; i < k.input_targets.size(); i++) targets_out[i] = (uint32_t)k.target_index(k.input_targets[i]);
-    }
-    return P25_OK;
+  return with_circuit(c, len_out, [&](const Circuit& k) {
+    const std::vector<uint8_t> b = circuit_to_blob(k);
+    return copy_out(b.data(), b.size(), buf, cap, len_out);
   });
 }
 p25_status p25_circuit_import(const uint8_t* blob, size_t len, p25_circuit** out) {
   return host_guarded([&]() -> p25_status {
     if (!blob || !out) throw std::invalid_argument("null argument");
-    auto* h = new p25_circuit();
-    try {
-      h->circuit = p25::circuit_from_blob(blob, len);
-    } catch (...) {
-      delete h;
-      throw;
-    }
-    *out = h;
-    return P25_OK;
+    return new_circuit(out, [&] { return circuit_from_blob(blob, len); });
   });
 }
+p25_status p25_circuit_to_bytes(p25_circuit* c, uint8_t** bytes_out, size_t* len_out) {
+  return with_device(c, bytes_out && len_out, [&](DeviceCircuit& d) {   // the constants/sigmas commitment is computed on the GPU
+    std::vector<u64> coeffs, lde, tree;
+    d.commitment_to_host(coeffs, lde, tree);
+    CircuitCommitment cm;
+    cm.coeffs = coeffs.data();
+    cm.lde = lde.data();
+    cm.tree = tree.data();
+    memcpy(cm.digest, d.digest(), 32);
+    cm.public_inputs = d.circuit().public_inputs;
+    std::vector<uint8_t> b = circuit_data_to_bytes(d.circuit(), cm);
+    uint8_t* m = (uint8_t*)malloc(b.size() ? b.size() : 1);
+    if (!m) throw std::runtime_error("out of host memory");
+    memcpy(m, b.data(), b.size());
+    *bytes_out = m;
+    *len_out = b.size();
+  });
+}
+p25_status p25_circuit_from_bytes(const uint8_t* bytes, size_t len, const uint32_t* input_targets, size_t n_inputs,
+                                  uint64_t* digest4_out, p25_circuit** out) {
+  return host_guarded([&]() -> p25_status {
+    if (!bytes || !out || (!input_targets && n_inputs)) throw std::invalid_argument("null argument");
+    return new_circuit(out, [&] {
+      u64 dg[4];
+      Circuit k = circuit_data_from_bytes(bytes, len, input_targets, n_inputs, dg);
+      if (digest4_out) memcpy(digest4_out, dg, 32);
+      return k;
+    });
+  });
+}
+p25_status p25_circuit_input_targets(const p25_circuit* c, uint32_t* targets_out, size_t cap, size_t* n_out) {
+  return with_circuit(c, n_out, [&](const Circuit& k) {
+    std::vector<uint32_t> t(k.input_targets.size());
+    for (size_t i = 0; i < t.size(); i++) t[i] = (uint32_t)k.target_index(k.input_targets[i]);
+    return copy_out(t.data(), t.size(), targets_out, cap, n_out);
+  });
+}
+void p25_free(void* p) { free(p); }
 void p25_circuit_destroy(p25_circuit* c) { delete c; }
 
 p25_status p25_circuit_info(p25_circuit* c, p25_circuit_info_t* out) {
-  return host_guarded([&]() -> p25_status {
-    if (!c || !out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);   // reads c->c() and builds wp_info lazily: serialised with a concurrent first prove()
-    const p25::Circuit& k = c->c();
+  return with_circuit(c, out, [&](const Circuit& k) {   // builds wp_info lazily: serialised with a concurrent first prove()
     memset(out, 0, sizeof(*out));
     out->degree_bits = k.degree_bits;
     size_t used = 0;
-    for (auto& r : k.rows) used += r.kind != p25::G_NOOP;
+    for (auto& r : k.rows) used += r.kind != G_NOOP;
     out->num_rows_used = used;
     out->num_wires = k.cfg.num_wires;
     out->num_routed_wires = k.cfg.num_routed_wires;
@@ -626,8 +696,8 @@ p25_status p25_circuit_info(p25_circuit* c, p25_circuit_info_t* out) {
     out->num_selectors = k.num_selectors;
     out->num_constants_sigmas = k.constants_sigmas.size();
     out->num_gate_constraints = k.num_gate_constraints;
-    out->proof_words = p25::make_proof_layout(k).total;
-    if (!c->wp_info) c->wp_info.reset(new p25::WitnessProgram(p25::build_witness_program(k)));
+    out->proof_words = make_proof_layout(k).total;
+    if (!c->wp_info) c->wp_info.reset(new WitnessProgram(build_witness_program(k)));
     out->witness_levels = c->wp_info->level_start.size() - 1;
     out->witness_slots = c->wp_info->num_slots;
     out->num_random_fill = c->wp_info->num_random_fill;
@@ -639,17 +709,14 @@ p25_status p25_circuit_info(p25_circuit* c, p25_circuit_info_t* out) {
   });
 }
 p25_status p25_circuit_gate_counts(const p25_circuit* c, uint64_t* counts_out, size_t cap, char* ids_out, size_t ids_cap) {
-  return host_guarded([&]() -> p25_status {
-    if (!c || !counts_out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    const p25::Circuit& k = c->c();
-    if (cap < k.gates.size()) throw std::invalid_argument("buffer too small");
+  return with_circuit(c, counts_out, [&](const Circuit& k) {
+    check_cap(cap, k.gates.size());
     std::string ids;
     for (size_t i = 0; i < k.gates.size(); i++) {
       size_t n = 0;
       for (auto& r : k.rows) n += r.kind == k.gates[i];
       counts_out[i] = n;
-      ids += p25::gate_info(k.gates[i]).id;
+      ids += gate_info(k.gates[i]).id;
       ids += '\n';
     }
     if (ids_out && ids_cap) snprintf(ids_out, ids_cap, "%s", ids.c_str());
@@ -657,23 +724,13 @@ p25_status p25_circuit_gate_counts(const p25_circuit* c, uint64_t* counts_out, s
   });
 }
 p25_status p25_circuit_digest(p25_circuit* c, uint64_t* digest4, uint64_t* cs_cap) {
-  return guarded([&]() -> p25_status {
-    if (!c || !digest4) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    p25::DeviceCircuit& d = c->device();
+  return with_device(c, digest4 != nullptr, [&](DeviceCircuit& d) {
     memcpy(digest4, d.digest(), 32);
     if (cs_cap) memcpy(cs_cap, d.cs_cap().data(), d.cs_cap().size() * 8);
-    return P25_OK;
   });
 }
 
-static void fill_timings(p25_timings* t, const p25::PhaseTimes& pt) {
-  if (!t) return;
-  t->witness_ms = pt.witness; t->wires_commit_ms = pt.wires_commit; t->partial_products_ms = pt.zs_pp;
-  t->zs_commit_ms = pt.zs_commit; t->quotient_ms = pt.quotient; t->quotient_commit_ms = pt.quotient_commit;
-  t->openings_ms = pt.openings; t->fri_ms = pt.fri; t->total_ms = pt.total;
-}
-
+// ---- proving --------------------------------------------------------------------------------------------------------
 p25_status p25_prove_batch(p25_circuit* c, const uint64_t* inputs, size_t n_proofs, const uint64_t* seeds,
                            uint64_t* proofs_out, size_t proof_stride_words, p25_status* per_proof_status,
                            p25_timings* timings) {
@@ -681,7 +738,7 @@ p25_status p25_prove_batch(p25_circuit* c, const uint64_t* inputs, size_t n_proo
     if (!c || !inputs || !proofs_out || !per_proof_status) throw std::invalid_argument("null argument");
     P25_LOCK(c);
     if (!n_proofs) return P25_OK;
-    p25::PhaseTimes pt;
+    PhaseTimes pt;
     c->device().prove_batch(inputs, n_proofs, seeds, proofs_out, proof_stride_words, per_proof_status, timings ? &pt : nullptr);
     fill_timings(timings, pt);
     return P25_OK;
@@ -699,15 +756,11 @@ p25_status p25_prove_batch_filler(p25_circuit* c, const uint64_t* inputs, size_t
 }
 p25_status p25_prove_batch_dev(p25_circuit* c, const uint64_t* d_inputs, size_t n_proofs, const uint64_t* d_seeds,
                                uint64_t* d_proofs, size_t proof_stride_words, uint32_t* d_status, p25_timings* timings) {
-  return guarded([&]() -> p25_status {
-    if (!c || !d_inputs || !d_seeds || !d_proofs || !d_status) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    p25::DeviceCircuit& d = c->device();
+  return with_device(c, d_inputs && d_seeds && d_proofs && d_status, [&](DeviceCircuit& d) {
     if (proof_stride_words < d.layout().total) throw std::invalid_argument("proof_stride smaller than the proof");
-    p25::PhaseTimes pt;
+    PhaseTimes pt;
     d.prove_batch_dev(d_inputs, n_proofs, d_seeds, d_proofs, proof_stride_words, d_status, timings ? &pt : nullptr);
     fill_timings(timings, pt);
-    return P25_OK;
   });
 }
 p25_status p25_prove_batch_dev_windows(p25_circuit* c, const uint64_t* d_buffer, size_t window_stride_words,
@@ -722,62 +775,24 @@ p25_status p25_prove_batch_dev_windows(p25_circuit* c, const uint64_t* d_buffer,
     if (n_proofs && last_window_offset_words > (n_proofs - 1) * window_stride_words)
       throw std::invalid_argument("last window lies beyond the windows before it");
     P25_LOCK(c);
-    p25::DeviceCircuit& d = c->device();
+    DeviceCircuit& d = c->device();
     if (proof_stride_words < d.layout().total) throw std::invalid_argument("proof_stride smaller than the proof");
     d.prove_batch_dev(d_buffer, n_proofs, d_seeds, d_proofs, proof_stride_words, d_status, nullptr, nullptr,
                       window_stride_words, last_window_offset_words);
     return P25_OK;
   });
 }
-p25_status p25_circuit_set_streams(p25_circuit* c, int32_t n_streams) {
-  return host_guarded([&]() -> p25_status {
-    if (!c) throw std::invalid_argument("null argument");
-    if (n_streams < 1 || n_streams > 32) throw std::invalid_argument("n_streams must be in 1..32");
-    P25_LOCK(c);
-    c->streams = n_streams;
-    if (c->dev) c->dev->set_streams(n_streams);
-    return P25_OK;
-  });
-}
 p25_status p25_circuit_sync(p25_circuit* c) {
-  return guarded([&]() -> p25_status {
-    if (!c) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    c->device().sync();
-    return P25_OK;
-  });
+  return with_device(c, [&](DeviceCircuit& d) { d.sync(); });
 }
 p25_status p25_circuit_stream_join(p25_circuit* c, void* stream) {
-  return guarded([&]() -> p25_status {
-    if (!c) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    c->device().stream_join((hipStream_t)stream);
-    return P25_OK;
-  });
+  return with_device(c, [&](DeviceCircuit& d) { d.stream_join((hipStream_t)stream); });
 }
 p25_status p25_circuit_wait_stream(p25_circuit* c, void* stream) {
-  return guarded([&]() -> p25_status {
-    if (!c) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    c->device().wait_stream((hipStream_t)stream);
-    return P25_OK;
-  });
+  return with_device(c, [&](DeviceCircuit& d) { d.wait_stream((hipStream_t)stream); });
 }
 p25_status p25_circuit_mark(p25_circuit* c, uint32_t slot) {
-  return guarded([&]() -> p25_status {
-    if (!c) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    c->device().mark((int)slot);
-    return P25_OK;
-  });
-}
-p25_status p25_circuit_stream_wait_mark(p25_circuit* c, uint32_t slot, void* stream) {
-  return guarded([&]() -> p25_status {
-    if (!c) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    c->device().stream_wait_mark((hipStream_t)stream, (int)slot);
-    return P25_OK;
-  });
+  return with_device(c, [&](DeviceCircuit& d) { d.mark((int)slot); });
 }
 p25_status p25_circuit_wait_mark(p25_circuit* c, p25_circuit* producer, uint32_t slot) {
   return guarded([&]() -> p25_status {
@@ -789,28 +804,42 @@ p25_status p25_circuit_wait_mark(p25_circuit* c, p25_circuit* producer, uint32_t
     return P25_OK;
   });
 }
-p25_status p25_circuit_kernel_stats(p25_circuit* c, int enable, int reset, double* ms_out, uint64_t* launches_out) {
-  return guarded([&]() -> p25_status {
+p25_status p25_circuit_stream_wait_mark(p25_circuit* c, uint32_t slot, void* stream) {
+  return with_device(c, [&](DeviceCircuit& d) { d.stream_wait_mark((hipStream_t)stream, (int)slot); });
+}
+p25_status p25_circuit_set_streams(p25_circuit* c, int32_t n_streams) {
+  return host_guarded([&]() -> p25_status {
     if (!c) throw std::invalid_argument("null argument");
+    if (n_streams < 1 || n_streams > 32) throw std::invalid_argument("n_streams must be in 1..32");
     P25_LOCK(c);
-    p25::DeviceCircuit& d = c->device();
+    c->streams = n_streams;
+    if (c->dev) c->dev->set_streams(n_streams);
+    return P25_OK;
+  });
+}
+p25_status p25_circuit_kernel_stats(p25_circuit* c, int enable, int reset, double* ms_out, uint64_t* launches_out) {
+  return with_device(c, [&](DeviceCircuit& d) {
     d.kernel_stats_enable(enable != 0);
     u64 n = 0;
     d.kernel_stats(ms_out, &n, reset != 0);
     if (launches_out) *launches_out = n;
+  });
+}
+p25_status p25_shader_clock_hz(double* hz_out) {
+  return guarded([&]() -> p25_status {
+    if (!hz_out) throw std::invalid_argument("hz_out is null");
+    *hz_out = measure_shader_clock_hz(0);
     return P25_OK;
   });
 }
 p25_status p25_witness(p25_circuit* c, const uint64_t* inputs, uint64_t seed, uint64_t* wires_out, p25_status* proof_status) {
-  return guarded([&]() -> p25_status {
-    if (!c || !inputs || !wires_out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    int32_t st = c->device().witness(inputs, seed, wires_out);
+  return with_device(c, inputs && wires_out, [&](DeviceCircuit& d) {
+    const int32_t st = d.witness(inputs, seed, wires_out);
     if (proof_status) *proof_status = st;
-    return P25_OK;
   });
 }
 
+// ---- stages of the prover on their own ------------------------------------------------------------------------------
 p25_status p25_transcript(const uint64_t* observe, const uint32_t* seg_len, const uint32_t* n_challenges,
                           size_t n_segments, uint64_t* challenges_out) {
   return guarded([&]() -> p25_status {
@@ -818,27 +847,19 @@ p25_status p25_transcript(const uint64_t* observe, const uint32_t* seg_len, cons
     size_t n_obs = 0;
     for (size_t k = 0; k < n_segments; k++) n_obs += seg_len[k];
     if (n_obs && !observe) throw std::invalid_argument("null argument");
-    p25::transcript_script(observe, seg_len, n_challenges, n_segments, challenges_out);
+    transcript_script(observe, seg_len, n_challenges, n_segments, challenges_out);
     return P25_OK;
   });
 }
 p25_status p25_partial_products(p25_circuit* c, const uint64_t* wires, const uint64_t* betas, const uint64_t* gammas,
                                 uint64_t* out) {
-  return guarded([&]() -> p25_status {
-    if (!c || !wires || !betas || !gammas || !out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    c->device().partial_products(wires, betas, gammas, out);
-    return P25_OK;
-  });
+  return with_device(c, wires && betas && gammas && out,
+                     [&](DeviceCircuit& d) { d.partial_products(wires, betas, gammas, out); });
 }
 p25_status p25_quotient(p25_circuit* c, const uint64_t* wires, const uint64_t* zs_pp, const uint64_t* betas,
                         const uint64_t* gammas, const uint64_t* alphas, uint64_t* out) {
-  return guarded([&]() -> p25_status {
-    if (!c || !wires || !zs_pp || !betas || !gammas || !alphas || !out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    c->device().quotient(wires, zs_pp, betas, gammas, alphas, out);
-    return P25_OK;
-  });
+  return with_device(c, wires && zs_pp && betas && gammas && alphas && out,
+                     [&](DeviceCircuit& d) { d.quotient(wires, zs_pp, betas, gammas, alphas, out); });
 }
 p25_status p25_eval_polys(const uint64_t* coeffs, size_t n_polys, unsigned log_n, const uint64_t* point, uint64_t scale,
                           uint64_t* out) {
@@ -853,251 +874,85 @@ p25_status p25_eval_polys(const uint64_t* coeffs, size_t n_polys, unsigned log_n
     DevBuf d_c(n_polys * n), d_pt(2), d_scr(2 * 1026 + 2 * n_polys * chunks), d_out(2 * n_polys);
     P25_HIP(hipMemcpy(d_c.p, coeffs, n_polys * n * 8, hipMemcpyHostToDevice));
     P25_HIP(hipMemcpy(d_pt.p, point, 16, hipMemcpyHostToDevice));
-    p25::launch_eval_polys(d_c.p, (uint32_t)n_polys, log_n, d_pt.p, scale, d_scr.p, d_out.p, 0);
+    launch_eval_polys(d_c.p, (uint32_t)n_polys, log_n, d_pt.p, scale, d_scr.p, d_out.p, 0);
     P25_HIP(hipGetLastError());
     P25_HIP(hipMemcpy(out, d_out.p, 2 * n_polys * 8, hipMemcpyDeviceToHost));
     return P25_OK;
   });
 }
-static bool fri_shape_from_c(unsigned log_n, unsigned rate_bits, unsigned cap_height, const int32_t* arity_bits,
-                             size_t n_layers, unsigned pow_bits, unsigned num_queries, p25::FriShape& sh) {
-  if (log_n < 1 || log_n > 22 || rate_bits > 3 || cap_height > 16 || n_layers > 8 || (n_layers && !arity_bits) ||
-      num_queries < 1 || num_queries > 64 || pow_bits > 32)
-    return false;
-  sh.log_n = (int)log_n;
-  sh.rate_bits = (int)rate_bits;
-  sh.cap_height = cap_height;
-  sh.arity_bits.assign(arity_bits, arity_bits + n_layers);
-  sh.pow_bits = (int)pow_bits;
-  sh.num_queries = (int)num_queries;
-  int deg = (int)log_n, bits = (int)(log_n + rate_bits);
-  if (bits < (int)cap_height) return false;
-  for (int a : sh.arity_bits) {
-    if (a < 1 || a > 8) return false;
-    deg -= a;
-    bits -= a;
-    if (deg < 0 || bits < (int)cap_height) return false;
-  }
-  return true;
-}
 size_t p25_fri_prove_words(unsigned log_n, unsigned rate_bits, unsigned cap_height, const int32_t* arity_bits,
                            size_t n_layers, unsigned num_queries) {
-  p25::FriShape sh;
+  FriShape sh;
   if (!fri_shape_from_c(log_n, rate_bits, cap_height, arity_bits, n_layers, 0, num_queries, sh)) return 0;
-  return p25::fri_prove_words(sh);
+  return fri_prove_words(sh);
 }
 p25_status p25_fri_prove(const uint64_t* coeffs, unsigned log_n, unsigned rate_bits, unsigned cap_height,
                          const int32_t* arity_bits, size_t n_layers, unsigned pow_bits, unsigned num_queries,
                          const uint64_t* seed, size_t n_seed, uint64_t* out, size_t out_cap, p25_status* status_out) {
   return guarded([&]() -> p25_status {
     if (!coeffs || !out || !status_out || (n_seed && !seed)) throw std::invalid_argument("null argument");
-    p25::FriShape sh;
+    FriShape sh;
     if (!fri_shape_from_c(log_n, rate_bits, cap_height, arity_bits, n_layers, pow_bits, num_queries, sh))
       throw std::invalid_argument("p25_fri_prove: bad shape");
-    if (out_cap < p25::fri_prove_words(sh)) throw std::invalid_argument("buffer too small");
+    check_cap(out_cap, fri_prove_words(sh));
     std::lock_guard<std::mutex> lk(g_primitives_mutex);
     int32_t st = 0;
-    p25::fri_prove_standalone(tables(), coeffs, sh, seed, n_seed, out, &st);
+    fri_prove_standalone(tables(), coeffs, sh, seed, n_seed, out, &st);
     *status_out = st;
     return P25_OK;
   });
 }
 
+// ---- data formats either side of the path ---------------------------------------------------------------------------
 p25_status p25_p3_proof_from_json(const char* json, size_t len, uint64_t* inputs_out, size_t cap, size_t* n_out,
                                   p25_p3_config* cfg_out) {
-  p25_status s = host_guarded([&]() -> p25_status {
+  const p25_status s = host_guarded([&]() -> p25_status {
     if (!json || !n_out) throw std::invalid_argument("null argument");
     std::vector<u64> in;
-    p25::P3Config pc;
-    p25::p3_proof_from_json(json, len, in, pc);
-    *n_out = in.size();
-    if (inputs_out) {
-      if (cap < in.size()) throw std::invalid_argument("buffer too small");
-      memcpy(inputs_out, in.data(), in.size() * 8);
-    }
-    if (cfg_out) {
-      cfg_out->log_blowup = pc.fri_config.log_blowup;
-      cfg_out->num_queries = pc.fri_config.num_queries;
-      cfg_out->proof_of_work_bits = pc.fri_config.proof_of_work_bits;
-      cfg_out->log_quotient_degree = pc.log_quotient_degree;
-      cfg_out->log_trace_height = pc.log_trace_height;
-      cfg_out->trace_width = pc.trace_width;
-      cfg_out->opening_matrix_log_max_height = pc.opening_matrix_log_max_height;
-      cfg_out->quotient_opened_len = pc.opening_proof_query_openings_opened_values_length;
-      cfg_out->degree_bits = pc.degree_bits;
-    }
+    P3Config pc;
+    p3_proof_from_json(json, len, in, pc);
+    copy_out(in.data(), in.size(), inputs_out, cap, n_out);
+    if (cfg_out) *cfg_out = to_c(pc);
     return P25_OK;
   });
-  if (s == P25_ERR_INVALID_ARG && p25::g_last_error.rfind("p3 proof JSON", 0) == 0) return P25_ERR_PARSE;
+  if (s == P25_ERR_INVALID_ARG && g_last_error.rfind("p3 proof JSON", 0) == 0) return P25_ERR_PARSE;
   return s;
 }
-static void cfg_to_c(const p25::P3Config& pc, p25_p3_config* o) {
-  o->log_blowup = pc.fri_config.log_blowup;
-  o->num_queries = pc.fri_config.num_queries;
-  o->proof_of_work_bits = pc.fri_config.proof_of_work_bits;
-  o->log_quotient_degree = pc.log_quotient_degree;
-  o->log_trace_height = pc.log_trace_height;
-  o->trace_width = pc.trace_width;
-  o->opening_matrix_log_max_height = pc.opening_matrix_log_max_height;
-  o->quotient_opened_len = pc.opening_proof_query_openings_opened_values_length;
-  o->degree_bits = pc.degree_bits;
-}
-static p25::P3Config cfg_from_c(const p25_p3_config* c) {
-  p25::P3Config pc;
-  pc.fri_config.log_blowup = c->log_blowup;
-  pc.fri_config.num_queries = c->num_queries;
-  pc.fri_config.proof_of_work_bits = c->proof_of_work_bits;
-  pc.log_quotient_degree = c->log_quotient_degree;
-  pc.log_trace_height = c->log_trace_height;
-  pc.trace_width = c->trace_width;
-  pc.opening_matrix_log_max_height = c->opening_matrix_log_max_height;
-  pc.opening_proof_query_openings_opened_values_length = c->quotient_opened_len;
-  pc.degree_bits = c->degree_bits;
-  return pc;
-}
-
 p25_status p25_p3_prove_fibonacci(int32_t log_n, int32_t num_queries, int32_t pow_bits, uint64_t pow_start,
                                   int32_t threads, uint64_t* inputs_out, size_t cap, size_t* n_out,
                                   p25_p3_config* cfg_out) {
   return host_guarded([&]() -> p25_status {
     if (!n_out) throw std::invalid_argument("null argument");
-    p25::P3ProveParams prm;
-    prm.log_n = log_n;
-    prm.num_queries = num_queries;
-    prm.pow_bits = pow_bits;
-    prm.pow_start = pow_start;
-    prm.threads = threads < 1 ? 1 : threads;
-    p25::P3Config pc;
-    pc.fri_config.num_queries = num_queries;
-    pc.log_trace_height = log_n;
-    pc.opening_matrix_log_max_height = log_n + 1;
-    pc.degree_bits = log_n;
-    if (!inputs_out) {  // size query only
-      if (log_n < 1 || log_n > 22 || num_queries < 1) throw std::invalid_argument("bad parameters");
-      *n_out = pc.num_inputs();
-      if (cfg_out) {
-        pc.fri_config.proof_of_work_bits = pow_bits;
-        cfg_to_c(pc, cfg_out);
-      }
-      return P25_OK;
-    }
-    std::vector<u64> v = p25::p3_prove_fibonacci(prm, pc);
-    *n_out = v.size();
-    if (cap < v.size()) throw std::invalid_argument("buffer too small");
-    memcpy(inputs_out, v.data(), v.size() * 8);
-    if (cfg_out) cfg_to_c(pc, cfg_out);
-    return P25_OK;
-  });
-}
-p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t num_queries,
-                            int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
-                            size_t* n_out, p25_p3_config* cfg_out) {
-  return p25_p3_prove_air_ex(air, trace, log_n, 1, num_queries, pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
-}
-p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t log_blowup, int32_t num_queries,
-                               int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
-                               size_t* n_out, p25_p3_config* cfg_out) {
-  return host_guarded([&]() -> p25_status {
-    if (!air || !n_out) throw std::invalid_argument("null argument");
-    p25::AirProgram prog = air_from_c(air);
-    if (log_blowup < 1 || log_blowup > 4) throw std::invalid_argument("log_blowup must be 1..4");
-    if (prog.log_quotient_degree() > log_blowup)
-      throw std::invalid_argument("an AIR of constraint degree " + std::to_string(prog.max_constraint_degree()) + " needs log_blowup >= " +
-                                  std::to_string(prog.log_quotient_degree()));
-    p25::P3ProveParams prm;
-    prm.log_n = log_n;
-    prm.log_blowup = log_blowup;
-    prm.num_queries = num_queries;
-    prm.pow_bits = pow_bits;
-    prm.pow_start = pow_start;
-    prm.threads = threads < 1 ? 1 : threads;
-    p25::P3Config pc;
-    pc.fri_config.log_blowup = log_blowup;
-    pc.fri_config.num_queries = num_queries;
-    pc.log_trace_height = log_n;
-    pc.trace_width = prog.width;
-    pc.opening_matrix_log_max_height = log_n + log_blowup;
-    pc.degree_bits = log_n;
-    pc.log_quotient_degree = prog.log_quotient_degree();   // the number of quotient chunks follows from the AIR's degree (p3_prove_air)
-    if (!inputs_out) {  // size query only
-      if (log_n < 1 || log_n > 22 || num_queries < 1) throw std::invalid_argument("bad parameters");
-      *n_out = pc.num_inputs();
-      if (cfg_out) {
-        pc.fri_config.proof_of_work_bits = pow_bits;
-        cfg_to_c(pc, cfg_out);
-      }
-      return P25_OK;
-    }
-    if (!trace) throw std::invalid_argument("null trace");
-    if (log_n < 1 || log_n > 22) throw std::invalid_argument("bad parameters");
-    const size_t n = (size_t)1 << log_n;
-    std::vector<std::vector<u64>> col(prog.width, std::vector<u64>(n));
-    for (size_t r = 0; r < n; r++)
-      for (int c = 0; c < prog.width; c++) col[c][r] = trace[r * prog.width + c];
-    std::vector<u64> v;
-    try {
-      v = p25::p3_prove_air(prog, col, prm, pc);
-    } catch (const std::logic_error& e) {  // "quotient identity does not hold": the trace violates the AIR
-      throw std::invalid_argument(e.what());
-    }
-    *n_out = v.size();
-    if (cap < v.size()) throw std::invalid_argument("buffer too small");
-    memcpy(inputs_out, v.data(), v.size() * 8);
-    if (cfg_out) cfg_to_c(pc, cfg_out);
-    return P25_OK;
+    const P3ProveParams prm{log_n, 1, num_queries, pow_bits, pow_start, threads < 1 ? 1 : threads};
+    P3Config pc = p3_shape(prm);
+    return p3_prove_out(prm, pc, [&] { return p3_prove_fibonacci(prm, pc); }, inputs_out, cap, n_out, cfg_out);
   });
 }
 p25_status p25_p3_inputs_to_json(const uint64_t* inputs, size_t n, const p25_p3_config* cfg, char* buf,
                                  size_t cap, size_t* len_out) {
   return host_guarded([&]() -> p25_status {
     if (!inputs || !cfg || !len_out) throw std::invalid_argument("null argument");
-    std::string s = p25::p3_inputs_to_json(std::vector<u64>(inputs, inputs + n), cfg_from_c(cfg));
-    *len_out = s.size();
-    if (buf) {
-      if (cap < s.size()) throw std::invalid_argument("buffer too small");
-      memcpy(buf, s.data(), s.size());
-    }
-    return P25_OK;
+    const std::string s = p3_inputs_to_json(std::vector<u64>(inputs, inputs + n), from_c(cfg));
+    return copy_out(s.data(), s.size(), buf, cap, len_out);
   });
 }
-
 p25_status p25_proof_to_json(p25_circuit* c, const uint64_t* proof, char* buf, size_t cap, size_t* len_out) {
-  return host_guarded([&]() -> p25_status {
-    if (!c || !proof || !len_out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    const p25::Circuit& k = c->c();
-    std::string s = p25::proof_to_json(k, p25::make_proof_layout(k), proof);
-    *len_out = s.size();
-    if (buf) {
-      if (cap < s.size()) throw std::invalid_argument("buffer too small");
-      memcpy(buf, s.data(), s.size());
-    }
-    return P25_OK;
+  return with_circuit(c, proof && len_out, [&](const Circuit& k) {
+    const std::string s = proof_to_json(k, make_proof_layout(k), proof);
+    return copy_out(s.data(), s.size(), buf, cap, len_out);
   });
 }
-
 p25_status p25_proof_to_bytes(p25_circuit* c, const uint64_t* proof, uint8_t* buf, size_t cap, size_t* len_out) {
-  return host_guarded([&]() -> p25_status {
-    if (!c || !proof || !len_out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    const p25::Circuit& k = c->c();
-    std::vector<uint8_t> b = p25::proof_to_bytes(k, p25::make_proof_layout(k), proof);
-    *len_out = b.size();
-    if (buf) {
-      if (cap < b.size()) throw std::invalid_argument("buffer too small");
-      memcpy(buf, b.data(), b.size());
-    }
-    return P25_OK;
+  return with_circuit(c, proof && len_out, [&](const Circuit& k) {
+    const std::vector<uint8_t> b = proof_to_bytes(k, make_proof_layout(k), proof);
+    return copy_out(b.data(), b.size(), buf, cap, len_out);
   });
 }
 p25_status p25_proof_from_bytes(p25_circuit* c, const uint8_t* bytes, size_t len, uint64_t* proof_out, size_t cap_words) {
-  return host_guarded([&]() -> p25_status {
-    if (!c || !bytes || !proof_out) throw std::invalid_argument("null argument");
-    P25_LOCK(c);
-    const p25::Circuit& k = c->c();
-    p25::ProofLayout L = p25::make_proof_layout(k);
-    if (cap_words < L.total) throw std::invalid_argument("buffer too small");
-    p25::proof_from_bytes(k, L, bytes, len, proof_out);
+  return with_circuit(c, bytes && proof_out, [&](const Circuit& k) {
+    const ProofLayout L = make_proof_layout(k);
+    check_cap(cap_words, L.total);
+    proof_from_bytes(k, L, bytes, len, proof_out);
     return P25_OK;
   });
 }

@@ -25,6 +25,7 @@
 namespace p25 {
 extern thread_local std::string g_last_error;
 p25_status ensure_device();
+p25_status status_of_current_exception();   // capi.hip: the ABI's exception -> status mapping
 
 namespace {
 struct Rccl {
@@ -103,15 +104,8 @@ p25_status comm_guarded(F&& f) {
   } catch (const RcclError& e) {
     g_last_error = e.what();
     return P25_ERR_RCCL;
-  } catch (const HipError& e) {
-    g_last_error = e.what();
-    return P25_ERR_HIP;
-  } catch (const std::invalid_argument& e) {
-    g_last_error = e.what();
-    return P25_ERR_INVALID_ARG;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return P25_ERR_INTERNAL;
+  } catch (...) {
+    return status_of_current_exception();
   }
 }
 }  // namespace

@@ -11,11 +11,16 @@ gather of the finished proofs onto rank 0 at the end of each step.
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process BEFORE torch or HIP
 is touched, and exits with the child's code.
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+Prints ONE JSON line on rank 0: the headline (metric, value, unit, higher_is_better, dtype, ms_per_step) and the
+run's shape.  A plain run does only what that line needs: set up, warm up, time the steps, --dump-outputs, print.
+With --full, everything else is measured and checked after the timed steps and added to the same line:
+  config       -- the oracle's verifier on proofs spread over the last step, the single-proof latency by phase
   roofline     -- the dominant kernel (Poseidon leaf sponge over the 2^19 x 135 wires LDE): algorithmic
                   bytes per launch / its duration measured with HIP events on the proving stream, for
                   launches that have the GPU to themselves (the figure rocprofv3 reports per kernel) and,
                   separately, for the launches of the timed region (16 proofs in flight, time-sliced)
+  aggregation  -- the last step's proofs folded to one root proof, and the same tree pipelined under the leaves
+  configs      -- BASELINE configs 2 (single proof) and 5 (2^20-row inner STARK), N = 1 only
   cpu_baseline -- the oracle (CPU restatement, kind "port") on the host cores: one proof on ONE pinned thread (the
                   reference build has no `parallel` feature, Cargo.toml:15-18) and the whole host (independent proofs
                   in flight on all physical cores, 16 threads each).
@@ -32,6 +37,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s
 COLLECTIVE_TIMEOUT_S = 1800   # torch.distributed process-group timeout (RCCL watchdog included)
 N_SIMD, NOMINAL_CLOCK_HZ = 1024, 2.4e9   # 256 CUs x 4 SIMDs; the clock is measured in the run (p25_shader_clock_hz)
+# options of what --full adds after the timed steps: a plain run refuses them rather than ignore them
+FULL_ONLY = ("--verify", "--cpu-baseline", "--no-cpu-baseline", "--cpu-cores", "--aggregate", "--aggregate-arity",
+             "--extra-configs")
 
 
 def parse_args():
@@ -75,9 +83,18 @@ def parse_args():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rank 0: the proofs and statuses of the "
                          "whole step, gathered ones with N > 1) as DIR/<name>.npy, float64, 64 MB at most (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything the headline does not need: the oracle's verifier, the "
+                         "aggregation tree, the roofline / VALU / HBM views, BASELINE configs 2 and 5, the CPU baseline "
+                         "(" + ", ".join(FULL_ONLY) + " shape these)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        for opt in FULL_ONLY:
+            dest = opt[2:].replace("-", "_")
+            if getattr(args, dest) != ap.get_default(dest):
+                ap.error(f"{opt} only applies with --full")
     return args
 
 
@@ -507,7 +524,7 @@ def main():
         step()
     drain()
     gather_host_s[0] = 0.0
-    circuit.kernel_stats(enable=True, reset=True)
+    circuit.kernel_stats(enable=True, reset=True)     # read by --full only, on in every run: the same timed steps either way
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
@@ -549,6 +566,62 @@ def main():
             dump_p, dump_s = last.cpu().numpy().view(np.uint64), d_status_all[n_steps_all - 1].cpu().numpy()
         dump_outputs(args.dump_outputs, np, dump_p, dump_s)
 
+    total_proofs = n_step_total * args.steps
+    out = None
+    if rank == 0:     # the headline line: all that a plain run prints, and what --full adds its blocks to
+        if distributed:
+            gathered_ok = (sum(int(b.shape[0]) for b in gathered[0]) == n_step_total
+                           and all(int((s.cpu() != 0).sum()) == 0 for s in gathered[1]))
+        else:
+            gathered_ok = True
+        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip()
+        out = {
+            "metric": "recursive proofs/sec (fib-64 p3-in-p2 circuit)",
+            "value": total_proofs / elapsed,
+            "unit": "proofs/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong" if args.total else "weak",
+            "vs_baseline": None,
+            "dtype": "u64 (Goldilocks, p = 2^64 - 2^32 + 1)",
+            "data": f"synthetic: {len(variants)} distinct plonky3 proofs of fibonacci(2^{args.log_n}) "
+                    "(item 0 = the reference's artifacts/proof_fibonacci.json for log_n 6; the others from the native "
+                    "p3 prover with other PoW witnesses) cycled through the batch, distinct filler seeds",
+            "config": {"workload": (f"batch of {n_step_total} independent " if args.total else f"batch of {B} independent ")
+                                   + f"{'fib-64' if args.log_n == 6 else f'fibonacci(2^{args.log_n})'} plonky3-verifier proofs "
+                                   + ("sharded over the GPUs " if args.total else "per GPU ") +
+                                   f"(n = 2^{int(info.degree_bits)} rows x 135 wires, LDE 2^{int(info.degree_bits) + 3}), "
+                                   f"{world} GPU(s), replicas + RCCL gather"
+                                   + (" (p25_gather_proofs: librccl behind the C ABI)" if native else "")
+                                   + ("" if args.dist_backend == "nccl" else " [TEST MODE: all ranks on GPU 0, gloo]"),
+                       "proofs_per_gpu_per_step": B, "proofs_per_step_total": n_step_total,
+                       "all_statuses_ok": ok, "gathered_complete_and_ok": gathered_ok,
+                       "circuit_build_s": round(build_s, 2), "head": head, "runtime": p25.runtime_info().as_dict()},
+        }
+        if per_rank:
+            out["per_rank"] = per_rank
+
+    def finish():
+        if rank == 0:
+            # what the other ranks sit out in the final barrier (everything rank 0 did alone since the timed region ended,
+            # the collectives of the aggregation blocks included) against the process group's timeout
+            out["rank0_post_region_s"] = round(time.perf_counter() - t_region_end, 2)
+            out["collective_timeout_s"] = COLLECTIVE_TIMEOUT_S
+            print(json.dumps(out), flush=True)
+        if native:
+            comm.close()
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+
+    # --- --full from here on ------------------------------------------------------------------------------------------
     # --- the batch folded to ONE proof, sharded like the batch (outside the timed region; all ranks take part) ------
     # Every rank folds the first n_agg proofs of ITS last step to one root on its own GPU, the N roots (not the leaves)
     # are gathered over RCCL, rank 0 proves one N-to-1 aggregate on top.  Collectives only where every rank reaches them:
@@ -651,9 +724,8 @@ def main():
         if distributed:
             all_blocks = [b.cpu().numpy().view(np.uint64) for b in gathered[0]]
             all_p = np.concatenate(all_blocks) if all_blocks else np.zeros((0, pw), dtype=np.uint64)
-            gathered_ok = bool(all(int((g.cpu() != 0).sum()) == 0 for g in gathered[1])) and all_p.shape[0] == n_step_total
         else:
-            all_p, gathered_ok = last.cpu().numpy().view(np.uint64), True
+            all_p = last.cpu().numpy().view(np.uint64)
         nver = max(1, min(args.verify, all_p.shape[0]))
         ver_idx = sorted({int(round(k * (all_p.shape[0] - 1) / max(1, nver - 1))) for k in range(nver)})
         ver_fail = []
@@ -667,7 +739,6 @@ def main():
         ms_busy = k_ms_busy / max(1, k_launches_busy)
         achieved = algo_bytes / (ms_alone * 1e-3) / 1e9 if ms_alone > 0 else 0.0
         ms_all = (k_ms_alone + k_ms_busy) / max(1, k_launches_alone + k_launches_busy)
-        head = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip()
         traffic, traffic_note = None, "no PMC file"
         tp = os.path.join(ROOT, "profiles", "pmc_hash_leaves.json")
         if os.path.exists(tp):
@@ -685,7 +756,6 @@ def main():
                     traffic_note = "profiles/pmc_hash_leaves.json was collected for other kernel sources: re-run the PMC passes"
             except Exception:
                 traffic = None
-        total_proofs = n_step_total * args.steps
         # Integer-VALU view of the same run (the bound that actually binds): wave-level VALU instructions
         # per proof from the latest committed PMC pass (SQ_INSTS_VALU, profiles/*_pmc_SQ_INSTS_VALU.json,
         # written by tools/collect_profiles.sh) x proofs/s per GPU, against two ceilings.
@@ -758,56 +828,28 @@ def main():
         hbm_overall = {"alg_GB_per_proof": round(bytes_per_proof / 1e9, 3),
                        "achieved_GBps": round(bytes_per_proof * (total_proofs / elapsed) / world / 1e9, 1),
                        "frac_of_peak": round(bytes_per_proof * (total_proofs / elapsed) / world / 1e9 / HBM_PEAK_GBS, 4)}
-        out = {
-            "metric": "recursive proofs/sec (fib-64 p3-in-p2 circuit)",
-            "value": total_proofs / elapsed,
-            "unit": "proofs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong" if args.total else "weak",
-            "vs_baseline": None,
-            "dtype": "u64 (Goldilocks, p = 2^64 - 2^32 + 1)",
-            "data": f"synthetic: {len(variants)} distinct plonky3 proofs of fibonacci(2^{args.log_n}) "
-                    "(item 0 = the reference's artifacts/proof_fibonacci.json for log_n 6; the others from the native "
-                    "p3 prover with other PoW witnesses) cycled through the batch, distinct filler seeds",
-            "config": {"workload": (f"batch of {n_step_total} independent " if args.total else f"batch of {B} independent ")
-                                   + f"{'fib-64' if args.log_n == 6 else f'fibonacci(2^{args.log_n})'} plonky3-verifier proofs "
-                                   + ("sharded over the GPUs " if args.total else "per GPU ") +
-                                   f"(n = 2^{int(info.degree_bits)} rows x 135 wires, LDE 2^{int(info.degree_bits) + 3}), "
-                                   f"{world} GPU(s), replicas + RCCL gather"
-                                   + (" (p25_gather_proofs: librccl behind the C ABI)" if native else "")
-                                   + ("" if args.dist_backend == "nccl" else " [TEST MODE: all ranks on GPU 0, gloo]"),
-                       "proofs_per_gpu_per_step": B, "proofs_per_step_total": n_step_total,
-                       "all_statuses_ok": ok, "gathered_complete_and_ok": gathered_ok,
-                       "oracle_verifier_accepts": not ver_fail, "oracle_verified_indices": ver_idx,
-                       "circuit_build_s": round(build_s, 2), "head": head, "runtime": p25.runtime_info().as_dict(),
-                       "single_proof_latency_ms": round(tmd["total_ms"], 3),
-                       "phase_ms_single_proof": {k: round(v, 3) for k, v in tmd.items()}},
-            "roofline": {"bound": "valu", "contract_view": "hbm",   # achieved / peak / unit / frac / traffic below: the contract's HBM roof
-                         "view": "achieved / peak / frac are the HBM view the contract prescribes (algorithmic bytes of the dominant "
-                                 "kernel per launch / its launch duration against 8 TB/s); the roof that BINDS is integer-VALU issue: "
-                                 "`valu` below (wave-instructions per second against 1 per SIMD per 4 cycles)",
-                         "kernel": "k_hash_leaves_wide (Poseidon sponge, 2^19 leaves x 135 words)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
-                         "avg_launch_ms": ms_alone, "launches": int(k_launches_alone), "algorithmic_bytes": algo_bytes,
-                         "avg_launch_ms_timed_region": ms_busy, "launches_timed_region": int(k_launches_busy),
-                         # the figure a rocprofv3 --stats AverageNs over the WHOLE run gives: every launch, overlapped or not
-                         "avg_launch_ms_all_launches": ms_all,
-                         "frac_all_launches": (algo_bytes / (ms_all * 1e-3) / 1e9 / HBM_PEAK_GBS) if ms_all > 0 else 0.0,
-                         "note": "integer-VALU bound (17 Poseidon permutations per 1,080-B leaf), not HBM bound. achieved/frac "
-                                 "use avg_launch_ms = the kernel with the GPU to itself (single-proof passes after the timed "
-                                 "region, HIP events on the proving stream; this is what rocprofv3's per-kernel duration "
-                                 "shows for non-overlapped launches).  avg_launch_ms_timed_region is the same bracket with "
-                                 "up to 16 proofs in flight: co-resident kernels time-slice the SIMDs, so it measures "
-                                 "residency, not speed",
-                         "valu": valu, "hbm_phases": hbm_phases, "hbm_overall": hbm_overall},
-        }
-        if per_rank:
-            out["per_rank"] = per_rank
+        out["config"].update({"oracle_verifier_accepts": not ver_fail, "oracle_verified_indices": ver_idx,
+                              "single_proof_latency_ms": round(tmd["total_ms"], 3),
+                              "phase_ms_single_proof": {k: round(v, 3) for k, v in tmd.items()}})
+        out["roofline"] = {"bound": "valu", "contract_view": "hbm",   # achieved / peak / unit / frac / traffic below: the contract's HBM roof
+                           "view": "achieved / peak / frac are the HBM view the contract prescribes (algorithmic bytes of the dominant "
+                                   "kernel per launch / its launch duration against 8 TB/s); the roof that BINDS is integer-VALU issue: "
+                                   "`valu` below (wave-instructions per second against 1 per SIMD per 4 cycles)",
+                           "kernel": "k_hash_leaves_wide (Poseidon sponge, 2^19 leaves x 135 words)",
+                           "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
+                           "avg_launch_ms": ms_alone, "launches": int(k_launches_alone), "algorithmic_bytes": algo_bytes,
+                           "avg_launch_ms_timed_region": ms_busy, "launches_timed_region": int(k_launches_busy),
+                           # the figure a rocprofv3 --stats AverageNs over the WHOLE run gives: every launch, overlapped or not
+                           "avg_launch_ms_all_launches": ms_all,
+                           "frac_all_launches": (algo_bytes / (ms_all * 1e-3) / 1e9 / HBM_PEAK_GBS) if ms_all > 0 else 0.0,
+                           "note": "integer-VALU bound (17 Poseidon permutations per 1,080-B leaf), not HBM bound. achieved/frac "
+                                   "use avg_launch_ms = the kernel with the GPU to itself (single-proof passes after the timed "
+                                   "region, HIP events on the proving stream; this is what rocprofv3's per-kernel duration "
+                                   "shows for non-overlapped launches).  avg_launch_ms_timed_region is the same bracket with "
+                                   "up to 16 proofs in flight: co-resident kernels time-slice the SIMDs, so it measures "
+                                   "residency, not speed",
+                           "valu": valu, "hbm_phases": hbm_phases, "hbm_overall": hbm_overall}
         if ver_fail:
             out["config"]["oracle_verifier_failures"] = [f"{i}: {m}" for i, m in ver_fail]
         def verify_with_oracle(circ, proof, dg=None, cap=None):
@@ -949,16 +991,7 @@ def main():
                                              f"{float(pern.min()):.1f}-{float(pern.max()):.1f} s, all ok: {bool((stn == 0).all())}"}
             ora.set_tuned(False)
             out["cpu_baseline"] = cb
-        # what the other ranks sit out in the final barrier (everything rank 0 did alone since the timed region ended,
-        # the collectives of the aggregation blocks included) against the process group's timeout
-        out["rank0_post_region_s"] = round(time.perf_counter() - t_region_end, 2)
-        out["collective_timeout_s"] = COLLECTIVE_TIMEOUT_S
-        print(json.dumps(out), flush=True)
-    if native:
-        comm.close()
-    if distributed:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
-"""CPU: bench.py fails fast -- one JSON error line, non-zero exit -- when fewer GPUs are visible than --gpus asks for; and
---dump-outputs writes the proofs exactly, within its size budget."""
+"""CPU: bench.py fails fast -- one JSON error line, non-zero exit -- when fewer GPUs are visible than --gpus asks for;
+--dump-outputs writes the proofs exactly, within its size budget; a plain run refuses the options of --full."""
 import importlib.util
 import json
 import os
@@ -59,3 +59,16 @@ def test_bench_steps_must_be_positive():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
                        timeout=300, cwd=ROOT)
     assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_bench_options_of_the_full_run_need_full():
+    """A plain run refuses what only --full uses instead of ignoring it; with --full the same options are taken (the run
+    then stops at the GPU count, before any GPU work)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    for opt in (["--aggregate", "4"], ["--cpu-baseline", "none"], ["--no-cpu-baseline"], ["--extra-configs", "none"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "64"] + opt, capture_output=True,
+                           text=True, timeout=300, cwd=ROOT, env=env)
+        assert r.returncode == 2 and f"{opt[0]} only applies with --full" in r.stderr and not r.stdout.strip(), r.stderr
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "64", "--full"] + opt,
+                           capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+        assert r.returncode == 2 and "64" in json.loads(r.stdout.splitlines()[-1])["error"], (r.stdout, r.stderr)

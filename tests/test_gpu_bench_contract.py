@@ -3,16 +3,57 @@ import json
 import os
 import subprocess
 import sys
+import time
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
+FULL_BLOCKS = ("roofline", "aggregation", "configs", "cpu_baseline")
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full: set up, warm up, time the steps, write --dump-outputs, print the headline line -- none of the blocks
+    --full adds, and at most 30 s of the whole run outside its warm-up and timed steps."""
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "16", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    wall_s = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "recursive proofs/sec (fib-64 p3-in-p2 circuit)" and d["unit"] == "proofs/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "u64 (Goldilocks, p = 2^64 - 2^32 + 1)"
+    assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] - 16 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["config"]["all_statuses_ok"] and "oracle_verifier_accepts" not in d["config"]
+    assert not [k for k in FULL_BLOCKS if k in d]
+    assert np.load(tmp_path / "statuses.npy").tolist() == [0] * 16
+    assert np.load(tmp_path / "proofs.npy").shape[0] == 16
+    assert wall_s - 3 * d["ms_per_step"] * 1e-3 < 30, (wall_s, d["ms_per_step"])
+
+
+def test_bench_plain_run_multi_rank():
+    """The plain run's multi-rank exit (test mode: two ranks on GPU 0, gloo): the gathered step checked, one line, every
+    rank leaves the process group."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "8", "--steps", "1",
+                        "--warmup", "1", "--dist-backend", "gloo"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                       env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["config"]["all_statuses_ok"] and d["config"]["gathered_complete_and_ok"]
+    assert [p["proofs_per_step"] for p in d["per_rank"]] == [8, 8]
+    assert not [k for k in FULL_BLOCKS if k in d]
+
 
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "16", "--steps", "1", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "16", "--steps", "1", "--warmup", "1",
                         "--cpu-cores", "4", "--aggregate", "4", "--aggregate-arity", "2", "--extra-configs", "none"],
                        capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -64,7 +105,7 @@ def test_bench_multi_rank_path_bare_launch():
     or HIP is touched).  Test mode: both ranks share GPU 0 and the collectives run on host copies (gloo) -- the rank
     bookkeeping, barriers, max-over-ranks timing, gather and JSON assembly are the code the 8-GPU run executes."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "8", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--batch", "8", "--steps", "2",
                         "--warmup", "1", "--dist-backend", "gloo", "--aggregate", "4", "--aggregate-arity", "2"],
                        capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -86,7 +127,7 @@ def test_bench_multi_rank_path_bare_launch():
 def test_bench_strong_scaling_mode_two_ranks():
     """--total T (BASELINE config 4 literally: T proofs per step split across the ranks), uneven shards (9 = 5 + 4)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--total", "9", "--steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--total", "9", "--steps", "1",
                         "--warmup", "1", "--dist-backend", "gloo", "--verify", "9"], capture_output=True, text=True,
                        timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -105,7 +146,7 @@ def test_bench_four_ranks_uneven_shards_and_the_four_to_one_cross_rank_aggregate
     against 2) around the same collectives.  Also: what rank 0 does alone after the timed region is reported and far
     below the process group's timeout (the other ranks wait in the final barrier for that long)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--total", "11", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--total", "11", "--steps", "2",
                         "--warmup", "1", "--dist-backend", "gloo", "--verify", "11", "--aggregate", "2",
                         "--aggregate-arity", "2"], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

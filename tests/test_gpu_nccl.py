@@ -29,7 +29,7 @@ def test_rccl_world1_collectives_on_device_tensors():
 def test_bench_force_dist_takes_the_rccl_branch():
     """bench.py --gpus 1 --force-dist: RCCL init with device_id, per-step device-tensor gather on the side streams
     (5 steps: the buffer-reuse wait of step k >= 2 executes), the float64 reductions, the sharded-aggregation collectives."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--batch", "24",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-dist", "--batch", "24",
                         "--steps", "3", "--warmup", "2", "--cpu-baseline", "none", "--extra-configs", "none",
                         "--aggregate", "4", "--aggregate-arity", "2", "--verify", "4"],
                        capture_output=True, text=True, timeout=1500, cwd=ROOT, env=_env())
@@ -51,10 +51,12 @@ def test_bench_dist_native_gathers_through_the_librarys_own_communicator():
     """bench.py --gpus 1 --force-dist --dist-native: the gather of every step through p25_comm_init / p25_gather_proofs
     (librccl called by libp25 on its own side stream, ordered by p25_circuit_mark) instead of torch.distributed; the gathered
     proofs are the ones the oracle's verifier is handed, so a gather that moved nothing fails the run."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--dist-native", "--batch", "24",
+    # the queue count asserted below is bench.py's own request: a count the launching shell exported would stand instead
+    env = {k: v for k, v in _env().items() if k != "GPU_MAX_HW_QUEUES"}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-dist", "--dist-native", "--batch", "24",
                         "--steps", "4", "--warmup", "2", "--cpu-baseline", "none", "--extra-configs", "none",
                         "--aggregate", "0", "--verify", "6"],
-                       capture_output=True, text=True, timeout=1500, cwd=ROOT, env=_env())
+                       capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -35,11 +35,11 @@ for C in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_INSTS_LDS" "FETCH_SIZE" "WRITE
 done
 fi
 if want bench; then
-( time python bench.py ) > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
+( time python bench.py --full ) > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
 # rocprofv3 per-kernel summary of the same command (smaller batch) + the dominant kernel's launches split into
 # "GPU to itself" (bench.py's single-proof passes = roofline.avg_launch_ms) and "in flight"
 rm -rf $OUT/_prof
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/_prof -- python3 bench.py --batch 64 --steps 1 --warmup 1 --no-cpu-baseline --extra-configs none --aggregate 0 > $OUT/${TAG}_bench_b64_rocprof.json 2> $OUT/_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/_prof -- python3 bench.py --full --batch 64 --steps 1 --warmup 1 --no-cpu-baseline --extra-configs none --aggregate 0 > $OUT/${TAG}_bench_b64_rocprof.json 2> $OUT/_prof.err
 find $OUT/_prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_rocprofv3_kernel_stats_bench_b64.csv
 find $OUT/_prof -name "*kernel_trace.csv" | head -1 | xargs -I{} python3 tools/rocprof_kernel_split.py {} > $OUT/${TAG}_rocprof_hash_leaves_split.txt
 rm -rf $OUT/_prof

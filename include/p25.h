@@ -81,27 +81,37 @@ p25_status p25_runtime_info(p25_runtime_info_t* out);
 
 /* ------------------------------------------------------------------------------------------
  * Primitives (host buffers; used by the parity tests).
+ *
+ * Words >= p (non-canonical field elements), per entry point -- never a different canonical-looking answer:
+ *   p25_poseidon_permute    reduced: the result is the result for the words mod p, and canonical
+ *   p25_poseidon2_permute   P25_ERR_INVALID_ARG (the kernel is canonical in, canonical out)
+ *   p25_merkle_commit       P25_ERR_INVALID_ARG (a leaf of at most 4 words is its own digest: its words are tree words)
+ *   p25_lde_commit          P25_ERR_INVALID_ARG (with from_coeffs the input words are coeffs_out)
+ *   p25_transcript          P25_ERR_INVALID_ARG
+ * as p25_quotient, p25_partial_products, p25_eval_polys, p25_fri_prove and p25_prove_batch refuse them.  The *_dev
+ * variants below check nothing (device buffers): their caller keeps the words canonical.
  * ------------------------------------------------------------------------------------------ */
 
-/* In-place Poseidon (v1) permutation of n width-12 states, states[n][12].
+/* In-place Poseidon (v1) permutation of n width-12 states, states[n][12].  Any u64 in (a word >= p stands for its
+ * residue), canonical words out.
  * Replaces upstream PoseidonPermutation::permute (selected by `type C = PoseidonGoldilocksConfig`,
  * src/p3/mod.rs:229); KATs: src/common/poseidon2/poseidon2_goldilocks.rs:190-211. */
 p25_status p25_poseidon_permute(uint64_t* states, size_t n);
 
-/* In-place Poseidon2 permutation, states[n][12].
+/* In-place Poseidon2 permutation, states[n][12]; every word < p (P25_ERR_INVALID_ARG otherwise).
  * Replaces `Poseidon2::poseidon2` (src/common/poseidon2/poseidon2.rs:59-91). */
 p25_status p25_poseidon2_permute(uint64_t* states, size_t n);
 
 /* Merkle commitment of n_leaves leaves of `width` words, given COLUMN-major
  * (leaves_cm[c * n_leaves + l] = word c of leaf l; n_leaves a power of two >= 2^cap_height).
  * cap_out[2^cap_height][4]; tree_out (nullable) receives all levels, leaf digests first
- * (p25_merkle_tree_words words).  Replaces upstream MerkleTree::<F, PoseidonHash>::new(leaves, cap_height). */
+ * (p25_merkle_tree_words words).  Every leaf word < p (P25_ERR_INVALID_ARG otherwise).  Replaces upstream MerkleTree::<F, PoseidonHash>::new(leaves, cap_height). */
 p25_status p25_merkle_commit(const uint64_t* leaves_cm, size_t n_leaves, size_t width,
                              unsigned cap_height, uint64_t* cap_out, uint64_t* tree_out);
 size_t p25_merkle_tree_words(size_t n_leaves, unsigned cap_height);
 
 /* Polynomial-batch commitment.  polys[n_polys][2^log_n] are values on the subgroup in natural order
- * (from_coeffs = 0) or coefficients (from_coeffs = 1).  Outputs (each nullable):
+ * (from_coeffs = 0) or coefficients (from_coeffs = 1), every word < p (P25_ERR_INVALID_ARG otherwise).  Outputs (each nullable):
  *   coeffs_out[n_polys][2^log_n]               coefficients
  *   lde_out[n_polys][2^(log_n+rate_bits)]      LDE on the coset 7*<w>, stored at BIT-REVERSED index
  *                                              (lde_out[p][rev(i)] = f_p(7 w^i)) = Merkle leaf order
@@ -453,7 +463,8 @@ p25_status p25_gather_proofs(p25_comm* comm, p25_circuit* circuit, int32_t mark_
  * ------------------------------------------------------------------------------------------ */
 /* Challenger script (upstream iop/challenger.rs `Challenger<F, PoseidonHash>`: duplex sponge, rate 8, challenges
  * popped from the end of the output buffer): for segment k observe seg_len[k] words of `observe` (consumed in
- * order), then draw n_challenges[k] (<= 64) challenges, appended to challenges_out. */
+ * order), then draw n_challenges[k] (<= 64) challenges, appended to challenges_out.  Every observed word < p
+ * (P25_ERR_INVALID_ARG otherwise). */
 p25_status p25_transcript(const uint64_t* observe, const uint32_t* seg_len, const uint32_t* n_challenges,
                           size_t n_segments, uint64_t* challenges_out);
 /* upstream prover.rs `wires_permutation_partial_products_and_zs`: wires[num_wires][n] (witness values, column

@@ -249,10 +249,15 @@ p25_status with_device(p25_circuit* c, F&& f) { return with_device(c, true, f); 
 
 bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 
-// the host-buffer permutation entry points: states[n][12] in place
-p25_status permute_host(uint64_t* states, size_t n, void (*launch)(u64*, size_t, hipStream_t)) {
+// the host-buffer permutation entry points: states[n][12] in place.  any_u64: the kernel reduces words >= p itself
+// (Poseidon v1's layers are lazy arithmetic: poseidon.h, "any u64 representatives in"); otherwise such a word is refused
+// (Poseidon2 is canonical in, canonical out: its linear layers are gl::add chains, poseidon2.h)
+p25_status permute_host(uint64_t* states, size_t n, void (*launch)(u64*, size_t, hipStream_t), bool any_u64) {
   return guarded([&]() -> p25_status {
     if (!states && n) throw std::invalid_argument("states is null");
+    if (!any_u64)
+      for (size_t i = 0; i < n * 12; i++)
+        if (states[i] >= gl::P) throw std::invalid_argument("non-canonical field element in states");
     DevBuf d(n * 12);
     P25_HIP(hipMemcpy(d.p, states, n * 96, hipMemcpyHostToDevice));
     launch(d.p, n, 0);
@@ -463,8 +468,8 @@ p25_status p25_runtime_info(p25_runtime_info_t* out) {
 }
 
 // ---- primitives -----------------------------------------------------------------------------------------------------
-p25_status p25_poseidon_permute(uint64_t* states, size_t n) { return permute_host(states, n, launch_poseidon_permute); }
-p25_status p25_poseidon2_permute(uint64_t* states, size_t n) { return permute_host(states, n, launch_poseidon2_permute); }
+p25_status p25_poseidon_permute(uint64_t* states, size_t n) { return permute_host(states, n, launch_poseidon_permute, true); }
+p25_status p25_poseidon2_permute(uint64_t* states, size_t n) { return permute_host(states, n, launch_poseidon2_permute, false); }
 
 p25_status p25_merkle_commit(const uint64_t* leaves_cm, size_t n_leaves, size_t width,
                              unsigned cap_height, uint64_t* cap_out, uint64_t* tree_out) {
@@ -472,6 +477,9 @@ p25_status p25_merkle_commit(const uint64_t* leaves_cm, size_t n_leaves, size_t 
     if (!is_pow2(n_leaves) || cap_height > 40 || n_leaves < ((size_t)1 << cap_height) || !width ||
         width > (1u << 20) || !leaves_cm)
       throw std::invalid_argument("p25_merkle_commit: bad shape");
+    // refused, not reduced: a leaf of at most 4 words is its own digest (hash_or_noop), so its words ARE tree words
+    for (size_t i = 0; i < n_leaves * width; i++)
+      if (leaves_cm[i] >= gl::P) throw std::invalid_argument("p25_merkle_commit: non-canonical field element");
     DevBuf d(n_leaves * width);
     size_t tw = merkle_tree_words(n_leaves, cap_height);
     DevBuf t(tw);
@@ -494,8 +502,11 @@ p25_status p25_lde_commit(const uint64_t* polys, unsigned log_n, size_t n_polys,
   return guarded([&]() -> p25_status {
     if (!polys || !n_polys || log_n > 20 || rate_bits > 3 || log_n + rate_bits < cap_height)
       throw std::invalid_argument("p25_lde_commit: bad shape");
-    std::lock_guard<std::mutex> lk(g_primitives_mutex);
     const size_t n = (size_t)1 << log_n, big = n << rate_bits;
+    // refused, not reduced: with from_coeffs the input words ARE coeffs_out, and the commitment is of what was handed in
+    for (size_t i = 0; i < n * n_polys; i++)
+      if (polys[i] >= gl::P) throw std::invalid_argument("p25_lde_commit: non-canonical field element");
+    std::lock_guard<std::mutex> lk(g_primitives_mutex);
     DevBuf in(n * n_polys), co(n * n_polys), tmp(n * n_polys), lde(big * n_polys);
     size_t tw = merkle_tree_words(big, cap_height);
     DevBuf tree(tw);

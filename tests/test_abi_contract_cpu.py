@@ -54,6 +54,10 @@ def fx(p25):
                         trace=trace, proof=proof, n=C.c_size_t(0))
     f.ci = p25.binding.CircuitInfo()
     f.u64 = np.zeros(64, dtype=np.uint64)
+    f.noncanon = np.zeros(8, dtype=np.uint64)          # one word >= p: refused by the host before any launch
+    f.noncanon[5] = P
+    f.noncanon12 = np.zeros(12, dtype=np.uint64)
+    f.noncanon12[11] = P
     return f
 
 
@@ -234,10 +238,18 @@ DEVICE_NULL = {
     "shader_clock_hz": ("hz_out is null", lambda f: f.lib.p25_shader_clock_hz(None)),
     "poseidon_permute": ("states is null", lambda f: f.lib.p25_poseidon_permute(None, 1)),
     "poseidon2_permute": ("states is null", lambda f: f.lib.p25_poseidon2_permute(None, 1)),
+    "poseidon2_permute/canonical": ("non-canonical field element",
+                                    lambda f: f.lib.p25_poseidon2_permute(_p(f.noncanon12), 1)),
     "poseidon_permute_dev": (None, lambda f: f.lib.p25_poseidon_permute_dev(None, 0, None)),
     "merkle_commit": ("bad shape", lambda f: f.lib.p25_merkle_commit(None, 8, 1, 0, None, None)),
+    "merkle_commit/canonical": ("non-canonical field element",
+                                lambda f: f.lib.p25_merkle_commit(_p(f.noncanon), 8, 1, 0, _p(f.u64), None)),
     "merkle_commit_dev": ("bad shape", lambda f: f.lib.p25_merkle_commit_dev(None, 8, 8, 1, 0, None, None)),
     "lde_commit": ("bad shape", lambda f: f.lib.p25_lde_commit(None, 3, 1, 0, 1, 0, None, None, None)),
+    "lde_commit/canonical": ("non-canonical field element",
+                             lambda f: f.lib.p25_lde_commit(_p(f.noncanon), 3, 1, 0, 1, 0, None, None, _p(f.u64))),
+    "lde_commit/canonical_coeffs": ("non-canonical field element",
+                                    lambda f: f.lib.p25_lde_commit(_p(f.noncanon), 3, 1, 1, 1, 0, None, None, _p(f.u64))),
     "lde_commit_dev": ("bad shape", lambda f: f.lib.p25_lde_commit_dev(None, 3, 1, 0, 1, 0, None, None, None, None, None)),
     "circuit_to_bytes": ("null argument", lambda f: f.lib.p25_circuit_to_bytes(f.h, None, None)),
     "circuit_digest/c": ("null argument", lambda f: f.lib.p25_circuit_digest(None, _p(f.u64), None)),
@@ -260,6 +272,9 @@ DEVICE_NULL = {
     "circuit_kernel_stats": ("null argument", lambda f: f.lib.p25_circuit_kernel_stats(None, 1, 0, None, None)),
     "witness": ("null argument", lambda f: f.lib.p25_witness(f.h, None, 0, None, None)),
     "transcript": ("null argument", lambda f: f.lib.p25_transcript(None, None, None, 1, None)),
+    "transcript/canonical": ("non-canonical field element",
+                             lambda f: f.lib.p25_transcript(_p(f.noncanon), _p(np.array([8], dtype=np.uint32)),
+                                                            _p(np.array([1], dtype=np.uint32)), 1, _p(f.u64))),
     "partial_products": ("null argument", lambda f: f.lib.p25_partial_products(f.h, None, None, None, None)),
     "quotient": ("null argument", lambda f: f.lib.p25_quotient(f.h, None, None, None, None, None, None)),
     "eval_polys": ("null argument", lambda f: f.lib.p25_eval_polys(None, 1, 3, None, 1, None)),

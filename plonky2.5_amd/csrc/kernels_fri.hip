@@ -15,37 +15,68 @@
 
 namespace p25 {
 
-// out[t] = (scale * point)^t for t <= count (count+1 entries), as (a, b) pairs
-__global__ void k_ext_pows(const u64* __restrict__ point, u64 scale, uint32_t count, int invert,
-                           u64* __restrict__ out) {
+// Power tables, one per grid row: job.out[t] = (scale * point)^t (or its inverse's powers) for t <= count (count + 1
+// entries), as (a, b) pairs
+constexpr uint32_t EXT_POW_MAX_JOBS = 5;
+struct ExtPowJob {
+  const u64* point;
+  u64 scale;
+  u64* out;
+  uint32_t count, invert;
+};
+struct ExtPowJobs {
+  ExtPowJob job[EXT_POW_MAX_JOBS];
+};
+__global__ void k_ext_pows(ExtPowJobs a) {
   P25_WAVE_PRIO(P25_PRIO_CHAIN);
+  const ExtPowJob jb = a.job[blockIdx.y];
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t > count) return;
-  gl::E2 z = gl::mul(gl::E2{point[0], point[1]}, scale);
-  if (invert) z = gl::inv(z);
+  if (t > jb.count) return;
+  gl::E2 z = gl::mul(gl::E2{jb.point[0], jb.point[1]}, jb.scale);
+  if (jb.invert) z = gl::inv(z);
   gl::E2 r = gl::e2(1);   // square-and-multiply in lazy arithmetic (gl_lazy.h), canonical at the store
   for (uint32_t e = t; e; e >>= 1) {
     if (e & 1) r = gl::e2_mul_nc(r, z);
     z = gl::e2_mul_nc(z, z);
   }
-  out[2 * t] = gl::canon(r.a);
-  out[2 * t + 1] = gl::canon(r.b);
+  jb.out[2 * t] = gl::canon(r.a);
+  jb.out[2 * t + 1] = gl::canon(r.b);
+}
+static void launch_ext_pows(const ExtPowJobs& jobs, uint32_t n_jobs, hipStream_t st) {
+  uint32_t most = 0;
+  for (uint32_t j = 0; j < n_jobs; j++) most = jobs.job[j].count > most ? jobs.job[j].count : most;
+  hipLaunchKernelGGL(k_ext_pows, dim3((most + 1 + 255) / 256, n_jobs), dim3(256), 0, st, jobs);
 }
 
 // one block per polynomial: sum_k c_k z^k with lane t taking the coefficients k = t (mod S).  S = 1024
 // lanes: the per-lane Horner chain (n / S dependent extension multiplies) is what a lone proof waits for.
 constexpr uint32_t EVAL_LANES = 1024;
 constexpr uint32_t EVAL_CHUNK_LOG = 16;  // polynomials longer than 2^16 are split into chunks, one block each
+constexpr uint32_t EVAL_POW_WORDS = 2 * (EVAL_LANES + 2);  // one power table in the scratch
+// The job table of one launch: blocks [block_end[j - 1], block_end[j]) belong to job j, `chunks` blocks per polynomial.
+struct EvalJobs {
+  EvalJob job[EVAL_MAX_JOBS];
+  uint32_t block_end[EVAL_MAX_JOBS];
+  uint32_t n_jobs, log_n, log_chunk;
+  const u64* pows;   // [points][EVAL_POW_WORDS]: (scale[p] * point)^t, t <= S
+  u64* part;         // chunks > 1: partial sums [polynomial over all jobs][chunks]
+  const u64* point;
+  u64 scale[2];
+};
 // out[(poly, chunk)] = sum_{k in chunk} c_k z^(k - chunk_start): lane t takes k = t (mod S) within the chunk
-__global__ __launch_bounds__(1024) void k_eval_polys(const u64* __restrict__ coeffs, uint32_t log_n, uint32_t log_chunk,
-                                                     const u64* __restrict__ pows /*[S+1] ext*/,
-                                                     u64* __restrict__ out) {
+__global__ __launch_bounds__(1024) void k_eval_polys(EvalJobs a) {
   P25_WAVE_PRIO(P25_PRIO_BULK);
   __shared__ u64 sa[EVAL_LANES], sb[EVAL_LANES];
+  uint32_t j = 0;
+  while (j + 1 < a.n_jobs && blockIdx.x >= a.block_end[j]) j++;
+  const EvalJob jb = a.job[j];
+  const uint32_t local = blockIdx.x - (j ? a.block_end[j - 1] : 0);
+  const uint32_t log_n = a.log_n, log_chunk = a.log_chunk;
+  const u64* __restrict__ pows = a.pows + (size_t)jb.point * EVAL_POW_WORDS;
   const uint32_t n = 1u << log_chunk;
   const uint32_t S = n < EVAL_LANES ? n : EVAL_LANES;
   const uint32_t chunks = 1u << (log_n - log_chunk);
-  const u64* c = coeffs + ((size_t)(blockIdx.x / chunks) << log_n) + ((size_t)(blockIdx.x % chunks) << log_chunk);
+  const u64* __restrict__ c = jb.coeffs + ((size_t)(local / chunks) << log_n) + ((size_t)(local % chunks) << log_chunk);
   const uint32_t t = threadIdx.x;
   gl::E2 acc = gl::e2(0);
   if (t < S) {
@@ -67,40 +98,66 @@ __global__ __launch_bounds__(1024) void k_eval_polys(const u64* __restrict__ coe
     __syncthreads();
   }
   if (t == 0) {
-    out[2 * blockIdx.x] = sa[0];
-    out[2 * blockIdx.x + 1] = sb[0];
+    u64* out = chunks == 1 ? jb.out + 2 * local : a.part + 2 * (size_t)blockIdx.x;
+    out[0] = sa[0];
+    out[1] = sb[0];
   }
 }
-// out[p] = sum_b part[p][b] (z^chunk)^b  (Horner over the chunks of polynomial p)
-__global__ void k_eval_combine(const u64* __restrict__ part, uint32_t n_polys, uint32_t chunks, uint32_t log_chunk,
-                               const u64* __restrict__ point, u64 scale, u64* __restrict__ out) {
+// out[p] = sum_b part[p][b] (z^chunk)^b  (Horner over the chunks of polynomial p), over the polynomials of all jobs
+__global__ void k_eval_combine(EvalJobs a) {
   P25_WAVE_PRIO(P25_PRIO_CHAIN);
+  const uint32_t chunks = 1u << (a.log_n - a.log_chunk);
   uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n_polys) return;
-  gl::E2 y = gl::exp_pow2(gl::mul(gl::E2{point[0], point[1]}, scale), log_chunk);
+  if (p >= a.block_end[a.n_jobs - 1] / chunks) return;
+  uint32_t j = 0;
+  while (j + 1 < a.n_jobs && p >= a.block_end[j] / chunks) j++;
+  const EvalJob jb = a.job[j];
+  const uint32_t local = p - (j ? a.block_end[j - 1] / chunks : 0);
+  gl::E2 y = gl::exp_pow2(gl::mul(gl::E2{a.point[0], a.point[1]}, a.scale[jb.point]), a.log_chunk);
   gl::E2 acc = gl::e2(0);
   for (int b = (int)chunks - 1; b >= 0; b--) {
     acc = gl::mul(acc, y);
-    acc = gl::add(acc, gl::E2{part[2 * ((size_t)p * chunks + b)], part[2 * ((size_t)p * chunks + b) + 1]});
+    acc = gl::add(acc, gl::E2{a.part[2 * ((size_t)p * chunks + b)], a.part[2 * ((size_t)p * chunks + b) + 1]});
   }
-  out[2 * p] = acc.a;
-  out[2 * p + 1] = acc.b;
+  jb.out[2 * local] = acc.a;
+  jb.out[2 * local + 1] = acc.b;
 }
 
-void launch_eval_polys(const u64* d_coeffs, uint32_t n_polys, uint32_t log_n, const u64* d_point, u64 scale,
-                       u64* d_scratch_pows, u64* d_out, hipStream_t st, bool reuse_pows) {
+size_t eval_scratch_words(uint32_t n_points, size_t total_polys, uint32_t log_n) {
+  const size_t chunks = log_n > EVAL_CHUNK_LOG ? (size_t)1 << (log_n - EVAL_CHUNK_LOG) : 1;
+  return (size_t)n_points * EVAL_POW_WORDS + 2 * total_polys * chunks;
+}
+void launch_eval_jobs(const EvalJob* jobs, uint32_t n_jobs, uint32_t log_n, const u64* d_point, const u64* scale,
+                      uint32_t n_points, u64* d_scratch, hipStream_t st) {
+  if (!n_jobs || n_jobs > EVAL_MAX_JOBS || !n_points || n_points > 2) throw std::invalid_argument("launch_eval_jobs: bad job table");
   const uint32_t log_chunk = log_n < EVAL_CHUNK_LOG ? log_n : EVAL_CHUNK_LOG;
   const uint32_t n = 1u << log_chunk, S = n < EVAL_LANES ? n : EVAL_LANES, chunks = 1u << (log_n - log_chunk);
-  if (!reuse_pows)  // (scale * point)^t, t <= S; successive calls at the same point share the table
-    hipLaunchKernelGGL(k_ext_pows, dim3((S + 1 + 255) / 256), dim3(256), 0, st, d_point, scale, S, 0, d_scratch_pows);
-  if (chunks == 1) {
-    hipLaunchKernelGGL(k_eval_polys, dim3(n_polys), dim3(EVAL_LANES), 0, st, d_coeffs, log_n, log_chunk, d_scratch_pows, d_out);
-    return;
+  // the power tables (scale[p] * point)^t, t <= S, one grid row per point
+  ExtPowJobs pj{};
+  for (uint32_t p = 0; p < n_points; p++) pj.job[p] = ExtPowJob{d_point, scale[p], d_scratch + (size_t)p * EVAL_POW_WORDS, S, 0};
+  launch_ext_pows(pj, n_points, st);
+  EvalJobs ej{};
+  uint32_t blocks = 0;
+  for (uint32_t j = 0; j < n_jobs; j++) {
+    if (jobs[j].point >= n_points) throw std::invalid_argument("launch_eval_jobs: bad point index");
+    ej.job[j] = jobs[j];
+    blocks += jobs[j].n_polys * chunks;
+    ej.block_end[j] = blocks;
   }
-  // partial sums behind the power table: [n_polys][chunks] extension values
-  u64* part = d_scratch_pows + 2 * (EVAL_LANES + 2);
-  hipLaunchKernelGGL(k_eval_polys, dim3(n_polys * chunks), dim3(EVAL_LANES), 0, st, d_coeffs, log_n, log_chunk, d_scratch_pows, part);
-  hipLaunchKernelGGL(k_eval_combine, dim3((n_polys + 63) / 64), dim3(64), 0, st, part, n_polys, chunks, log_chunk, d_point, scale, d_out);
+  ej.n_jobs = n_jobs;
+  ej.log_n = log_n;
+  ej.log_chunk = log_chunk;
+  ej.pows = d_scratch;
+  ej.part = d_scratch + (size_t)n_points * EVAL_POW_WORDS;  // partial sums behind the power tables
+  ej.point = d_point;
+  for (uint32_t p = 0; p < n_points; p++) ej.scale[p] = scale[p];
+  hipLaunchKernelGGL(k_eval_polys, dim3(blocks), dim3(EVAL_LANES), 0, st, ej);
+  if (chunks > 1) hipLaunchKernelGGL(k_eval_combine, dim3((blocks / chunks + 63) / 64), dim3(64), 0, st, ej);
+}
+void launch_eval_polys(const u64* d_coeffs, uint32_t n_polys, uint32_t log_n, const u64* d_point, u64 scale,
+                       u64* d_scratch_pows, u64* d_out, hipStream_t st) {
+  const EvalJob job{d_coeffs, d_out, n_polys, 0};
+  launch_eval_jobs(&job, 1, log_n, d_point, &scale, 1, d_scratch_pows, st);
 }
 
 // ---------------------------------------------------------------- FRI batching
@@ -232,11 +289,13 @@ void launch_fri_combine(const FriCombineArgs& a, hipStream_t st) {
   u64* zinv1 = zinv0 + 2 * (size_t)(n + 1);
   u64* block_tot = zinv1 + 2 * (size_t)(n + 1);
   const unsigned nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_ext_pows, dim3((total + 1 + 255) / 256), dim3(256), 0, st, a.chal + CH_FRI_ALPHA, (u64)1, total, 0, alpha_pows);
-  hipLaunchKernelGGL(k_ext_pows, dim3((n + 1 + 255) / 256), dim3(256), 0, st, a.chal + CH_ZETA, (u64)1, n, 0, zpow0);
-  hipLaunchKernelGGL(k_ext_pows, dim3((n + 1 + 255) / 256), dim3(256), 0, st, a.chal + CH_ZETA, a.g, n, 0, zpow1);
-  hipLaunchKernelGGL(k_ext_pows, dim3((n + 1 + 255) / 256), dim3(256), 0, st, a.chal + CH_ZETA, (u64)1, n, 1, zinv0);
-  hipLaunchKernelGGL(k_ext_pows, dim3((n + 1 + 255) / 256), dim3(256), 0, st, a.chal + CH_ZETA, a.g, n, 1, zinv1);
+  ExtPowJobs pj{};  // the five tables in one grid
+  pj.job[0] = ExtPowJob{a.chal + CH_FRI_ALPHA, (u64)1, alpha_pows, total, 0};
+  pj.job[1] = ExtPowJob{a.chal + CH_ZETA, (u64)1, zpow0, n, 0};
+  pj.job[2] = ExtPowJob{a.chal + CH_ZETA, a.g, zpow1, n, 0};
+  pj.job[3] = ExtPowJob{a.chal + CH_ZETA, (u64)1, zinv0, n, 1};
+  pj.job[4] = ExtPowJob{a.chal + CH_ZETA, a.g, zinv1, n, 1};
+  launch_ext_pows(pj, 5, st);
   CombineK ck;
   for (int o = 0; o < 4; o++) {
     ck.coeffs[o] = a.coeffs[o];

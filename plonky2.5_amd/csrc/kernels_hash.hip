@@ -145,11 +145,14 @@ __global__ __launch_bounds__(256) void k_tree_top_coop(u64* __restrict__ nodes, 
   }
 }
 
-// Levels with at most this many parents use the cooperative per-level kernel (above the fused top).  512 when many
-// proofs are in flight (the per-lane form costs several times fewer instructions and other streams hide its latency;
-// measured 4096 / 512 / 0: 122.3 / 123.0 / 122.8 proofs/s); a lone proof prefers 32768: at that size the per-lane
-// form leaves most SIMDs with one wave or none, and the level takes a full permutation latency.
-constexpr size_t COOP_PARENTS_BATCH = 512, COOP_PARENTS_SINGLE = 32768;
+// Levels with at most this many parents use the cooperative per-level kernel (above the fused top).  2048 when many
+// proofs are in flight: the per-lane form costs several times fewer instructions, but a launch of a few dozen waves
+// holds its hardware queue for a whole per-lane permutation (58 us at best), and with sixteen proving streams on four
+// in-order queues three other proofs wait behind it (512 / 2048 / 8192 at four queues: 119.9 / 123.6 / 123.3 proofs/s,
+// profiles/r07_fused_chain.txt; at 24 queues, where the slots were free, 4096 / 512 / 0 measured 122.3 / 123.0 / 122.8).
+// A lone proof prefers 32768: at that size the per-lane form leaves most SIMDs with one wave or none, and the level
+// takes a full permutation latency.
+constexpr size_t COOP_PARENTS_BATCH = 2048, COOP_PARENTS_SINGLE = 32768;
 
 static void launch_level(const u64* cur, u64* nxt, size_t m, hipStream_t st, bool single_proof) {
   if (m <= (single_proof ? COOP_PARENTS_SINGLE : COOP_PARENTS_BATCH)) {

@@ -46,8 +46,11 @@ struct Sponge {
   }
 };
 
-__global__ __launch_bounds__(64) void k_transcript(Transcript* tr, int init, const u64* __restrict__ obs,
-                                                   uint32_t n_obs, u64* __restrict__ chal_out, uint32_t n_chal) {
+// One launch = one stretch of the challenger's script: reset (optional), observe up to TR_MAX_SEGMENTS segments in
+// order, draw n_chal challenges, then one closing action (TranscriptArgs, prover_kernels.h).  A segment is loaded 64
+// words at a time, one word per lane (which also stores it to copy_dst: how a Merkle cap, the final polynomial and the
+// PoW witness reach the proof), and fed to the sponge from the lanes' registers; only the observe order is sequential.
+__global__ __launch_bounds__(64) void k_transcript(Transcript* tr, TranscriptArgs a) {
   P25_WAVE_PRIO(P25_PRIO_CHAIN);
   __shared__ u64 rc_lds[360];
   coop::stage_poseidon_rc(rc_lds);
@@ -55,7 +58,7 @@ __global__ __launch_bounds__(64) void k_transcript(Transcript* tr, int init, con
   Sponge sp;
   sp.lane = lane;
   sp.rc = rc_lds;
-  if (init) {
+  if (a.init) {
     sp.state = 0;
     sp.inb = 0;
     sp.outb = 0;
@@ -68,10 +71,27 @@ __global__ __launch_bounds__(64) void k_transcript(Transcript* tr, int init, con
     sp.n_in = tr->n_in;
     sp.n_out = tr->n_out;
   }
-  for (uint32_t i = 0; i < n_obs; i++) sp.observe(obs[i]);
-  for (uint32_t i = 0; i < n_chal; i++) {
+  u64 w0 = 0;  // the first observed word (TR_CLOSE_FINISH: the PoW witness)
+  for (uint32_t s = 0; s < a.n_seg; s++) {
+    const TrSegment sg = a.seg[s];
+    for (uint32_t base = 0; base < sg.n_words; base += 64) {
+      const uint32_t cnt = sg.n_words - base < 64 ? sg.n_words - base : 64;
+      u64 v = 0;
+      if ((uint32_t)lane < cnt) {
+        const uint32_t i = base + (uint32_t)lane;
+        v = sg.src_b ? ((i & 1) ? sg.src_b : sg.src)[i >> 1] : sg.src[i];
+        if (sg.copy_dst) sg.copy_dst[i] = v;
+      }
+      if (s == 0 && base == 0) w0 = shfl64(v, 0);
+      for (uint32_t j = 0; j < cnt; j++) sp.observe(shfl64(v, (int)j));
+    }
+  }
+  u64 c0 = 0, c1 = 0;  // the first two challenges, for the closing action
+  for (uint32_t i = 0; i < a.n_chal; i++) {
     u64 c = sp.challenge();
-    if (lane == 0) chal_out[i] = c;
+    if (i == 0) c0 = c;
+    if (i == 1) c1 = c;
+    if (lane == 0) a.chal_out[i] = c;
   }
   if (lane < 12) tr->state[lane] = sp.state;
   if (lane < 8) {
@@ -82,33 +102,73 @@ __global__ __launch_bounds__(64) void k_transcript(Transcript* tr, int init, con
     tr->n_in = sp.n_in;
     tr->n_out = sp.n_out;
   }
+  switch (a.close) {
+    case TR_CLOSE_ALPHA_POWS: {  // (c0, c1) = alphas: out[c][j] = alpha_c^j, j < ALPHA_POWS; lane l takes j = l (mod 64)
+      for (int c = 0; c < 2; c++) {
+        const u64 al = c ? c1 : c0, al64 = gl::pow(al, 64);
+        u64 p = gl::pow(al, (u64)lane);
+        for (int j = lane; j < ALPHA_POWS; j += 64) {
+          a.close_out[c * ALPHA_POWS + j] = p;
+          p = gl::mul(p, al64);
+        }
+      }
+      break;
+    }
+    case TR_CLOSE_CHECK_ZETA: {  // (c0, c1) = zeta
+      gl::E2 zn = gl::exp_pow2(gl::E2{c0, c1}, a.close_arg);
+      if (lane == 0 && zn.a == 1 && zn.b == 0) set_status(a.status, 6);  // "Opening point is in the subgroup."
+      break;
+    }
+    case TR_CLOSE_POW_INIT:
+      if (lane == 0) *a.close_out = ~0ull;
+      break;
+    case TR_CLOSE_FINISH:  // w0 = the witness just observed (none found: ~0), c0 = the PoW response
+      if (lane == 0 && (w0 == ~0ull || (uint32_t)__clzll((long long)c0) < a.close_arg)) set_status(a.status, 7);
+      break;
+    default:
+      break;
+  }
 }
 
+void launch_transcript(Transcript* d_tr, const TranscriptArgs& a, hipStream_t st) {
+  if (a.n_seg > TR_MAX_SEGMENTS) throw std::invalid_argument("too many transcript segments in one launch");
+  hipLaunchKernelGGL(k_transcript, dim3(1), dim3(64), 0, st, d_tr, a);
+}
 void launch_transcript(Transcript* d_tr, int init, const u64* d_obs, uint32_t n_obs, u64* d_chal_out,
                        uint32_t n_chal, hipStream_t st) {
-  hipLaunchKernelGGL(k_transcript, dim3(1), dim3(64), 0, st, d_tr, init, d_obs, n_obs, d_chal_out, n_chal);
+  TranscriptArgs a{};
+  a.seg[0] = TrSegment{d_obs, nullptr, nullptr, n_obs};
+  a.n_seg = 1;
+  a.init = (uint32_t)init;
+  a.chal_out = d_chal_out;
+  a.n_chal = n_chal;
+  launch_transcript(d_tr, a, st);
 }
 
-// One candidate per lane: result = min over candidates in [base, base + count) that satisfy the PoW
-// (UINT64_MAX if none).  Skips the whole range if a smaller witness was already found.
-__global__ __launch_bounds__(256) void k_pow_search(const Transcript* __restrict__ tr, int pow_bits, u64 base,
-                                                    u64* __restrict__ result) {
-  if (*result < base) return;
-  u64 cand = base + (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  u64 s[12];
+// The PoW search in one launch: lane t tries the candidates t, t + G, t + 2G, ... (G = the grid's lane count) in
+// increasing order and leaves as soon as a witness below its next candidate is known.  A lane only ever skips
+// candidates above a witness already found, so *result ends as the smallest witness among the first `total` candidates
+// (~0, as the launch before left it, if there is none).  No lane waits for another.
+__global__ __launch_bounds__(256) void k_pow_search(const Transcript* __restrict__ tr, uint32_t pow_bits, u64 total,
+                                                    u64* result) {
+  const u64 G = (u64)gridDim.x * blockDim.x;
+  for (u64 cand = (u64)blockIdx.x * blockDim.x + threadIdx.x; cand < total; cand += G) {
+    if (__hip_atomic_load(result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < cand) return;
+    u64 s[12];
 #pragma unroll
-  for (int i = 0; i < 12; i++) s[i] = tr->state[i];
-  const uint32_t pos = tr->n_in;
-  for (uint32_t i = 0; i < pos; i++) s[i] = tr->in[i];
-  // witness goes to sponge position `pos` (an invariant of the challenger: pos < 8)
+    for (int i = 0; i < 12; i++) s[i] = tr->state[i];
+    const uint32_t pos = tr->n_in;
+    for (uint32_t i = 0; i < pos; i++) s[i] = tr->in[i];
+    // witness goes to sponge position `pos` (an invariant of the challenger: pos < 8)
 #pragma unroll
-  for (int i = 0; i < 8; i++)
-    if ((uint32_t)i == pos) s[i] = cand;
-  poseidon::permute(s);
-  if (__clzll((long long)s[7]) >= pow_bits) atomicMin((unsigned long long*)result, (unsigned long long)cand);
+    for (int i = 0; i < 8; i++)
+      if ((uint32_t)i == pos) s[i] = cand;
+    poseidon::permute(s);
+    // No `return` after the atomicMin: the compiler would sink the atomic below the loop, where a wave only arrives once
+    // ALL its lanes have left, i.e. after the other lanes have run out of candidates.  The finder leaves at its next check.
+    if ((uint32_t)__clzll((long long)s[7]) >= pow_bits) atomicMin((unsigned long long*)result, (unsigned long long)cand);
+  }
 }
-__global__ void k_pow_init(u64* result) {
-  P25_WAVE_PRIO(P25_PRIO_CHAIN); *result = ~0ull; }
 
 // hash_no_pad of a proof's public inputs (overwrite-mode sponge, rate 8; hash/hashing.rs `hash_n_to_m_no_pad`): state
 // word r in lane r, one cooperative permutation per chunk of 8.
@@ -135,18 +195,14 @@ void launch_public_inputs(const u64* d_vals, size_t B, uint32_t p, const uint32_
 }
 
 void launch_pow_search(const Transcript* d_tr, int pow_bits, u64* d_result, hipStream_t st) {
-  hipLaunchKernelGGL(k_pow_init, dim3(1), dim3(1), 0, st, d_result);
-  // Expected number of candidates is 2^pow_bits; a window is skipped once a smaller witness is known.
-  // Windows grow geometrically -- 1, 1, 2, 4, ... x 2^pow_bits candidates, 2^(pow_bits+6) in total -- so
-  // the expected work is ~1.7 x 2^pow_bits permutations (a flat 2^(pow_bits+2) window costs 4 x) and all
-  // windows fail with probability e^-64 (reported as P25_ERR_INTERNAL by k_finish).
+  // *d_result = ~0 comes from the transcript launch that observed the final polynomial (TR_CLOSE_POW_INIT).
+  // Expected number of candidates is 2^pow_bits.  The grid is 2^16 lanes (2^12 for pow_bits <= 12), so the expected
+  // work is ~1.6 x 2^pow_bits permutations; the search gives up after 2^(pow_bits + 6) candidates, which happens with
+  // probability e^-64 (reported as P25_ERR_INTERNAL by the transcript launch that observes the witness).
   const int wb = pow_bits < 12 ? 12 : pow_bits;
-  u64 base = 0;
-  for (int w = 0; w < 7; w++) {
-    const u64 window = (u64)1 << (w == 0 ? wb : wb + w - 1);
-    hipLaunchKernelGGL(k_pow_search, dim3((unsigned)(window / 256)), dim3(256), 0, st, d_tr, pow_bits, base, d_result);
-    base += window;
-  }
+  const int gb = wb < 16 ? wb : 16;
+  hipLaunchKernelGGL(k_pow_search, dim3(1u << (gb - 8)), dim3(256), 0, st, d_tr, (uint32_t)pow_bits, (u64)1 << (wb + 6),
+                     d_result);
 }
 
 }  // namespace p25

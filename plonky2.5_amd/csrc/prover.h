@@ -132,7 +132,8 @@ class DeviceCircuit {
   struct Ctx;  // per-proof working set
   void prove_one(Ctx& cx, int buf, size_t B, uint32_t p, u64* d_proof, uint32_t* d_status, PhaseTimes* t);
   void enqueue_partial_products(Ctx& cx, hipStream_t st);
-  void enqueue_quotient(Ctx& cx, hipStream_t st);
+  // alpha_table: launch the alpha-power table kernel first (prove_one gets the table from its transcript launch)
+  void enqueue_quotient(Ctx& cx, hipStream_t st, bool alpha_table = true);
   void set_challenges(Ctx& cx, const u64* betas, const u64* gammas, const u64* alphas);
   size_t ctx_bytes() const;
   void ensure_ctx(size_t count);

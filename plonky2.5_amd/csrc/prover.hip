@@ -148,28 +148,6 @@ ProofLayout make_proof_layout(const Circuit& c) {
   return L;
 }
 
-// ---------------------------------------------------------------- small glue kernels
-__global__ void k_check_zeta(const u64* chal, uint32_t degree_bits, uint32_t* status) {
-  P25_WAVE_PRIO(P25_PRIO_CHAIN);
-  gl::E2 z{chal[CH_ZETA], chal[CH_ZETA + 1]};
-  gl::E2 zn = gl::exp_pow2(z, degree_bits);
-  if (zn.a == 1 && zn.b == 0) set_status(status, 6);  // "Opening point is in the subgroup."
-}
-__global__ void k_interleave(const u64* a, const u64* b, uint32_t m, u64* out) {
-  P25_WAVE_PRIO(P25_PRIO_CHAIN);
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < m) {
-    out[2 * i] = a[i];
-    out[2 * i + 1] = b[i];
-  }
-}
-__global__ void k_finish(const u64* chal, int pow_bits, u64* proof_pow, uint32_t* status) {
-  P25_WAVE_PRIO(P25_PRIO_CHAIN);
-  u64 w = chal[CH_POW_WITNESS];
-  *proof_pow = w;
-  if (w == ~0ull || __clzll((long long)chal[CH_POW_RESPONSE]) < pow_bits) set_status(status, 7);
-}
-
 // ---------------------------------------------------------------- FRI (upstream fri/prover.rs `fri_proof`)
 void FriWork::alloc(int log_n, int rate_bits, unsigned cap_height, const std::vector<int>& arity_bits) {
   size_t m = (size_t)1 << log_n;
@@ -193,9 +171,6 @@ void FriWork::alloc(int log_n, int rate_bits, unsigned cap_height, const std::ve
 void fri_commit_pow_query(NttTables& tables, FriWork& w, const FriShape& sh, Transcript* tr, u64* chal, QueryArgs qy,
                           u64* d_proof, const FriOffsets& fo, uint32_t* d_status, hipStream_t st, bool single_proof) {
   const size_t capw = (size_t)4 << sh.cap_height;
-  auto d2d = [&](u64* dst, const u64* src, size_t words) {
-    P25_HIP(hipMemcpyAsync(dst, src, words * 8, hipMemcpyDeviceToDevice, st));
-  };
   size_t m = (size_t)1 << sh.log_n;
   int log_m = sh.log_n;
   u64 shift = gl::GENERATOR;
@@ -210,8 +185,14 @@ void fri_commit_pow_query(NttTables& tables, FriWork& w, const FriShape& sh, Tra
     launch_tree_from_digests(w.tree[l].p, n_leaves, sh.cap_height, st, single_proof);
     const size_t ltw = merkle_tree_words(n_leaves, sh.cap_height);
     const u64* cap = w.tree[l].p + ltw - capw;
-    d2d(d_proof + fo.caps + l * capw, cap, capw);
-    launch_transcript(tr, 0, cap, (uint32_t)capw, chal + CH_FRI_BETAS + 2 * l, 2, st);
+    {  // observe the cap (and store it to the proof), draw beta
+      TranscriptArgs ta{};
+      ta.seg[0] = TrSegment{cap, nullptr, d_proof + fo.caps + l * capw, (uint32_t)capw};
+      ta.n_seg = 1;
+      ta.chal_out = chal + CH_FRI_BETAS + 2 * l;
+      ta.n_chal = 2;
+      launch_transcript(tr, ta, st);
+    }
     launch_fri_fold(w.coeffs[l].p, w.coeffs[l].p + m, (uint32_t)(m >> ab), ab, chal + CH_FRI_BETAS + 2 * l,
                     w.coeffs[l + 1].p, w.coeffs[l + 1].p + (m >> ab), st);
     qy.arity_bits[l] = ab;
@@ -222,15 +203,30 @@ void fri_commit_pow_query(NttTables& tables, FriWork& w, const FriShape& sh, Tra
     m >>= ab;
     log_m -= ab;
   }
-  // final polynomial (the coefficients that survive truncation by the rate)
-  hipLaunchKernelGGL(k_interleave, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.coeffs[nl].p,
-                     w.coeffs[nl].p + m, (uint32_t)m, d_proof + fo.final_poly);
-  launch_transcript(tr, 0, d_proof + fo.final_poly, (uint32_t)(2 * m), chal, 0, st);
+  // final polynomial (the coefficients that survive truncation by the rate): observed from its component arrays and
+  // stored interleaved to the proof by the same wave, which also resets the PoW result
+  {
+    TranscriptArgs ta{};
+    ta.seg[0] = TrSegment{w.coeffs[nl].p, w.coeffs[nl].p + m, d_proof + fo.final_poly, (uint32_t)(2 * m)};
+    ta.n_seg = 1;
+    ta.close = TR_CLOSE_POW_INIT;
+    ta.close_out = chal + CH_POW_WITNESS;
+    launch_transcript(tr, ta, st);
+  }
   qy.n_layers = (uint32_t)nl;
   // "find proof-of-work witness"
   launch_pow_search(tr, sh.pow_bits, chal + CH_POW_WITNESS, st);
-  launch_transcript(tr, 0, chal + CH_POW_WITNESS, 1, chal + CH_POW_RESPONSE, 1 + sh.num_queries, st);
-  hipLaunchKernelGGL(k_finish, dim3(1), dim3(1), 0, st, chal, sh.pow_bits, d_proof + fo.pow_witness, d_status);
+  {  // observe the witness (and store it to the proof), draw the PoW response and the query indices, check the response
+    TranscriptArgs ta{};
+    ta.seg[0] = TrSegment{chal + CH_POW_WITNESS, nullptr, d_proof + fo.pow_witness, 1};
+    ta.n_seg = 1;
+    ta.chal_out = chal + CH_POW_RESPONSE;
+    ta.n_chal = 1 + (uint32_t)sh.num_queries;
+    ta.close = TR_CLOSE_FINISH;
+    ta.close_arg = (uint32_t)sh.pow_bits;
+    ta.status = d_status;
+    launch_transcript(tr, ta, st);
+  }
   // query rounds
   qy.chal = chal;
   qy.num_queries = sh.num_queries;
@@ -461,10 +457,8 @@ void DeviceCircuit::ensure_ctx(size_t count) {
   x.chal = DevMem(CH_WORDS);
   x.alpha_pows = DevMem(2 * ALPHA_POWS);
   {
-    // z^t, t <= 1024, followed by the per-chunk partial sums of the widest oracle (launch_eval_polys)
-    const size_t chunks = c_.degree_bits > 16 ? ((size_t)1 << (c_.degree_bits - 16)) : 1;
-    size_t widest = std::max<size_t>({(size_t)layout_.oracle_width[0], (size_t)W, (size_t)nz, (size_t)nq});
-    x.eval_pows = DevMem(2 * 1026 + 2 * widest * chunks);
+    // the power tables of zeta and g zeta, followed by the per-chunk partial sums of the openings (launch_eval_jobs)
+    x.eval_pows = DevMem(eval_scratch_words(2, (size_t)layout_.oracle_width[0] + W + nz + nq + NC, (uint32_t)c_.degree_bits));
   }
   x.fri_comp = DevMem(4 * n);
   size_t total_polys = layout_.oracle_width[0] + layout_.oracle_width[1] + layout_.oracle_width[2] + layout_.oracle_width[3];
@@ -568,8 +562,20 @@ void DeviceCircuit::prove_one(Ctx& x, int buf, size_t Bstride, uint32_t p, u64* 
   auto mark = [&]() {
     if (t) P25_HIP(hipEventRecord(x.ev[evi++], st));
   };
-  auto d2d = [&](u64* dst, const u64* src, size_t words) {
-    P25_HIP(hipMemcpyAsync(dst, src, words * 8, hipMemcpyDeviceToDevice, st));
+  // observe a Merkle cap (and store it to the proof), draw challenges, closing action
+  auto observe_cap = [&](const u64* cap, size_t proof_off, u64* chal_out, uint32_t n_chal, uint32_t close, uint32_t close_arg,
+                         u64* close_out, bool with_preamble = false) {
+    TranscriptArgs ta{};
+    if (with_preamble) ta.seg[ta.n_seg++] = TrSegment{x.preamble.p, nullptr, nullptr, 8};
+    ta.seg[ta.n_seg++] = TrSegment{cap, nullptr, d_proof + proof_off, (uint32_t)capw};
+    ta.init = with_preamble;
+    ta.chal_out = chal_out;
+    ta.n_chal = n_chal;
+    ta.close = close;
+    ta.close_arg = close_arg;
+    ta.close_out = close_out;
+    ta.status = d_status;
+    launch_transcript(tr, ta, st);
   };
   mark();  // 0
   // "compute full witness" + "compute wire polynomials"
@@ -598,9 +604,7 @@ void DeviceCircuit::prove_one(Ctx& x, int buf, size_t Bstride, uint32_t p, u64* 
     launch_merkle_tree(x.wires_lde.p, B, W, B, cap_h, x.wires_tree.p, st, e0, e1, single_proof_);
   }
   const u64* wires_cap = x.wires_tree.p + tw - capw;
-  d2d(d_proof + L.wires_cap, wires_cap, capw);
-  launch_transcript(tr, 1, x.preamble.p, 8, chal, 0, st);
-  launch_transcript(tr, 0, wires_cap, (uint32_t)capw, chal + CH_BETAS, 2 * NC, st);  // betas, gammas
+  observe_cap(wires_cap, L.wires_cap, chal + CH_BETAS, 2 * NC, TR_CLOSE_NONE, 0, nullptr, true);  // preamble first; betas, gammas
   mark();  // 2
   // "compute partial products"
   enqueue_partial_products(x, st);
@@ -609,33 +613,39 @@ void DeviceCircuit::prove_one(Ctx& x, int buf, size_t Bstride, uint32_t p, u64* 
   ntt_inverse_then_lde(tables_, x.zs_vals.p, n, x.tmp.p, n, x.zs_coeffs.p, n, x.zs_lde.p, B, db, rb, nz, gl::GENERATOR, st);
   launch_merkle_tree(x.zs_lde.p, B, nz, B, cap_h, x.zs_tree.p, st, nullptr, nullptr, single_proof_);
   const u64* zs_cap = x.zs_tree.p + tw - capw;
-  d2d(d_proof + L.zs_cap, zs_cap, capw);
-  launch_transcript(tr, 0, zs_cap, (uint32_t)capw, chal + CH_ALPHAS, NC, st);
+  // alphas; the same wave writes the quotient kernel's alpha-power table (NC = 2: checked by the constructor)
+  observe_cap(zs_cap, L.zs_cap, chal + CH_ALPHAS, NC, TR_CLOSE_ALPHA_POWS, 0, x.alpha_pows.p);
   mark();  // 4
   // "compute quotient polys"
-  enqueue_quotient(x, st);
+  enqueue_quotient(x, st, false);
   mark();  // 5
   // "split up quotient polys" (chunks of n are contiguous: [NC][8][n] == [16][n]) + "commit to quotient polys"
   ntt_lde_bitrev(tables_, x.q_coeffs.p, n, x.q_lde.p, B, db, rb, nq, gl::GENERATOR, st);
   launch_merkle_tree(x.q_lde.p, B, nq, B, cap_h, x.q_tree.p, st, nullptr, nullptr, single_proof_);
   const u64* q_cap = x.q_tree.p + tw - capw;
-  d2d(d_proof + L.quotient_cap, q_cap, capw);
-  launch_transcript(tr, 0, q_cap, (uint32_t)capw, chal + CH_ZETA, 2, st);
-  hipLaunchKernelGGL(k_check_zeta, dim3(1), dim3(1), 0, st, chal, (uint32_t)db, d_status);
+  observe_cap(q_cap, L.quotient_cap, chal + CH_ZETA, 2, TR_CLOSE_CHECK_ZETA, (uint32_t)db, nullptr);  // zeta, not in the subgroup
   mark();  // 6
   // "construct the opening set"
   {
     const u64 g = gl::root_of_unity(db);
-    launch_eval_polys(cs_coeffs_.p, L.oracle_width[0], db, chal + CH_ZETA, 1, x.eval_pows.p, d_proof + L.constants, st);
-    launch_eval_polys(x.wires_coeffs.p, W, db, chal + CH_ZETA, 1, x.eval_pows.p, d_proof + L.wires, st, true);
-    launch_eval_polys(x.zs_coeffs.p, NC, db, chal + CH_ZETA, 1, x.eval_pows.p, d_proof + L.zs, st, true);
-    launch_eval_polys(x.zs_coeffs.p + (size_t)NC * n, NC * NP, db, chal + CH_ZETA, 1, x.eval_pows.p, d_proof + L.pps, st, true);
-    launch_eval_polys(x.q_coeffs.p, nq, db, chal + CH_ZETA, 1, x.eval_pows.p, d_proof + L.quotient, st, true);
-    launch_eval_polys(x.zs_coeffs.p, NC, db, chal + CH_ZETA, g, x.eval_pows.p, d_proof + L.zs_next, st);
-    // observe: constants|sigmas|wires|zs, then pps|quotient, then zs_next; then FRI alpha
-    launch_transcript(tr, 0, d_proof + L.constants, (uint32_t)(L.zs_next - L.constants), chal, 0, st);
-    launch_transcript(tr, 0, d_proof + L.pps, (uint32_t)(L.fri_caps - L.pps), chal, 0, st);
-    launch_transcript(tr, 0, d_proof + L.zs_next, (uint32_t)(L.pps - L.zs_next), chal + CH_FRI_ALPHA, 2, st);
+    const EvalJob jobs[6] = {{cs_coeffs_.p, d_proof + L.constants, L.oracle_width[0], 0},
+                             {x.wires_coeffs.p, d_proof + L.wires, (uint32_t)W, 0},
+                             {x.zs_coeffs.p, d_proof + L.zs, (uint32_t)NC, 0},
+                             {x.zs_coeffs.p + (size_t)NC * n, d_proof + L.pps, (uint32_t)(NC * NP), 0},
+                             {x.q_coeffs.p, d_proof + L.quotient, (uint32_t)nq, 0},
+                             {x.zs_coeffs.p, d_proof + L.zs_next, (uint32_t)NC, 1}};
+    const u64 scales[2] = {1, g};
+    launch_eval_jobs(jobs, 6, db, chal + CH_ZETA, scales, 2, x.eval_pows.p, st);
+    {  // observe: constants|sigmas|wires|zs, then pps|quotient, then zs_next; then FRI alpha
+      TranscriptArgs ta{};
+      ta.seg[0] = TrSegment{d_proof + L.constants, nullptr, nullptr, (uint32_t)(L.zs_next - L.constants)};
+      ta.seg[1] = TrSegment{d_proof + L.pps, nullptr, nullptr, (uint32_t)(L.fri_caps - L.pps)};
+      ta.seg[2] = TrSegment{d_proof + L.zs_next, nullptr, nullptr, (uint32_t)(L.pps - L.zs_next)};
+      ta.n_seg = 3;
+      ta.chal_out = chal + CH_FRI_ALPHA;
+      ta.n_chal = 2;
+      launch_transcript(tr, ta, st);
+    }
     mark();  // 7
     // "compute opening proofs": batch, divide, multiply by X
     FriCombineArgs fa;
@@ -718,11 +728,11 @@ void DeviceCircuit::enqueue_partial_products(Ctx& x, hipStream_t st) {
 
 // "compute quotient polys": quotient values on the coset from the wires / Z LDEs and the challenge block, then the
 // coset iNTT to 8n coefficients per challenge (= the NC x 8 chunks of n, contiguous).
-void DeviceCircuit::enqueue_quotient(Ctx& x, hipStream_t st) {
+void DeviceCircuit::enqueue_quotient(Ctx& x, hipStream_t st, bool alpha_table) {
   const size_t B = big();
   const int NC = c_.cfg.num_challenges, lde_bits = c_.degree_bits + c_.cfg.rate_bits;
   u64* chal = x.chal.p;
-  launch_alpha_pows(chal, x.alpha_pows.p, st);
+  if (alpha_table) launch_alpha_pows(chal, x.alpha_pows.p, st);  // prove_one: the transcript launch that drew the alphas wrote it
   {
     QuotientArgs qa = qa_proto_;
     qa.wires_lde = x.wires_lde.p;
@@ -810,11 +820,23 @@ void transcript_script(const u64* obs, const uint32_t* seg_len, const uint32_t* 
   check_canonical(obs, n_obs, "observed words");
   DevMem d_tr(sizeof(Transcript) / 8 + 1), d_obs(n_obs + 1), d_out(n_out + 1);
   P25_HIP(hipMemcpy(d_obs.p, obs, n_obs * 8, hipMemcpyHostToDevice));
-  size_t o = 0, c = 0;
-  for (size_t k = 0; k < n_seg; k++) {
-    launch_transcript((Transcript*)d_tr.p, k == 0, d_obs.p + o, seg_len[k], d_out.p + c, n_chal[k], 0);
-    o += seg_len[k];
-    c += n_chal[k];
+  // Up to four segments to a launch; challenges can only be drawn at the end of one, so a launch also ends after a
+  // segment that draws some.
+  size_t o = 0, c = 0, k = 0;
+  bool first = true;
+  while (k < n_seg) {
+    TranscriptArgs ta{};
+    ta.init = first;
+    ta.chal_out = d_out.p + c;
+    while (k < n_seg && ta.n_seg < TR_MAX_SEGMENTS) {
+      ta.seg[ta.n_seg++] = TrSegment{d_obs.p + o, nullptr, nullptr, seg_len[k]};
+      o += seg_len[k];
+      ta.n_chal = n_chal[k];
+      c += n_chal[k];
+      if (n_chal[k++]) break;
+    }
+    launch_transcript((Transcript*)d_tr.p, ta, 0);
+    first = false;
   }
   if (!n_seg) return;
   P25_HIP(hipMemcpy(out, d_out.p, n_out * 8, hipMemcpyDeviceToHost));

@@ -43,10 +43,35 @@ struct Transcript {
   u64 out[8];
   uint32_t n_in, n_out;
 };
-// init != 0: reset the transcript first.  Observes obs[0..n_obs), then draws n_chal challenges.
+// One launch of the transcript kernel: observe up to TR_MAX_SEGMENTS segments in order, draw n_chal challenges, then one
+// closing action that uses the challenges just drawn (from the wave's registers).
+constexpr uint32_t TR_MAX_SEGMENTS = 4;
+struct TrSegment {
+  const u64* src;   // n_words words; or, with src_b, the components of n_words / 2 extension elements:
+  const u64* src_b; //   word i = (i odd ? src_b : src)[i / 2]  (nullable)
+  u64* copy_dst;    // nullable: the observed words are also stored here (a cap, the final polynomial, the PoW witness -> proof)
+  uint32_t n_words;
+};
+enum : uint32_t {
+  TR_CLOSE_NONE = 0,
+  TR_CLOSE_ALPHA_POWS,  // challenges 0, 1 = alphas: close_out[c * ALPHA_POWS + j] = alpha_c^j (the quotient kernel's table)
+  TR_CLOSE_CHECK_ZETA,  // challenges 0, 1 = zeta: status 6 if zeta^(2^close_arg) = 1
+  TR_CLOSE_POW_INIT,    // *close_out = ~0 (no PoW witness found yet)
+  TR_CLOSE_FINISH       // first observed word = PoW witness, challenge 0 = PoW response: status 7 if there is no witness
+                        // or the response has fewer than close_arg leading zero bits
+};
+struct TranscriptArgs {
+  TrSegment seg[TR_MAX_SEGMENTS];
+  uint32_t n_seg, init /* != 0: reset the transcript first */, n_chal, close, close_arg;
+  u64* chal_out;
+  u64* close_out;
+  uint32_t* status;
+};
+void launch_transcript(Transcript* d_tr, const TranscriptArgs& a, hipStream_t st);
+// the one-segment form: observes obs[0..n_obs), then draws n_chal challenges
 void launch_transcript(Transcript* d_tr, int init, const u64* d_obs, uint32_t n_obs, u64* d_chal_out,
                        uint32_t n_chal, hipStream_t st);
-// observe two buffers back to back (e.g. openings at zeta, then at g*zeta)
+// *d_result = the smallest PoW witness for the transcript's current state; the caller has set it to ~0 (TR_CLOSE_POW_INIT)
 void launch_pow_search(const Transcript* d_tr, int pow_bits, u64* d_result, hipStream_t st);
 // Public inputs of proof p of a witness pass: values[i] = vals[pi_slots[i] * B + p] -> d_values_out[n] (the flat
 // proof's public_inputs section) and their hash_no_pad (upstream `C::InnerHasher::hash_no_pad(&public_inputs)`) ->
@@ -101,7 +126,18 @@ void launch_zpp(const ZppArgs& a, hipStream_t st);
 // openings: evaluates n_polys coefficient vectors (length n, stride n) at the extension point read
 // from d_point[0..2) (optionally multiplied by `scale`), writing (a, b) pairs to out[2*n_polys].
 void launch_eval_polys(const u64* d_coeffs, uint32_t n_polys, uint32_t log_n, const u64* d_point, u64 scale,
-                       u64* d_scratch_pows /*[2*1026 + 2*n_polys*chunks]*/, u64* d_out, hipStream_t st, bool reuse_pows = false);
+                       u64* d_scratch_pows /*[eval_scratch_words(1, n_polys, log_n)]*/, u64* d_out, hipStream_t st);
+// The same for several slices of coefficient matrices in ONE grid: job j evaluates its n_polys polynomials at
+// scale[point] * d_point and writes them to its own `out`.
+constexpr uint32_t EVAL_MAX_JOBS = 6;
+struct EvalJob {
+  const u64* coeffs;
+  u64* out;
+  uint32_t n_polys, point;
+};
+size_t eval_scratch_words(uint32_t n_points, size_t total_polys, uint32_t log_n);
+void launch_eval_jobs(const EvalJob* jobs, uint32_t n_jobs, uint32_t log_n, const u64* d_point, const u64* scale,
+                      uint32_t n_points /* <= 2 */, u64* d_scratch, hipStream_t st);
 
 // FRI
 struct FriCombineArgs {

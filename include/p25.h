@@ -121,10 +121,33 @@ p25_status p25_lde_commit(const uint64_t* polys, unsigned log_n, size_t n_polys,
                           unsigned rate_bits, unsigned cap_height, uint64_t* coeffs_out,
                           uint64_t* lde_out, uint64_t* cap_out);
 
-/* Device-resident variants for benchmarking: all pointers are HIP device addresses owned by the
- * caller, `stream` is a hipStream_t (NULL = default stream).  Asynchronous: the caller synchronises.
- * d_tree must hold p25_merkle_tree_words(n_leaves, cap_height) words; the cap is its last
- * 4 * 2^cap_height words.  d_tmp must hold n_polys * 2^log_n words. */
+/* Device-resident variants (bench.py, tools/, a host that keeps its data in HBM): all pointers are HIP device addresses
+ * owned by the caller, `stream` is a hipStream_t (NULL = default stream).  Asynchronous: every launch goes to `stream`
+ * and nowhere else, behind what the stream already holds; the caller synchronises.  They compute what the host forms
+ * compute (tests/test_gpu_device_entry_points.py).
+ *
+ * Where they read and write -- every buffer is touched inside the extent given here and nowhere else:
+ *   p25_poseidon_permute_dev  d_states[n][12] in place; n = 0 touches nothing.
+ *   p25_merkle_commit_dev     column c of leaf l is d_leaves_cm[c * col_stride + l], l < n_leaves, c < width:
+ *                             `col_stride` is the distance in words between the starts of two columns, >= n_leaves
+ *                             (= n_leaves for a packed matrix; larger when the columns are rows of a wider array).  The
+ *                             col_stride - n_leaves words between two columns are neither read nor written, and nothing
+ *                             is read behind word (width - 1) * col_stride + n_leaves.  Read-only input.
+ *                             d_tree receives exactly p25_merkle_tree_words(n_leaves, cap_height) words, leaf digests
+ *                             first; the cap is its last 4 * 2^cap_height words (cap_height = log2(n_leaves): the leaf
+ *                             digests are the cap).  width <= 2^20, as for the host form.
+ *   p25_lde_commit_dev        d_polys[n_polys][2^log_n] is read-only.  from_coeffs = 0: d_coeffs[n_polys][2^log_n]
+ *                             receives the coefficients and d_tmp (scratch) must hold n_polys * 2^log_n words; both are
+ *                             required.  from_coeffs = 1: d_polys are the coefficients; d_coeffs and d_tmp are not
+ *                             touched and may be NULL.  d_lde[n_polys][2^(log_n + rate_bits)] is required.  d_tree
+ *                             may be NULL (no commitment); otherwise it receives exactly
+ *                             p25_merkle_tree_words(2^(log_n + rate_bits), cap_height) words as above.
+ *                             cap_height > log_n + rate_bits is P25_ERR_INVALID_ARG, as for p25_lde_commit, with or
+ *                             without d_tree, and nothing is launched.
+ * The same holds wherever a stride is passed (proof_stride_words below): the words between one element and the next are
+ * neither read nor written.
+ * Alignment: a uint64_t buffer needs the alignment of a uint64_t (8 bytes), a uint32_t status array that of a uint32_t,
+ * and nothing more -- no kernel uses a wider access than the element it moves. */
 p25_status p25_merkle_commit_dev(const uint64_t* d_leaves_cm, size_t col_stride, size_t n_leaves,
                                  size_t width, unsigned cap_height, uint64_t* d_tree, void* stream);
 p25_status p25_lde_commit_dev(const uint64_t* d_polys, unsigned log_n, size_t n_polys, int from_coeffs,
@@ -304,6 +327,12 @@ p25_status p25_circuit_digest(p25_circuit* c, uint64_t* digest4, uint64_t* const
  *                                 filler is SplitMix64(seed, wire) and proofs are deterministic.
  *                                 NULL = seed i for proof i.
  *   proofs_out[n_proofs][proof_stride_words]   flat proofs (layout below), stride >= proof_words
+ *                                 (P25_ERR_INVALID_ARG below it); proof i is the proof_words words at
+ *                                 i * proof_stride_words, and the proof_stride_words - proof_words words behind it are
+ *                                 neither read nor written -- also behind a proof that failed.  The same in every entry
+ *                                 point that takes a proof_stride_words (p25_gather_proofs moves whole strides: its
+ *                                 n * proof_stride_words words arrive, padding included).  n_proofs = 0: P25_OK,
+ *                                 nothing written.
  *   per_proof_status[n_proofs]    P25_OK or the upstream failure mode (P25_ERR_WITNESS_CONFLICT ...);
  *                                 a bad witness fails that proof only.
  *   timings (nullable)            device milliseconds per upstream phase, summed over the batch.

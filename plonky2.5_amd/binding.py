@@ -584,14 +584,16 @@ class Circuit:
         _check(lib().p25_quotient(self._h, _ptr(w), _ptr(z), _ptr(b), _ptr(g), _ptr(a), _ptr(out)))
         return out
 
-    def prove(self, inputs, seeds=None, timings=False):
-        """inputs: [n_proofs][num_inputs].  Returns (proofs [n_proofs][proof_words], statuses[, timings])."""
+    def prove(self, inputs, seeds=None, timings=False, proof_stride=None):
+        """inputs: [n_proofs][num_inputs].  Returns (proofs [n_proofs][proof_words], statuses[, timings]).
+        proof_stride (>= proof_words): the proofs come back as [n_proofs][proof_stride], proof i in the first proof_words
+        words of row i; the words behind it are the zeros the array was made with (the library does not touch them)."""
         inp = _u64(inputs)
         if inp.ndim == 1:
             inp = inp.reshape(1, -1)
         n = inp.shape[0]
         assert inp.shape[1] == int(self.info.num_inputs)
-        pw = int(self.info.proof_words)
+        pw = int(self.info.proof_words) if proof_stride is None else int(proof_stride)
         proofs = np.zeros((n, pw), dtype=np.uint64)
         st = np.zeros(n, dtype=np.int32)
         sd = _u64(seeds) if seeds is not None else None
@@ -600,11 +602,11 @@ class Circuit:
                                      C.byref(tm) if timings else None))
         return (proofs, st, tm) if timings else (proofs, st)
 
-    def prove_filler(self, inputs, filler):
+    def prove_filler(self, inputs, filler, proof_stride=None):
         """prove() with explicit RandomValueGenerator values filler[n_proofs][num_random_fill] instead of seeds."""
         inp = _u64(inputs).reshape(-1, int(self.info.num_inputs))
         f = _u64(filler).reshape(inp.shape[0], int(self.info.num_random_fill))
-        pw = int(self.info.proof_words)
+        pw = int(self.info.proof_words) if proof_stride is None else int(proof_stride)
         proofs = np.zeros((inp.shape[0], pw), dtype=np.uint64)
         st = np.zeros(inp.shape[0], dtype=np.int32)
         _check(lib().p25_prove_batch_filler(self._h, _ptr(inp), inp.shape[0], _ptr(f), _ptr(proofs), pw, _ptr(st)))

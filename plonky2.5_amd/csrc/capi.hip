@@ -527,6 +527,8 @@ p25_status p25_lde_commit(const uint64_t* polys, unsigned log_n, size_t n_polys,
 p25_status p25_merkle_commit_dev(const uint64_t* d_leaves_cm, size_t col_stride, size_t n_leaves,
                                  size_t width, unsigned cap_height, uint64_t* d_tree, void* stream) {
   return guarded([&]() -> p25_status {
+    // the host form's bound (the launch takes the width as an int); first, so that the refusal names its reason
+    if (width > (1u << 20)) throw std::invalid_argument("p25_merkle_commit_dev: width above 2^20");
     if (!is_pow2(n_leaves) || cap_height > 40 || n_leaves < ((size_t)1 << cap_height) || !width ||
         col_stride < n_leaves || !d_leaves_cm || !d_tree)
       throw std::invalid_argument("p25_merkle_commit_dev: bad shape");
@@ -540,6 +542,10 @@ p25_status p25_lde_commit_dev(const uint64_t* d_polys, unsigned log_n, size_t n_
                               unsigned rate_bits, unsigned cap_height, uint64_t* d_coeffs,
                               uint64_t* d_tmp, uint64_t* d_lde, uint64_t* d_tree, void* stream) {
   return guarded([&]() -> p25_status {
+    // as the host form: a cap above the leaves has no tree (p25_merkle_tree_words answers 0 words for it), yet the leaf
+    // kernel would still write 4 << (log_n + rate_bits) words into d_tree.  Refused whether or not d_tree is given.
+    if (log_n <= 20 && rate_bits <= 3 && cap_height > log_n + rate_bits)
+      throw std::invalid_argument("p25_lde_commit_dev: cap_height above log_n + rate_bits");
     if (!d_polys || !n_polys || log_n > 20 || rate_bits > 3 || !d_lde ||
         (!from_coeffs && (!d_coeffs || !d_tmp)))
       throw std::invalid_argument("p25_lde_commit_dev: bad shape");

@@ -245,12 +245,18 @@ DEVICE_NULL = {
     "merkle_commit/canonical": ("non-canonical field element",
                                 lambda f: f.lib.p25_merkle_commit(_p(f.noncanon), 8, 1, 0, _p(f.u64), None)),
     "merkle_commit_dev": ("bad shape", lambda f: f.lib.p25_merkle_commit_dev(None, 8, 8, 1, 0, None, None)),
+    "merkle_commit_dev/stride": ("bad shape", lambda f: f.lib.p25_merkle_commit_dev(None, 7, 8, 1, 0, None, None)),
+    "merkle_commit_dev/width": ("width above 2^20",
+                                lambda f: f.lib.p25_merkle_commit_dev(None, 8, 8, (1 << 20) + 1, 0, None, None)),
     "lde_commit": ("bad shape", lambda f: f.lib.p25_lde_commit(None, 3, 1, 0, 1, 0, None, None, None)),
     "lde_commit/canonical": ("non-canonical field element",
                              lambda f: f.lib.p25_lde_commit(_p(f.noncanon), 3, 1, 0, 1, 0, None, None, _p(f.u64))),
     "lde_commit/canonical_coeffs": ("non-canonical field element",
                                     lambda f: f.lib.p25_lde_commit(_p(f.noncanon), 3, 1, 1, 1, 0, None, None, _p(f.u64))),
     "lde_commit_dev": ("bad shape", lambda f: f.lib.p25_lde_commit_dev(None, 3, 1, 0, 1, 0, None, None, None, None, None)),
+    "lde_commit_dev/cap": ("cap_height above log_n + rate_bits",
+                           lambda f: f.lib.p25_lde_commit_dev(None, 2, 1, 0, 1, 4, None, None, None, None, None)),
+    "lde_commit/cap": ("bad shape", lambda f: f.lib.p25_lde_commit(_p(f.u64), 2, 1, 0, 1, 4, None, None, _p(f.u64))),
     "circuit_to_bytes": ("null argument", lambda f: f.lib.p25_circuit_to_bytes(f.h, None, None)),
     "circuit_digest/c": ("null argument", lambda f: f.lib.p25_circuit_digest(None, _p(f.u64), None)),
     "circuit_digest/digest": ("null argument", lambda f: f.lib.p25_circuit_digest(f.h, None, None)),

@@ -93,6 +93,27 @@ def test_python_dft_equals_the_oracle_on_edge_columns(oracle, log_n):
             assert (lo[k] == ev.coset_lde_naive(coeffs, 3)).all(), (name, from_coeffs)
 
 
+@pytest.mark.parametrize("log_n", list(range(7)))
+def test_oracle_lde_over_the_small_end_of_the_accepted_domain(oracle, log_n):
+    """oracle.lde_commit == a direct DFT and Horner at 7 w^i in Python integers for log_n 0..6, every rate_bits 0..3 and
+    both from_coeffs values, two polynomials each: the reference of tests/test_gpu_device_entry_points.py's sweep over
+    the domain p25_lde_commit accepts, checked where the naive forms can go -- sizes 1, 2 and 4 and rate 0 included,
+    which nothing ran before.  The oracle refuses none of these shapes."""
+    n = 1 << log_n
+    vals = np.stack([ev.edge(n, 60 + log_n), ev.uniform(n, 61 + log_n)])
+    for rate in range(4):
+        for from_coeffs in (False, True):
+            co, lo, cap = oracle.lde_commit(vals, rate, 0, from_coeffs)
+            assert lo.shape == (2, n << rate) and (lo < np.uint64(P)).all() and (cap < np.uint64(P)).all()
+            for k in range(2):
+                coeffs = vals[k] if from_coeffs else ev.intt_naive(vals[k])
+                assert (co[k] == coeffs).all(), (log_n, rate, from_coeffs, k)
+                assert (lo[k] == ev.coset_lde_naive(coeffs, rate)).all(), (log_n, rate, from_coeffs, k)
+            # the cap over the leaves (lde[0..2][l])_l: a leaf of two words is its own digest, padded with zeros
+            if log_n + rate == 0:
+                assert cap.tolist() == [[int(lo[0, 0]), int(lo[1, 0]), 0, 0]]
+
+
 def test_python_horner_equals_the_oracle_on_edge_coefficients(oracle):
     """Horner in F_p[X]/(X^2 - 7) with the scale argument of p25_eval_polys == oracle.eval_polys, 2^10 coefficients."""
     n = 1 << 10

@@ -38,7 +38,15 @@ enum {
    * an effect (below).  The one status that is a warning, not a failure. */
   P25_WARN_HW_QUEUES_LATE = 9,
   /* p25_comm_* / p25_gather_proofs: librccl could not be loaded, or an RCCL call failed (p25_last_error has its text) */
-  P25_ERR_RCCL = 10
+  P25_ERR_RCCL = 10,
+  /* per-proof verdicts of p25_verify_batch[_dev]; P25_OK = accepted */
+  P25_REJECT_VANISHING = 20,       /* vanishing(zeta) != Z_H(zeta) * t(zeta) */
+  P25_REJECT_POW = 21,             /* proof-of-work response has too few leading zeros */
+  P25_REJECT_MALFORMED = 22,       /* a proof word >= p */
+  P25_REJECT_INITIAL_MERKLE = 23,  /* a Merkle path of one of the four initial oracles does not reach its cap */
+  P25_REJECT_FRI_EVAL = 24,        /* a FRI layer's opened value != the value folded so far */
+  P25_REJECT_FRI_MERKLE = 25,      /* a FRI layer's Merkle path does not reach its cap */
+  P25_REJECT_FINAL_POLY = 26       /* the final polynomial != the last folded value */
 };
 
 /* Last error message of the calling thread ("" if none). */
@@ -436,6 +444,27 @@ p25_status p25_circuit_kernel_stats(p25_circuit* c, int enable, int reset, doubl
 /* Measurement hook: the shader clock (Hz) under a full-chip Poseidon load, from the in-kernel cycle counter against
  * the constant-rate wall-clock counter; bench.py prices its VALU-instruction view with it instead of a nominal clock. */
 p25_status p25_shader_clock_hz(double* hz_out);
+/* ------------------------------------------------------------------------------------------
+ * Verifying.  Replaces `data.verify(proof)` (src/p3/mod.rs:266) for a batch of flat proofs of circuit `c`: per proof, P25_OK
+ * or the P25_REJECT_* code of the FIRST check the sequential verifier fails, in this order: a word >= p anywhere in the
+ * proof (public inputs included; also checked by the device form, unlike the proving *_dev entries), the vanishing
+ * identity at zeta, the proof of work, then the queries in index order -- inside a query the four initial Merkle paths,
+ * then per FRI layer the evaluation check and the layer's Merkle path, then the final polynomial.
+ *   digest4[4], cs_cap[2^cap_height][4]   the verifier data (p25_circuit_digest), HOST pointers in both forms, canonical
+ *                                 words; both NULL = the circuit's own, exactly one NULL = P25_ERR_INVALID_ARG.
+ *   proofs[n_proofs][proof_stride_words]  stride >= proof_words (P25_ERR_INVALID_ARG below it); the words behind a proof
+ *                                 are neither read nor written.  n_proofs = 0: P25_OK, nothing touched.
+ * One launch per stage over the whole batch; no proving context is allocated (about 100 words of device scratch per
+ * proof).  There is no CPU path: P25_ERR_NO_DEVICE without a GPU.
+ * ------------------------------------------------------------------------------------------ */
+p25_status p25_verify_batch(p25_circuit* c, const uint64_t* digest4, const uint64_t* cs_cap, const uint64_t* proofs,
+                            size_t n_proofs, size_t proof_stride_words, p25_status* per_proof_status);
+/* Same with the proofs and d_status (uint32_t[n_proofs]) resident in HBM.  Enqueues on the circuit's stream, behind every
+ * proof the circuit has been asked for so far, and returns: p25_circuit_sync waits, p25_circuit_stream_join and
+ * p25_circuit_mark order a caller's stream or another circuit behind it, as for p25_prove_batch_dev. */
+p25_status p25_verify_batch_dev(p25_circuit* c, const uint64_t* digest4, const uint64_t* cs_cap, const uint64_t* d_proofs,
+                                size_t n_proofs, size_t proof_stride_words, uint32_t* d_status);
+
 /* Witness only (parity tests): wires_out[num_wires][2^degree_bits], column-major. */
 p25_status p25_witness(p25_circuit* c, const uint64_t* inputs, uint64_t seed, uint64_t* wires_out,
                        p25_status* proof_status);

@@ -8,7 +8,8 @@ __all__ = ["P25Error", "lib", "lib_path", "device_init", "shader_clock_hz", "pos
            "merkle_commit", "merkle_tree_words", "lde_commit", "EXPORTED_SYMBOLS", "P",
            "P3Config", "Circuit", "p3_proof_from_json", "Timings", "p3_prove_fibonacci", "p3_inputs_to_json",
            "Air", "p3_prove_air", "transcript", "fri_prove", "eval_polys", "RuntimeInfo", "runtime_info", "Comm",
-           "comm_unique_id", "WARN_HW_QUEUES_LATE"]
+           "comm_unique_id", "WARN_HW_QUEUES_LATE", "REJECT_VANISHING", "REJECT_POW", "REJECT_MALFORMED",
+           "REJECT_INITIAL_MERKLE", "REJECT_FRI_EVAL", "REJECT_FRI_MERKLE", "REJECT_FINAL_POLY"]
 
 P = 0xFFFFFFFF00000001
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -18,8 +19,12 @@ lib_path = os.path.join(_HERE, "libp25.so")
 
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "NO_DEVICE", 3: "HIP", 4: "WITNESS_CONFLICT",
                 5: "GENERATORS_NOT_RUN", 6: "OPENING_IN_SUBGROUP", 7: "INTERNAL", 8: "PARSE",
-                9: "WARN_HW_QUEUES_LATE", 10: "RCCL"}
+                9: "WARN_HW_QUEUES_LATE", 10: "RCCL", 20: "REJECT_VANISHING", 21: "REJECT_POW", 22: "REJECT_MALFORMED",
+                23: "REJECT_INITIAL_MERKLE", 24: "REJECT_FRI_EVAL", 25: "REJECT_FRI_MERKLE", 26: "REJECT_FINAL_POLY"}
 WARN_HW_QUEUES_LATE = 9
+# per-proof verdicts of Circuit.verify / verify_dev (0 = accepted): the first check the sequential verifier fails
+REJECT_VANISHING, REJECT_POW, REJECT_MALFORMED, REJECT_INITIAL_MERKLE = 20, 21, 22, 23
+REJECT_FRI_EVAL, REJECT_FRI_MERKLE, REJECT_FINAL_POLY = 24, 25, 26
 COMM_ID_BYTES = 128
 
 
@@ -166,6 +171,8 @@ EXPORTED_SYMBOLS = {
     "p25_prove_batch_filler": (i32, [vp, vp, sz, vp, vp, sz, vp]),
     "p25_prove_batch_dev": (i32, [vp, vp, sz, vp, vp, sz, vp, C.POINTER(Timings)]),
     "p25_prove_batch_dev_windows": (i32, [vp, vp, sz, sz, sz, vp, vp, sz, vp]),
+    "p25_verify_batch": (i32, [vp, vp, vp, vp, sz, sz, vp]),
+    "p25_verify_batch_dev": (i32, [vp, vp, vp, vp, sz, sz, vp]),
     "p25_device_init_ex": (i32, [C.c_int, C.c_int]),
     "p25_circuit_sync": (i32, [vp]),
     "p25_circuit_stream_join": (i32, [vp, vp]),
@@ -621,6 +628,32 @@ class Circuit:
         """p25_prove_batch_dev_windows: proof i reads its inputs at d_buffer + min(i * window_stride, last_window_offset) words."""
         _check(lib().p25_prove_batch_dev_windows(self._h, d_buffer, window_stride, last_window_offset, n_proofs, d_seeds,
                                                  d_proofs, proof_stride, d_status))
+
+    def _verifier_data(self, digest, cs_cap):
+        """(digest, cap) as uint64 arrays for the verify entry points; (None, None) = the circuit's own.  One of the two
+        alone is passed on as it is: the library refuses it."""
+        return (_u64(digest) if digest is not None else None, _u64(cs_cap) if cs_cap is not None else None)
+
+    def verify(self, proofs, digest=None, cs_cap=None, proof_stride=None):
+        """proofs: [n_proofs][proof_stride] flat proofs (proof_stride defaults to the row length, >= proof_words; the words
+        behind a proof are ignored).  Returns int32 statuses: 0 = accepted, otherwise the REJECT_* code of the first
+        check the sequential verifier fails.  digest / cs_cap: the verifier data (Circuit.digest()), None = this circuit's."""
+        p = _u64(proofs)
+        if p.ndim == 1:
+            p = p.reshape(1, -1)
+        n = p.shape[0]
+        stride = p.shape[1] if proof_stride is None else int(proof_stride)
+        assert p.shape[1] == stride
+        st = np.zeros(n, dtype=np.int32)
+        d, cap = self._verifier_data(digest, cs_cap)
+        _check(lib().p25_verify_batch(self._h, _ptr(d), _ptr(cap), _ptr(p), n, stride, _ptr(st)))
+        return st
+
+    def verify_dev(self, d_proofs, n_proofs, proof_stride, d_status, digest=None, cs_cap=None):
+        """Device-resident batch (raw device addresses; d_status: uint32[n_proofs]).  Enqueues behind the circuit's proofs
+        and returns; sync() / stream_join() / mark() order a reader behind it.  digest / cs_cap are host arrays."""
+        d, cap = self._verifier_data(digest, cs_cap)
+        _check(lib().p25_verify_batch_dev(self._h, _ptr(d), _ptr(cap), d_proofs, n_proofs, proof_stride, d_status))
 
     def sync(self):
         _check(lib().p25_circuit_sync(self._h))

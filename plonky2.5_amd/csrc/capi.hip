@@ -799,6 +799,21 @@ p25_status p25_prove_batch_dev_windows(p25_circuit* c, const uint64_t* d_buffer,
     return P25_OK;
   });
 }
+// ---- verifying ------------------------------------------------------------------------------------------------------
+p25_status p25_verify_batch(p25_circuit* c, const uint64_t* digest4, const uint64_t* cs_cap, const uint64_t* proofs,
+                            size_t n_proofs, size_t proof_stride_words, p25_status* per_proof_status) {
+  return with_device(c, (digest4 == nullptr) == (cs_cap == nullptr) && (!n_proofs || (proofs && per_proof_status)),
+                     [&](DeviceCircuit& d) {
+    if (n_proofs) d.verify_batch(digest4, cs_cap, proofs, n_proofs, proof_stride_words, per_proof_status);
+  });
+}
+p25_status p25_verify_batch_dev(p25_circuit* c, const uint64_t* digest4, const uint64_t* cs_cap, const uint64_t* d_proofs,
+                                size_t n_proofs, size_t proof_stride_words, uint32_t* d_status) {
+  return with_device(c, (digest4 == nullptr) == (cs_cap == nullptr) && (!n_proofs || (d_proofs && d_status)),
+                     [&](DeviceCircuit& d) {
+    if (n_proofs) d.verify_batch_dev(digest4, cs_cap, d_proofs, n_proofs, proof_stride_words, d_status);
+  });
+}
 p25_status p25_circuit_sync(p25_circuit* c) {
   return with_device(c, [&](DeviceCircuit& d) { d.sync(); });
 }

@@ -101,6 +101,15 @@ class DeviceCircuit {
                        uint32_t* d_status, PhaseTimes* times, const u64* d_filler = nullptr, size_t in_stride = 0,
                        size_t in_max_off = (size_t)-1);
   void sync();
+  // The batch verifier (verify.hip, kernels_verify.hip): statuses[i] = 0 or the P25_REJECT_* code of the first check
+  // proof i fails, in the sequential verifier's order.  digest4 / cs_cap: HOST pointers to the verifier data, both null =
+  // this circuit's own.  verify_batch_dev enqueues on the main stream, behind every proof the circuit has been asked
+  // for so far, and returns; sync / stream_join / mark cover it.  Needs no proving context: its scratch is ~100 words
+  // per proof.
+  void verify_batch_dev(const u64* digest4, const u64* cs_cap, const u64* d_proofs, size_t n_proofs, size_t proof_stride,
+                        uint32_t* d_status);
+  void verify_batch(const u64* digest4, const u64* cs_cap, const u64* proofs, size_t n_proofs, size_t proof_stride,
+                    int32_t* statuses);
   // Device-side ordering against a caller's stream, no host synchronisation (the multi-GPU gather runs on a side
   // stream underneath the next step's proofs):
   //   stream_join(ext):  `ext` waits for everything this circuit has enqueued so far (all proving streams)
@@ -161,6 +170,7 @@ class DeviceCircuit {
   size_t vals_batch_[2] = {0, 0};
   size_t pass_counter_ = 0;    // witness passes issued so far (parity = buffer)
   std::vector<DevMem> owned_;
+  DevMem verify_scratch_;      // verify_batch_dev: challenge blocks and vanishing partials of a batch, caller's verifier data
   bool kstats_on_ = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> kstats_pending_, kstats_free_;
   double kstats_ms_ = 0;

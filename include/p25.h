@@ -465,6 +465,74 @@ p25_status p25_verify_batch(p25_circuit* c, const uint64_t* digest4, const uint6
 p25_status p25_verify_batch_dev(p25_circuit* c, const uint64_t* digest4, const uint64_t* cs_cap, const uint64_t* d_proofs,
                                 size_t n_proofs, size_t proof_stride_words, uint32_t* d_status);
 
+/* ------------------------------------------------------------------------------------------
+ * The inner plonky3 STARK on the device.  In the reference the inner proof is produced OUTSIDE the crate and shipped as
+ * artifacts/proof_fibonacci.json; its data model is src/p3/serde/proof.rs:349-383 and the verifier it must satisfy is
+ * src/p3/verifier.rs.  A p25_p3_prover produces such proofs for one AIR and one shape, a batch at a time, as the words
+ * p25_p3_prove_air_ex returns for the same arguments -- bit for bit (field arithmetic is exact) -- which are the words
+ * p25_prove_batch[_dev] takes as `inputs`.  Stages: trace LDE on 7*<w> (bit-reversed), Poseidon2 MMCS without a cap,
+ * width-12 duplex challenger, AIR quotient from the p25_air DAG, chunk LDEs, openings at zeta and zeta*w_n, the identity
+ * self-check, two-adic FRI (log_n rounds), proof of work, query gather; one launch per stage for a whole group of proofs.
+ *
+ * p25_p3_prover_create   host only, works without a GPU.  Replaces the shape half of p25_p3_prove_air_ex: validates exactly
+ *     what that function validates, with the same P25_ERR_INVALID_ARG cases (the AIR itself; log_n 1..22, log_blowup 1..4,
+ *     log_n + log_blowup <= 24; num_queries >= 1; pow_bits 0..30; log_quotient_degree <= log_blowup), and compiles the AIR
+ *     into the register program the quotient kernel interprets.  LOCAL / NEXT / CONST nodes cost nothing; the device form's
+ *     own limits are 64 arithmetic-node values alive at the same time (after a liveness pass over the DAG in constraint
+ *     order), 2^20 instructions and 65535 queries: an AIR beyond them is refused HERE, with a message naming the limit,
+ *     never later.  Width 64 and 512 nodes are within them.  No device memory is touched before the first compute call.
+ * p25_p3_prover_config   the shape for p25_circuit_build_p3_verifier[_air] and the words per proof (either may be NULL).
+ *
+ * p25_p3_prove_batch     host buffers.  Replaces n_proofs calls of p25_p3_prove_air_ex.
+ *   traces[n_proofs][2^log_n][width]   row-major, packed back to back, every word < p
+ *   pow_starts[n_proofs]               first proof-of-work witness tried per proof, every word < p; NULL = 0 for all.  The
+ *                                      witness found is the SMALLEST witness >= pow_start, as the host loop finds it; the
+ *                                      search covers 2^(max(pow_bits, 12) + 6) candidates.  pow_bits = 0: pow_start itself.
+ *   inputs_out[n_proofs][input_stride_words]   proof i = num_inputs words in `add_virtual_to` order (proof.rs:357-373) at
+ *                                      i * input_stride_words; stride >= num_inputs (P25_ERR_INVALID_ARG below it); the
+ *                                      words behind a proof are neither read nor written.
+ *   per_proof_status[n_proofs]         what p25_p3_prove_air_ex returns for that trace: P25_OK; P25_ERR_INVALID_ARG: the
+ *                                      trace does not satisfy the AIR (the quotient identity at zeta fails, evaluated on
+ *                                      the device as the host evaluates it); P25_ERR_INTERNAL: the FRI fold did not end
+ *                                      constant or no witness lies in the search window.  A failed proof's num_inputs
+ *                                      words are zeros; it fails that proof only.
+ *   A trace word or pow_start >= p makes the whole call P25_ERR_INVALID_ARG and nothing is launched.  n_proofs = 0: P25_OK,
+ *   nothing touched.  Argument errors come first, then P25_ERR_NO_DEVICE without a GPU.
+ * p25_p3_prove_batch_dev  the same with everything resident in HBM: trace i at d_traces + i * trace_stride_words
+ *   (stride >= 2^log_n * width), d_pow_starts (nullable), d_inputs, d_status (uint32_t[n_proofs]).  Checks no words: the
+ *   caller keeps them canonical, as for the proving *_dev entries above.  ENQUEUE-ONLY: every launch and copy goes to
+ *   `stream` (a hipStream_t; NULL = the default stream), behind what the stream holds, and nowhere else; the caller
+ *   synchronises (or p25_p3_prover_sync).  Two exceptions block the host before anything is enqueued, and change no
+ *   ordering: the first compute call on a handle allocates its constant tables (AIR program, NTT twiddles) and fills them
+ *   with blocking copies, and a call that needs more scratch than the handle holds waits for the earlier calls and
+ *   reallocates.  A call after one of the same or a larger batch does neither.  Chaining into the outer prover on one stream, no host copy:
+ *       p25_p3_prove_batch_dev(pr, d_traces, ts, n, NULL, d_inputs, num_inputs, d_st, s);
+ *       p25_circuit_wait_stream(c, s);  p25_prove_batch_dev(c, d_inputs, n, d_seeds, d_proofs, stride, d_status, NULL);
+ * p25_p3_prover_sync     host waits for everything this prover has enqueued.
+ *
+ * Memory: the handle owns its scratch (trees, LDEs, FRI layers: about 40 words = 320 bytes per LDE point, ~660 MB for a
+ * 2^20-row width-3 proof) and reuses it across calls; it grows only after the earlier use has finished, and a growth that
+ * fails (P25_ERR_HIP) leaves the handle without scratch but usable: the next call allocates what it needs.  A batch runs in groups of as
+ * many proofs as fit a fixed budget of 12 GiB (at least one proof; p25_p3_prover_set_scratch_budget, host only, replaces the
+ * budget for the calls that follow, 0 = the default).  Grouping changes no output word.
+ * Threading: calls on one prover are serialised by the handle's mutex, as for circuits; different provers never contend.
+ * Streams: the calls of one prover share its scratch, so each call's work starts, on the device, behind the call enqueued
+ * before it, whichever stream that went to (an event wait on `stream`; the host form runs on a stream of the handle and
+ * is ordered the same way).  Calls on different streams are therefore legal and give the same words; they do not overlap.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct p25_p3_prover p25_p3_prover;
+p25_status p25_p3_prover_create(const p25_air* air, int32_t log_n, int32_t log_blowup, int32_t num_queries,
+                                int32_t pow_bits, p25_p3_prover** out);
+void p25_p3_prover_destroy(p25_p3_prover* p);
+p25_status p25_p3_prover_config(const p25_p3_prover* p, p25_p3_config* cfg_out, size_t* num_inputs_out);
+p25_status p25_p3_prove_batch(p25_p3_prover* p, const uint64_t* traces, size_t n_proofs, const uint64_t* pow_starts,
+                              uint64_t* inputs_out, size_t input_stride_words, p25_status* per_proof_status);
+p25_status p25_p3_prove_batch_dev(p25_p3_prover* p, const uint64_t* d_traces, size_t trace_stride_words, size_t n_proofs,
+                                  const uint64_t* d_pow_starts, uint64_t* d_inputs, size_t input_stride_words,
+                                  uint32_t* d_status, void* stream);
+p25_status p25_p3_prover_sync(p25_p3_prover* p);
+p25_status p25_p3_prover_set_scratch_budget(p25_p3_prover* p, size_t bytes);
+
 /* Witness only (parity tests): wires_out[num_wires][2^degree_bits], column-major. */
 p25_status p25_witness(p25_circuit* c, const uint64_t* inputs, uint64_t seed, uint64_t* wires_out,
                        p25_status* proof_status);

@@ -7,7 +7,7 @@ import numpy as np
 __all__ = ["P25Error", "lib", "lib_path", "device_init", "shader_clock_hz", "poseidon_permute", "poseidon2_permute",
            "merkle_commit", "merkle_tree_words", "lde_commit", "EXPORTED_SYMBOLS", "P",
            "P3Config", "Circuit", "p3_proof_from_json", "Timings", "p3_prove_fibonacci", "p3_inputs_to_json",
-           "Air", "p3_prove_air", "transcript", "fri_prove", "eval_polys", "RuntimeInfo", "runtime_info", "Comm",
+           "Air", "p3_prove_air", "P3Prover", "transcript", "fri_prove", "eval_polys", "RuntimeInfo", "runtime_info", "Comm",
            "comm_unique_id", "WARN_HW_QUEUES_LATE", "REJECT_VANISHING", "REJECT_POW", "REJECT_MALFORMED",
            "REJECT_INITIAL_MERKLE", "REJECT_FRI_EVAL", "REJECT_FRI_MERKLE", "REJECT_FINAL_POLY"]
 
@@ -208,6 +208,13 @@ EXPORTED_SYMBOLS = {
     "p25_comm_barrier": (i32, [vp]),
     "p25_comm_max_f64": (i32, [vp, C.POINTER(C.c_double)]),
     "p25_gather_proofs": (i32, [vp, vp, i32, vp, sz, vp, C.POINTER(sz), i32, vp, vp]),
+    "p25_p3_prover_create": (i32, [C.POINTER(AirC), i32, i32, i32, i32, C.POINTER(vp)]),
+    "p25_p3_prover_destroy": (None, [vp]),
+    "p25_p3_prover_config": (i32, [vp, C.POINTER(P3Config), C.POINTER(sz)]),
+    "p25_p3_prove_batch": (i32, [vp, vp, sz, vp, vp, sz, vp]),
+    "p25_p3_prove_batch_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, vp, vp]),
+    "p25_p3_prover_sync": (i32, [vp]),
+    "p25_p3_prover_set_scratch_budget": (i32, [vp, sz]),
     "p25_p3_prove_air": (i32, [C.POINTER(AirC), vp, i32, i32, i32, C.c_uint64, i32, vp, sz, C.POINTER(sz),
                                C.POINTER(P3Config)]),
 }
@@ -446,6 +453,63 @@ def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=
     out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_ex(C.byref(ac), _ptr(t), log_n, log_blowup, num_queries, pow_bits,
                                                                pow_start, threads, buf, cap, n, C.byref(cfg)), np.uint64)
     return out, cfg
+
+
+class P3Prover:
+    """p25_p3_prover: the plonky3 prover on the GPU for one AIR (binding.Air) and shape.  Produces, a batch at a time, the
+    words p3_prove_air returns for the same arguments -- the `inputs` of Circuit.prove / prove_dev."""
+
+    def __init__(self, air, log_n, log_blowup=1, num_queries=100, pow_bits=16):
+        ac = air.to_c()
+        h = vp()
+        _check(lib().p25_p3_prover_create(C.byref(ac), log_n, log_blowup, num_queries, pow_bits, C.byref(h)))
+        self._h = vp(h.value)
+        self.width, self.log_n = air.width, log_n
+        self.config = P3Config()
+        n = sz(0)
+        _check(lib().p25_p3_prover_config(self._h, C.byref(self.config), C.byref(n)))
+        self.num_inputs = int(n.value)
+
+    def prove(self, traces, pow_starts=None, input_stride=None):
+        """traces: uint64[n][2^log_n][width] (or one trace) -> (inputs[n][num_inputs], int32 statuses).  A failed proof's
+        row is zeros.  input_stride (>= num_inputs): rows of that length, the words behind a proof left as made."""
+        t = _u64(traces)
+        if t.ndim == 2:
+            t = t.reshape((1,) + t.shape)
+        if t.ndim != 3 or t.shape[1:] != (1 << self.log_n, self.width):
+            raise ValueError("traces must be [n][2^log_n][width]")
+        n = t.shape[0]
+        ps = _u64(pow_starts) if pow_starts is not None else None
+        if ps is not None and ps.size != n:
+            raise ValueError("pow_starts must hold one word per proof")
+        stride = self.num_inputs if input_stride is None else int(input_stride)
+        out = np.zeros((n, stride), dtype=np.uint64)
+        st = np.zeros(n, dtype=np.int32)
+        _check(lib().p25_p3_prove_batch(self._h, _ptr(t), n, _ptr(ps), _ptr(out), stride, _ptr(st)))
+        return out, st
+
+    def prove_dev(self, d_traces, trace_stride, n, d_pow_starts, d_inputs, input_stride, d_status, stream=0):
+        """Device-resident batch (raw device addresses), enqueued on `stream` (a raw hipStream_t; 0 = the default stream)."""
+        _check(lib().p25_p3_prove_batch_dev(self._h, d_traces, trace_stride, n, d_pow_starts, d_inputs, input_stride, d_status,
+                                            C.c_void_p(stream) if stream else None))
+
+    def sync(self):
+        _check(lib().p25_p3_prover_sync(self._h))
+
+    def set_scratch_budget(self, nbytes):
+        """Bytes of device scratch a group of proofs may take (0 = the default, 12 GiB); at least one proof per group."""
+        _check(lib().p25_p3_prover_set_scratch_budget(self._h, int(nbytes)))
+
+    def close(self):
+        if self._h:
+            h, self._h = self._h, None
+            lib().p25_p3_prover_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def p3_inputs_to_json(inputs, cfg):

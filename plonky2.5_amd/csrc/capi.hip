@@ -22,6 +22,7 @@
 #include "json_io.h"
 #include "p3_circuit.h"
 #include "p3_prover.h"
+#include "p3_kernels.h"
 #include "prover.h"
 #include "recursion.h"
 
@@ -168,6 +169,11 @@ struct p25_circuit {
   }
 };
 #define P25_LOCK(c) std::lock_guard<std::recursive_mutex> p25_lock_((c)->mu)
+
+struct p25_p3_prover {
+  std::unique_ptr<p25::P3ProverDev> dev;
+  std::recursive_mutex mu;   // one call at a time per prover, as for circuits
+};
 
 namespace p25 {
 namespace {
@@ -330,6 +336,19 @@ p25_status p3_prove_out(const P3ProveParams& prm, P3Config& pc, F&& prove, uint6
   }
   if (cfg_out) *cfg_out = to_c(pc);
   return P25_OK;
+}
+
+// the argument errors of the two compute entry points that need no device; returns false for an empty batch
+bool p3_prove_args(p25_p3_prover* p, const void* traces, size_t n_proofs, void* inputs, size_t input_stride, void* status,
+                   size_t trace_stride) {
+  if (!p) throw std::invalid_argument("null argument");
+  if (!n_proofs) return false;
+  if (!traces || !inputs || !status) throw std::invalid_argument("null argument");
+  if (input_stride < p->dev->num_inputs()) throw std::invalid_argument("input_stride smaller than the proof's num_inputs");
+  if (trace_stride < p->dev->trace_words()) throw std::invalid_argument("trace_stride smaller than the trace");
+  if (n_proofs > ((size_t)1 << 24) || input_stride > ((size_t)1 << 60) / n_proofs || trace_stride > ((size_t)1 << 60) / n_proofs)
+    throw std::invalid_argument("batch out of range (n_proofs * stride must stay below 2^60)");
+  return true;
 }
 
 p25_status build_verifier(const p25_p3_config* cfg, const Air& air, p25_circuit** out) {
@@ -619,6 +638,77 @@ p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_
       }
     };
     return p3_prove_out(prm, pc, prove, inputs_out, cap, n_out, cfg_out);
+  });
+}
+
+// ---- the plonky3 prover on the device -------------------------------------------------------------------------------
+p25_status p25_p3_prover_create(const p25_air* air, int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits,
+                                p25_p3_prover** out) {
+  return host_guarded([&]() -> p25_status {
+    if (!air || !out) throw std::invalid_argument("null argument");
+    const AirProgram prog = air_from_c(air);
+    std::unique_ptr<p25_p3_prover> h(new p25_p3_prover());
+    h->dev.reset(new P3ProverDev(prog, log_n, log_blowup, num_queries, pow_bits));
+    *out = h.release();
+    return P25_OK;
+  });
+}
+void p25_p3_prover_destroy(p25_p3_prover* p) { delete p; }
+p25_status p25_p3_prover_config(const p25_p3_prover* p, p25_p3_config* cfg_out, size_t* num_inputs_out) {
+  return host_guarded([&]() -> p25_status {
+    if (!p) throw std::invalid_argument("null argument");
+    if (cfg_out) *cfg_out = to_c(p->dev->config());
+    if (num_inputs_out) *num_inputs_out = p->dev->num_inputs();
+    return P25_OK;
+  });
+}
+p25_status p25_p3_prover_set_scratch_budget(p25_p3_prover* p, size_t bytes) {
+  return host_guarded([&]() -> p25_status {
+    if (!p) throw std::invalid_argument("null argument");
+    P25_LOCK(p);
+    p->dev->set_scratch_budget(bytes);
+    return P25_OK;
+  });
+}
+p25_status p25_p3_prove_batch(p25_p3_prover* p, const uint64_t* traces, size_t n_proofs, const uint64_t* pow_starts,
+                              uint64_t* inputs_out, size_t input_stride_words, p25_status* per_proof_status) {
+  return host_guarded([&]() -> p25_status {
+    if (!p3_prove_args(p, traces, n_proofs, inputs_out, input_stride_words, per_proof_status, p ? p->dev->trace_words() : 0))
+      return P25_OK;
+    const size_t tw = n_proofs * p->dev->trace_words();
+    for (size_t i = 0; i < tw; i++)
+      if (traces[i] >= gl::P) throw std::invalid_argument("non-canonical field element in a trace");
+    for (size_t i = 0; pow_starts && i < n_proofs; i++)
+      if (pow_starts[i] >= gl::P) throw std::invalid_argument("non-canonical field element in pow_starts");
+    const p25_status s = ensure_device();
+    if (s != P25_OK) return s;
+    P25_LOCK(p);
+    static_assert(sizeof(p25_status) == sizeof(int32_t), "p25_status is a 32-bit enum");
+    p->dev->prove_host(traces, n_proofs, pow_starts, inputs_out, input_stride_words, reinterpret_cast<int32_t*>(per_proof_status));
+    return P25_OK;
+  });
+}
+p25_status p25_p3_prove_batch_dev(p25_p3_prover* p, const uint64_t* d_traces, size_t trace_stride_words, size_t n_proofs,
+                                  const uint64_t* d_pow_starts, uint64_t* d_inputs, size_t input_stride_words,
+                                  uint32_t* d_status, void* stream) {
+  return host_guarded([&]() -> p25_status {
+    if (!p3_prove_args(p, d_traces, n_proofs, d_inputs, input_stride_words, d_status, trace_stride_words)) return P25_OK;
+    const p25_status s = ensure_device();
+    if (s != P25_OK) return s;
+    P25_LOCK(p);
+    p->dev->prove_dev(d_traces, trace_stride_words, n_proofs, d_pow_starts, d_inputs, input_stride_words, d_status,
+                      (hipStream_t)stream);
+    return P25_OK;
+  });
+}
+p25_status p25_p3_prover_sync(p25_p3_prover* p) {
+  return host_guarded([&]() -> p25_status {
+    if (!p) throw std::invalid_argument("null argument");
+    const p25_status s = ensure_device();
+    if (s != P25_OK) return s;
+    P25_LOCK(p);
+    p->dev->sync();
+    return P25_OK;
   });
 }
 

@@ -1,0 +1,122 @@
+// Internal: the device form of the plonky3 prover (p3_prover.cpp stage by stage) -- shapes, per-proof state and the
+// launchers of kernels_p3.hip.  Every launcher takes the proofs of one GROUP as a grid dimension: one launch per stage for
+// the whole group (p3_prover_dev.hip).
+#pragma once
+#include "kernels.h"
+#include "p3_circuit.h"
+
+namespace p25 {
+
+// ---- the AIR as a register program (compiled by P3AirDevice::compile from the AirProgram DAG) ----
+// Operands: kind << 28 | index.  LOCAL / NEXT / CONST nodes never take a slot: they are re-read where they are used.
+enum : uint32_t { P3_OPND_SLOT = 0, P3_OPND_LOCAL = 1, P3_OPND_NEXT = 2, P3_OPND_CONST = 3 };
+enum : uint32_t { P3_OP_ADD = 3, P3_OP_SUB = 4, P3_OP_MUL = 5, P3_OP_EMIT = 6 };  // ADD..MUL as AirProgram::Op
+struct P3Instr {
+  uint32_t op, dst /* slot; EMIT: the constraint's `when` */, a, b;
+};
+// The limits of the device form, refused by p25_p3_prover_create: the values of arithmetic nodes that are alive at the same
+// time (after the host's liveness pass) live in a per-lane array of this many words.
+constexpr uint32_t P3_MAX_LIVE = 64;
+constexpr uint32_t P3_MAX_INSTR = 1u << 20;
+
+struct P3AirDevice {
+  std::vector<P3Instr> instr;
+  std::vector<u64> consts;
+  uint32_t max_live = 0;
+  // throws std::invalid_argument naming the limit the program exceeds
+  static P3AirDevice compile(const AirProgram& air);
+};
+
+// ---- per-proof device state ----
+struct P3State {
+  u64 st[12], inb[12], outb[12];  // the duplex challenger (src/p3/challenger.rs:70-169)
+  uint32_t n_in, n_out;
+  u64 alpha[2], zeta[2], fri_alpha[2], final_poly[2];
+  u64 pow_witness;
+  uint32_t status, pad;
+};
+
+// Shape of one proof and the layout of a group's scratch.  All offsets in words.
+struct P3Shape {
+  uint32_t k, B, L, lqd, Q, W, num_queries, pow_bits;
+  uint32_t n_instr, tail_round;   // FRI rounds >= tail_round run in k_p3_fri_tail
+  uint32_t G;                     // proofs of this group
+  u64 w[26], w_inv[26];           // primitive 2^i-th roots of unity and their inverses
+  u64 zh[8], zh_inv[8];           // x^n - 1 on the quotient coset, by chunk
+  u64 s_inv[8];                   // 1 / s_c
+  u64 g_inv;                      // 1 / w_n
+  // hdr: the proof's first words (trace root | quotient root | trace_local | trace_next | chunks | FRI roots), then
+  // points (zeta, zeta w_n, zeta / s_c), powers of fri_alpha, betas, query indices
+  uint32_t hdr_words, o_points, o_apow, o_betas, o_idx, hdr_stride;
+  uint32_t sz_a, sz_b;            // words per query: commit-phase openings, input openings
+};
+struct P3Bufs {
+  P3State* state;
+  u64* hdr;
+  u64 *tvals, *tmp, *tcoef, *tlde, *ttree;   // [G][W][n] x3, [G][W][N2], [G][8 N2]
+  u64 *qv, *qcoef, *qlde, *qtree;            // [Q][G][2][n] x2, [Q][G][2][N2], [G][8 N2]
+  u64 *layers, *ftrees;                      // [G][4 N2], [G][8 N2]
+  const P3Instr* prog;
+  const u64* consts;
+  const u64* zfirst_inv;                     // [Q][Q]: 1 / Z_{D_j}(s_c)
+};
+
+// words of level l of a tree over h leaves (levels concatenated, 4 words per digest), FRI layer r, FRI tree r
+GL_HD size_t p3_level_off(size_t h, unsigned l) { return 8 * (h - (h >> l)); }
+GL_HD size_t p3_layer_off(size_t N2, unsigned r) { return 4 * (N2 - (N2 >> r)); }
+GL_HD size_t p3_ftree_off(size_t N2, unsigned r) { return 8 * (N2 - (N2 >> r)); }
+
+enum : uint32_t { P3_CH_TRACE = 0, P3_CH_QUOTIENT = 1, P3_CH_FRI_ALPHA = 2, P3_CH_FRI_ROUND = 3, P3_CH_QUERIES = 4 };
+
+void p3_launch_transpose(const u64* d_traces, size_t trace_stride, const P3Shape& s, const P3Bufs& b, hipStream_t st);
+// leaves of the column matrix at base + g * proof_stride + (c >> 1) * pair_stride + (c & 1) * col_stride, then the tree
+void p3_launch_commit_cols(const u64* base, size_t proof_stride, size_t pair_stride, size_t col_stride, uint32_t width,
+                           size_t h, u64* tree, size_t tree_stride, uint32_t G, hipStream_t st);
+// leaves = rows of 4 words, then the tree
+void p3_launch_commit_rows4(const u64* rows, size_t rows_stride, size_t h, u64* tree, size_t tree_stride, uint32_t G,
+                            hipStream_t st);
+void p3_launch_chain(const P3Shape& s, const P3Bufs& b, uint32_t phase, uint32_t round, hipStream_t st);
+void p3_launch_quotient(const P3Shape& s, const P3Bufs& b, hipStream_t st);
+void p3_launch_openings(const P3Shape& s, const P3Bufs& b, hipStream_t st);   // evaluations, then the identity check
+void p3_launch_reduced(const P3Shape& s, const P3Bufs& b, hipStream_t st);
+void p3_launch_fold(const P3Shape& s, const P3Bufs& b, uint32_t round, hipStream_t st);
+void p3_launch_fri_tail(const P3Shape& s, const P3Bufs& b, hipStream_t st);
+void p3_launch_pow_search(const P3Shape& s, const P3Bufs& b, const u64* d_pow_starts, hipStream_t st);
+void p3_launch_gather(const P3Shape& s, const P3Bufs& b, u64* d_out, size_t out_stride, uint32_t* d_status, hipStream_t st);
+
+// ---- the prover handle's device side (p3_prover_dev.hip) ----
+// Default scratch budget of a prover: a batch runs in groups of as many proofs as fit (at least one).
+constexpr size_t P3_SCRATCH_BUDGET_BYTES = (size_t)12 << 30;
+struct P3ProverImpl;
+class P3ProverDev {
+ public:
+  // host only: validates as p3_prove_air does and compiles the AIR; throws std::invalid_argument
+  P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int num_queries, int pow_bits);
+  ~P3ProverDev();
+  const P3Config& config() const { return cfg_; }
+  size_t num_inputs() const { return cfg_.num_inputs(); }
+  size_t trace_words() const { return ((size_t)1 << cfg_.log_trace_height) * (size_t)cfg_.trace_width; }
+  size_t scratch_words_per_proof() const;
+  size_t group_size(size_t n_proofs) const;
+  void set_scratch_budget(size_t bytes) { budget_bytes_ = bytes ? bytes : P3_SCRATCH_BUDGET_BYTES; }
+  // enqueue-only on `st`
+  void prove_dev(const u64* d_traces, size_t trace_stride, size_t n_proofs, const u64* d_pow_starts, u64* d_inputs,
+                 size_t input_stride, uint32_t* d_status, hipStream_t st);
+  // host buffers (checked by the caller): copies, proves on the handle's own stream, waits
+  void prove_host(const u64* traces, size_t n_proofs, const u64* pow_starts, u64* inputs_out, size_t input_stride,
+                  int32_t* statuses);
+  void sync();
+
+ private:
+  void ensure_impl();
+  void run_group(const u64* d_traces, size_t trace_stride, uint32_t G, const u64* d_pow_starts, u64* d_inputs,
+                 size_t input_stride, uint32_t* d_status, hipStream_t st);
+  P3Config cfg_;
+  P3AirDevice prog_;
+  P3Shape shape_;
+  std::vector<u64> zfirst_inv_;
+  size_t budget_bytes_;
+  P3ProverImpl* impl_ = nullptr;   // device state, made by the first compute call
+};
+
+}  // namespace p25

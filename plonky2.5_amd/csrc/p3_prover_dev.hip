@@ -1,0 +1,343 @@
+// Host side of the device plonky3 prover: the AIR's register program, the shape tables and the launch sequence of one
+// group of proofs, which mirrors p3_prove_air (p3_prover.cpp) stage by stage.  The kernels are in kernels_p3.hip.
+#include <algorithm>
+#include <functional>
+#include "p3_kernels.h"
+#include "prover.h"
+
+namespace p25 {
+
+// ---------------------------------------------------------------------------------------------------------------------
+// AirProgram -> register program.  Nodes are visited in the order AirProgram::fold evaluates them; a LOCAL / NEXT / CONST
+// node becomes an operand, an arithmetic node takes a slot from its evaluation to its last use.
+// ---------------------------------------------------------------------------------------------------------------------
+P3AirDevice P3AirDevice::compile(const AirProgram& air) {
+  typedef AirProgram A;
+  const size_t N = air.nodes.size();
+  P3AirDevice out;
+  auto is_leaf = [&](uint32_t i) { return air.nodes[i].op <= A::CONST; };
+  // uses of every arithmetic node by the nodes and constraints that are evaluated
+  std::vector<uint32_t> uses(N, 0);
+  std::vector<char> seen(N, 0);
+  std::function<void(uint32_t)> count = [&](uint32_t root) {
+    std::vector<uint32_t> stack{root};
+    while (!stack.empty()) {
+      const uint32_t i = stack.back();
+      stack.pop_back();
+      if (seen[i]) continue;
+      seen[i] = 1;
+      if (is_leaf(i)) continue;
+      uses[air.nodes[i].a]++;
+      uses[air.nodes[i].b]++;
+      stack.push_back(air.nodes[i].a);
+      stack.push_back(air.nodes[i].b);
+    }
+  };
+  for (const auto& c : air.constraints) {
+    uses[c.node]++;
+    count(c.node);
+  }
+  std::vector<uint32_t> const_index(N, 0), slot_of(N, 0), free_slots;
+  std::vector<char> have(N, 0);
+  uint32_t n_slots = 0, live = 0;
+  auto operand = [&](uint32_t i) -> uint32_t {
+    const A::Node& nd = air.nodes[i];
+    if (nd.op == A::LOCAL) return (P3_OPND_LOCAL << 28) | nd.a;
+    if (nd.op == A::NEXT) return (P3_OPND_NEXT << 28) | nd.a;
+    if (nd.op == A::CONST) {
+      if (!have[i]) {
+        have[i] = 1;
+        const_index[i] = (uint32_t)out.consts.size();
+        out.consts.push_back(nd.value);
+      }
+      return (P3_OPND_CONST << 28) | const_index[i];
+    }
+    return (P3_OPND_SLOT << 28) | slot_of[i];
+  };
+  auto release = [&](uint32_t i) {
+    if (is_leaf(i)) return;
+    if (--uses[i] == 0) {
+      free_slots.push_back(slot_of[i]);
+      live--;
+    }
+  };
+  for (const auto& c : air.constraints) {
+    std::vector<uint32_t> stack{c.node};
+    while (!stack.empty()) {
+      const uint32_t i = stack.back();
+      if (is_leaf(i) || have[i]) {
+        stack.pop_back();
+        continue;
+      }
+      const A::Node& nd = air.nodes[i];
+      if (!is_leaf(nd.a) && !have[nd.a]) {
+        stack.push_back(nd.a);
+        continue;
+      }
+      if (!is_leaf(nd.b) && !have[nd.b]) {
+        stack.push_back(nd.b);
+        continue;
+      }
+      P3Instr in{nd.op, 0, operand(nd.a), operand(nd.b)};
+      release(nd.a);
+      release(nd.b);
+      if (free_slots.empty()) free_slots.push_back(n_slots++);
+      in.dst = slot_of[i] = free_slots.back();
+      free_slots.pop_back();
+      live++;
+      out.max_live = std::max(out.max_live, live);
+      out.instr.push_back(in);
+      have[i] = 1;
+      stack.pop_back();
+    }
+    out.instr.push_back(P3Instr{P3_OP_EMIT, c.when, operand(c.node), 0});
+    release(c.node);
+  }
+  if (out.consts.empty()) out.consts.push_back(0);
+  if (n_slots > P3_MAX_LIVE)
+    throw std::invalid_argument("p25_p3_prover_create: the AIR keeps " + std::to_string(n_slots) +
+                                " intermediate values alive at once; the device form holds at most " + std::to_string(P3_MAX_LIVE));
+  if (out.instr.size() > P3_MAX_INSTR || out.consts.size() >= (1u << 28))
+    throw std::invalid_argument("p25_p3_prover_create: the AIR compiles to more than " + std::to_string(P3_MAX_INSTR) +
+                                " instructions, the device form's limit");
+  return out;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+struct P3ProverImpl {
+  NttTables tables;
+  DevMem prog, consts, zfirst, scratch;
+  hipStream_t own_stream = nullptr;
+  // Recorded behind the last launch of every compute call.  The next call's stream waits for it before it touches the
+  // scratch, so calls on different streams take the one scratch region in turn; each call's record sits behind its wait
+  // for the call before, so the latest record covers everything the prover has enqueued.
+  hipEvent_t done = nullptr;
+  bool recorded = false;
+  ~P3ProverImpl() {
+    if (done) (void)hipEventDestroy(done);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
+};
+
+P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int num_queries, int pow_bits) {
+  // exactly p3_prove_air's checks (p3_prover.cpp:194-230)
+  if (log_n < 1 || log_n > 22 || log_blowup < 1 || log_blowup > 4 || log_n + log_blowup > 24 || num_queries < 1 || pow_bits < 0 ||
+      pow_bits > 30)
+    throw std::invalid_argument("p3_prove: unsupported parameters");
+  air.validate();
+  const int lqd = air.log_quotient_degree();
+  if (lqd > log_blowup)
+    throw std::invalid_argument("p3_prove: the AIR's constraint degree needs more quotient chunks than log_blowup holds");
+  if (num_queries > 65535) throw std::invalid_argument("p25_p3_prover_create: more than 65535 queries (the gather's grid limit)");
+  prog_ = P3AirDevice::compile(air);
+  const int k = log_n, B = log_blowup, L = k + B, W = air.width;
+  const size_t n = (size_t)1 << k, Q = (size_t)1 << lqd;
+  cfg_ = P3Config();
+  cfg_.fri_config.log_blowup = B;
+  cfg_.fri_config.num_queries = num_queries;
+  cfg_.fri_config.proof_of_work_bits = pow_bits;
+  cfg_.log_quotient_degree = lqd;
+  cfg_.log_trace_height = k;
+  cfg_.trace_width = W;
+  cfg_.opening_matrix_log_max_height = L;
+  cfg_.opening_proof_query_openings_opened_values_length = 2;
+  cfg_.degree_bits = k;
+
+  P3Shape& s = shape_;
+  s = P3Shape{};
+  s.k = k; s.B = B; s.L = L; s.lqd = lqd; s.Q = (uint32_t)Q; s.W = W;
+  s.num_queries = num_queries; s.pow_bits = pow_bits;
+  s.n_instr = (uint32_t)prog_.instr.size();
+  // FRI layers of at most 2^P3_TAIL_LOG values fold in one workgroup per proof
+  constexpr int P3_TAIL_LOG = 10;
+  s.tail_round = L > P3_TAIL_LOG ? std::min(k, L - P3_TAIL_LOG) : 0;
+  for (int i = 0; i < 26; i++) {
+    s.w[i] = gl::root_of_unity(i);
+    s.w_inv[i] = gl::inv(s.w[i]);
+  }
+  const u64 w_q = gl::root_of_unity(k + lqd), gn = gl::pow(gl::GENERATOR, n);
+  std::vector<u64> s_c(Q);
+  for (size_t r = 0; r < Q; r++) {
+    s.zh[r] = gl::sub(gl::mul(gn, gl::pow(w_q, r * n)), 1);
+    s.zh_inv[r] = gl::inv(s.zh[r]);
+    s_c[r] = gl::mul(gl::GENERATOR, gl::pow(w_q, r));
+    s.s_inv[r] = gl::inv(s_c[r]);
+  }
+  s.g_inv = gl::inv(gl::root_of_unity(k));
+  zfirst_inv_.assign(Q * Q, 0);
+  for (size_t c = 0; c < Q; c++)
+    for (size_t j = 0; j < Q; j++)
+      if (j != c) zfirst_inv_[c * Q + j] = gl::inv(gl::sub(gl::pow(gl::mul(s_c[c], s.s_inv[j]), n), 1));
+  s.hdr_words = 8 + 4 * W + 4 * (uint32_t)Q + 4 * k;
+  s.o_points = s.hdr_words;
+  s.o_apow = s.o_points + 2 * (2 + (uint32_t)Q);
+  s.o_betas = s.o_apow + 2 * (2 * W + 2 * (uint32_t)Q);
+  s.o_idx = s.o_betas + 2 * k;
+  s.hdr_stride = s.o_idx + (num_queries + 1) / 2;
+  s.sz_a = 0;
+  for (int r = 0; r < k; r++) s.sz_a += 2 + 4 * (L - r - 1);
+  s.sz_b = W + 4 * L + 2 * (uint32_t)Q + 4 * L;
+  if ((size_t)s.hdr_words + (size_t)num_queries * (s.sz_a + s.sz_b) + 3 != cfg_.num_inputs())
+    throw std::logic_error("p3 device prover: flattened size mismatch");
+  budget_bytes_ = P3_SCRATCH_BUDGET_BYTES;
+}
+P3ProverDev::~P3ProverDev() {
+  if (impl_) {
+    try {
+      sync();
+    } catch (...) {
+    }
+    delete impl_;
+  }
+}
+
+size_t P3ProverDev::scratch_words_per_proof() const {
+  const P3Shape& s = shape_;
+  const size_t n = (size_t)1 << s.k, N2 = (size_t)1 << s.L, W = s.W, Q2 = 2 * (size_t)s.Q;
+  // run_group's carve-up: state, header; tvals, tcoef, tmp, qv, qcoef over n; tlde, qlde, two trees, layers, layer trees over N2
+  return (sizeof(P3State) + 7) / 8 + s.hdr_stride + (2 * W + std::max(W, Q2) + 2 * Q2) * n + (W + Q2 + 8 + 8 + 4 + 8) * N2;
+}
+size_t P3ProverDev::group_size(size_t n_proofs) const {
+  size_t g = budget_bytes_ / (scratch_words_per_proof() * 8);
+  g = std::max<size_t>(1, std::min<size_t>(g, 4096));
+  return std::min(g, n_proofs);
+}
+
+void P3ProverDev::sync() {
+  if (!impl_ || !impl_->recorded) return;
+  P25_HIP(hipEventSynchronize(impl_->done));
+}
+
+void P3ProverDev::ensure_impl() {
+  if (!impl_) {
+    std::unique_ptr<P3ProverImpl> im(new P3ProverImpl());
+    im->prog = DevMem((prog_.instr.size() * sizeof(P3Instr) + 7) / 8);
+    im->consts = DevMem(prog_.consts.size());
+    im->zfirst = DevMem(zfirst_inv_.size());
+    P25_HIP(hipMemcpy(im->prog.p, prog_.instr.data(), prog_.instr.size() * sizeof(P3Instr), hipMemcpyHostToDevice));
+    P25_HIP(hipMemcpy(im->consts.p, prog_.consts.data(), prog_.consts.size() * 8, hipMemcpyHostToDevice));
+    P25_HIP(hipMemcpy(im->zfirst.p, zfirst_inv_.data(), zfirst_inv_.size() * 8, hipMemcpyHostToDevice));
+    P25_HIP(hipEventCreateWithFlags(&im->done, hipEventDisableTiming));
+    impl_ = im.release();
+  }
+}
+
+void P3ProverDev::prove_dev(const u64* d_traces, size_t trace_stride, size_t n_proofs, const u64* d_pow_starts, u64* d_inputs,
+                            size_t input_stride, uint32_t* d_status, hipStream_t st) {
+  if (!n_proofs) return;
+  ensure_impl();
+  const size_t G = group_size(n_proofs), need = G * scratch_words_per_proof();
+  if (impl_->scratch.words < need) {   // as verify_scratch_ (verify.hip): 0 words after a failed growth, so the next call allocates
+    sync();   // an earlier call may still be using the old allocation
+    impl_->scratch = DevMem();
+    impl_->scratch = DevMem(need);
+  }
+  // the scratch is one region: wait, on the device, for the call before, whichever stream it went to; and leave the
+  // record for the next call behind whatever this one managed to enqueue, also when it throws half way
+  if (impl_->recorded) P25_HIP(hipStreamWaitEvent(st, impl_->done, 0));
+  struct Record {
+    P3ProverImpl* im;
+    hipStream_t st;
+    ~Record() {
+      if (hipEventRecord(im->done, st) == hipSuccess) im->recorded = true;
+    }
+  } record{impl_, st};
+  for (size_t g0 = 0; g0 < n_proofs; g0 += G) {
+    const size_t cnt = std::min(G, n_proofs - g0);
+    run_group(d_traces + g0 * trace_stride, trace_stride, (uint32_t)cnt, d_pow_starts ? d_pow_starts + g0 : nullptr,
+              d_inputs + g0 * input_stride, input_stride, d_status + g0, st);
+  }
+  P25_HIP(hipGetLastError());
+}
+
+void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, uint32_t G, const u64* d_pow_starts, u64* d_inputs,
+                            size_t input_stride, uint32_t* d_status, hipStream_t st) {
+  P3Shape s = shape_;
+  s.G = G;
+  const int k = s.k, B = s.B;
+  const size_t n = (size_t)1 << k, N2 = (size_t)1 << s.L, W = s.W, Q = s.Q, Q2 = 2 * Q;
+  NttTables& tb = impl_->tables;
+  // scratch of the group
+  P3Bufs b{};
+  u64* p = impl_->scratch.p;
+  auto take = [&](size_t words) {
+    u64* r = p;
+    p += words;
+    return r;
+  };
+  b.state = reinterpret_cast<P3State*>(take(G * ((sizeof(P3State) + 7) / 8)));
+  static_assert(sizeof(P3State) % 8 == 0, "P3State is an array of words");
+  b.hdr = take(G * s.hdr_stride);
+  b.tvals = take(G * W * n);
+  b.tmp = take(G * std::max(W, Q2) * n);
+  b.tcoef = take(G * W * n);
+  b.qv = take(G * Q2 * n);
+  b.qcoef = take(G * Q2 * n);
+  b.tlde = take(G * W * N2);
+  b.qlde = take(G * Q2 * N2);
+  b.ttree = take(G * 8 * N2);
+  b.qtree = take(G * 8 * N2);
+  b.layers = take(G * 4 * N2);
+  b.ftrees = take(G * 8 * N2);
+  b.prog = reinterpret_cast<const P3Instr*>(impl_->prog.p);
+  b.consts = impl_->consts.p;
+  b.zfirst_inv = impl_->zfirst.p;
+
+  // the LDE on shift * <w_{n 2^B}> in bit-reversed order; 16 cosets as two interleaved sets of 8 (coset 2 c + e of the
+  // first kind is coset c of the set with shift * w^e, and lands in half e of the bit-reversed output)
+  auto lde = [&](const u64* coeffs, u64* out, int n_polys, u64 shift) {
+    if (B <= 3) {
+      ntt_lde_bitrev(tb, coeffs, n, out, N2, k, B, n_polys, shift, st);
+    } else {
+      ntt_lde_bitrev(tb, coeffs, n, out, N2, k, 3, n_polys, shift, st);
+      ntt_lde_bitrev(tb, coeffs, n, out + N2 / 2, N2, k, 3, n_polys, gl::mul(shift, gl::root_of_unity(s.L)), st);
+    }
+  };
+
+  // trace: columns -> coefficients (kept for the openings) -> LDE on 7 H_{n 2^B} -> tree   (p3_prover.cpp:208-218)
+  p3_launch_transpose(d_traces, trace_stride, s, b, st);
+  ntt_inverse(tb, b.tvals, n, false, b.tmp, n, b.tcoef, n, k, (int)(G * W), 1, st);
+  lde(b.tcoef, b.tlde, (int)(G * W), gl::GENERATOR);
+  p3_launch_commit_cols(b.tlde, W * N2, 2 * N2, N2, (uint32_t)W, N2, b.ttree, 8 * N2, G, st);
+  p3_launch_chain(s, b, P3_CH_TRACE, 0, st);                       // observe the root, sample alpha
+  // quotient on 7 H_{n 2^lqd}, split into chunks; chunk c: iNTT on H_n, LDE with shift 7 / s_c   (:231-290)
+  p3_launch_quotient(s, b, st);
+  ntt_inverse(tb, b.qv, n, true, b.tmp, n, b.qcoef, n, k, (int)(G * Q2), 1, st);
+  for (size_t c = 0; c < Q; c++)
+    lde(b.qcoef + c * G * 2 * n, b.qlde + c * G * 2 * N2, (int)(2 * G), gl::mul(gl::GENERATOR, s.s_inv[c]));
+  p3_launch_commit_cols(b.qlde, 2 * N2, (size_t)G * 2 * N2, N2, (uint32_t)Q2, N2, b.qtree, 8 * N2, G, st);
+  p3_launch_chain(s, b, P3_CH_QUOTIENT, 0, st);                    // observe the root, sample zeta
+  p3_launch_openings(s, b, st);                                    // :296-329
+  p3_launch_chain(s, b, P3_CH_FRI_ALPHA, 0, st);
+  p3_launch_reduced(s, b, st);                                     // :331-355
+  for (uint32_t r = 0; r < s.tail_round; r++) {                    // :359-387
+    p3_launch_commit_rows4(b.layers + p3_layer_off(N2, r), 4 * N2, N2 >> (r + 1), b.ftrees + p3_ftree_off(N2, r), 8 * N2, G, st);
+    p3_launch_chain(s, b, P3_CH_FRI_ROUND, r, st);
+    p3_launch_fold(s, b, r, st);
+  }
+  p3_launch_fri_tail(s, b, st);
+  p3_launch_pow_search(s, b, d_pow_starts, st);                    // :394-400
+  p3_launch_chain(s, b, P3_CH_QUERIES, 0, st);                     // :401-404
+  p3_launch_gather(s, b, d_inputs, input_stride, d_status, st);    // :423-445
+}
+
+void P3ProverDev::prove_host(const u64* traces, size_t n_proofs, const u64* pow_starts, u64* inputs_out, size_t input_stride,
+                             int32_t* statuses) {
+  if (!n_proofs) return;
+  const size_t tw = trace_words(), ni = num_inputs();
+  ensure_impl();
+  if (!impl_->own_stream) P25_HIP(hipStreamCreateWithFlags(&impl_->own_stream, hipStreamNonBlocking));
+  hipStream_t st = impl_->own_stream;
+  DevMem d_traces(n_proofs * tw), d_pow(n_proofs), d_out(n_proofs * ni), d_status((n_proofs + 1) / 2);
+  P25_HIP(hipMemcpyAsync(d_traces.p, traces, n_proofs * tw * 8, hipMemcpyHostToDevice, st));
+  if (pow_starts) P25_HIP(hipMemcpyAsync(d_pow.p, pow_starts, n_proofs * 8, hipMemcpyHostToDevice, st));
+  prove_dev(d_traces.p, tw, n_proofs, pow_starts ? d_pow.p : nullptr, d_out.p, ni, reinterpret_cast<uint32_t*>(d_status.p), st);
+  // the input_stride - num_inputs words behind a proof stay untouched
+  P25_HIP(hipMemcpy2DAsync(inputs_out, input_stride * 8, d_out.p, ni * 8, ni * 8, n_proofs, hipMemcpyDeviceToHost, st));
+  std::vector<uint32_t> hs(n_proofs);
+  P25_HIP(hipMemcpyAsync(hs.data(), d_status.p, n_proofs * 4, hipMemcpyDeviceToHost, st));
+  P25_HIP(hipStreamSynchronize(st));
+  for (size_t i = 0; i < n_proofs; i++) statuses[i] = (int32_t)hs[i];
+}
+
+}  // namespace p25

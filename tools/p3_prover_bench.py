@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""Device plonky3 prover against the host prover, per proof, on the same box.
+
+Fibonacci AIR, 100 queries, 16 proof-of-work bits, log_n in {12, 16, 20} (--log-n to choose), batches of 1 and 16 with
+distinct pow_starts.  For each shape:
+  * device: P3Prover.prove_dev on device-resident traces, one warm-up call (tables, scratch, code objects), then the timed
+    calls; the time is a host clock around enqueue + P3Prover.sync(), i.e. it ends in a device synchronise;
+  * host: p3_prove_fibonacci(threads=16), the unchanged yardstick, once per distinct pow_start that is compared;
+  * the device rows are asserted equal to the host's, word for word.
+Writes one JSON (default profiles/p3_prover_bench.json) and prints it as one line; exits non-zero if the device form is not
+faster per proof than the host form at the largest log_n of the run.  There is no CPU path: without a GPU the
+first compute call raises.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as entry  # noqa: E402
+
+P = 0xFFFFFFFF00000001
+
+
+def fib_trace(log_n):
+    n = 1 << log_n
+    t = np.zeros((n, 3), dtype=np.uint64)
+    a, b = 1, 1
+    for i in range(n):
+        c = a + b
+        if c >= P:
+            c -= P
+        t[i] = (a, b, c)
+        a, b = b, c
+    return t
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log-n", type=int, nargs="+", default=[12, 16, 20])
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 16])
+    ap.add_argument("--queries", type=int, default=100)
+    ap.add_argument("--pow-bits", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=3, help="timed device calls per shape (the median is reported)")
+    ap.add_argument("--host-proofs", type=int, default=2, help="distinct host proofs timed and compared per log_n")
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "p3_prover_bench.json"))
+    args = ap.parse_args()
+
+    import torch
+    p25 = entry.load_package()
+    p25.device_init(0)
+    dev = torch.device("cuda", 0)
+    air = p25.Air.fibonacci()
+    result = {"tool": "tools/p3_prover_bench.py", "air": "fibonacci", "queries": args.queries, "pow_bits": args.pow_bits,
+              "host_threads": args.threads, "device": torch.cuda.get_device_name(0), "shapes": []}
+    for log_n in args.log_n:
+        trace = fib_trace(log_n)
+        pr = p25.P3Prover(air, log_n, 1, args.queries, args.pow_bits)
+        ni = pr.num_inputs
+        max_b = max(args.batches)
+        starts = np.array([(i * 0x9E3779B97F4A7C15) % (P - (1 << 40)) for i in range(max_b)], dtype=np.uint64)
+        starts[0] = 0
+        # host yardstick: time and keep the first few distinct proofs
+        host_rows, host_s = {}, []
+        for i in range(min(args.host_proofs, max_b)):
+            t0 = time.perf_counter()
+            row, _cfg = p25.p3_prove_fibonacci(log_n, args.queries, args.pow_bits, pow_start=int(starts[i]), threads=args.threads)
+            host_s.append(time.perf_counter() - t0)
+            host_rows[i] = row
+        host_per_proof = float(np.median(host_s))
+        d_trace = torch.from_numpy(trace.view(np.int64).copy()).to(dev)
+        for b in args.batches:
+            # the batch proves the SAME trace b times from b pow_starts: distinct proofs, one device copy of the trace each
+            d_traces = d_trace.reshape(1, -1).repeat(b, 1).contiguous()
+            d_starts = torch.from_numpy(starts[:b].view(np.int64).copy()).to(dev)
+            d_inputs = torch.zeros((b, ni), dtype=torch.int64, device=dev)
+            d_status = torch.zeros(b, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+
+            def call():
+                pr.prove_dev(d_traces.data_ptr(), trace.size, b, d_starts.data_ptr(), d_inputs.data_ptr(), ni,
+                             d_status.data_ptr())
+                pr.sync()
+
+            call()   # warm-up
+            times = []
+            for _ in range(args.reps):
+                d_inputs.zero_()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                call()
+                times.append(time.perf_counter() - t0)
+            got = d_inputs.cpu().numpy().view(np.uint64)
+            assert d_status.cpu().numpy().tolist() == [0] * b, "device prover reported a failure"
+            for i, row in host_rows.items():
+                if i < b:
+                    assert np.array_equal(got[i], row), f"log_n {log_n}, batch {b}: proof {i} differs from the host prover's"
+            per_proof = float(np.median(times)) / b
+            result["shapes"].append({"log_n": log_n, "batch": b, "num_inputs": ni, "gpu_call_s": [round(t, 6) for t in times],
+                                     "gpu_s_per_proof": per_proof, "host_s_per_proof": host_per_proof,
+                                     "host_s": [round(t, 6) for t in host_s], "host_over_gpu": host_per_proof / per_proof,
+                                     "rows_compared_equal": min(len(host_rows), b)})
+            del d_traces, d_inputs
+        pr.close()
+    # the acceptance for speed: per proof, the device form beats the host form of the same run at the largest size
+    top = max(args.log_n)
+    result["acceptance"] = {"log_n": top, "gpu_faster_than_host": all(sh["host_over_gpu"] > 1.0 for sh in result["shapes"]
+                                                                      if sh["log_n"] == top)}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+    if not result["acceptance"]["gpu_faster_than_host"]:
+        sys.exit(f"the device prover is not faster per proof than the host prover at log_n {top}")
+
+
+if __name__ == "__main__":
+    main()

@@ -71,8 +71,11 @@ __global__ __launch_bounds__(64, 6) void k_hash_leaves_wide(const u64* __restric
 // still rises from 6 to 8 resident waves (profiles/r06_instr_rates.txt: 4.35-4.42 -> 4.28-4.32 cycles per instruction); in the
 // pipeline 145.7 against 145.3 proofs/s in every round of three (profiles/r06_ab_hash_occupancy_7_8.txt).  The leaf sponges stay
 // at 6 (79 VGPRs: 7 waves = 71 VGPRs and 8 = 63 VGPRs + 28 B of scratch measure the same as 6 there).
+// PRIO: the wave priority, chosen per launch by launch_level (LEVEL_PRIO_BATCH below).
+template <int PRIO>
 __global__ __launch_bounds__(64, 8) void k_tree_level(const u64* __restrict__ children,
                                                     u64* __restrict__ parents, size_t n_parents) {
+  if constexpr (PRIO != 0) P25_WAVE_PRIO(PRIO);
   size_t m = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (m >= n_parents) return;
   u64 l[4], r[4], o[4];
@@ -153,13 +156,30 @@ __global__ __launch_bounds__(256) void k_tree_top_coop(u64* __restrict__ nodes, 
 // A lone proof prefers 32768: at that size the per-lane form leaves most SIMDs with one wave or none, and the level
 // takes a full permutation latency.
 constexpr size_t COOP_PARENTS_BATCH = 2048, COOP_PARENTS_SINGLE = 32768;
+// Wave priority of the per-lane levels when many proofs are in flight.  A level is a job of 100 us or less that shares
+// its SIMDs with the leaf sponges of the other queues, whose waves run for a millisecond each; at priority 0 its waves
+// get one issue slot in six or seven beside them (mean 316 us in the pipeline against 58 us alone), and on an in-order
+// queue the three other proofs of that queue wait as long.  Above the sponges' priority the level finishes first:
+// shortest job first.  Measured at four queues (tools/ab_bench.py, profiles/r08_tree_level_priority.txt): priority 0
+// 121.2-121.9 proofs/s, 1 for levels of up to 65536 parents only (at most a wave per SIMD) 124.6-125.7, 1 for every level
+// 128.8-129.4; on another box 0 123.7-124.0 and 1 / 2 / 3 for every level 130.3-130.5 / 130.3-130.6 / 129.9-130.1: the
+// lowest priority above the sponges' is kept.  (Round 3 saw "nothing" from this at 24 queues, where a slow thin launch
+// delayed nobody.)
+// A lone proof has no sponge of another proof beside its levels and keeps priority 0.
+// Measured and not adopted on top of this (same file; tools/exp/tree_tail.patch): the levels from 2^15 nodes down in ONE
+// launch (k_tree_tail: a 256-lane block reduces 512 nodes to one, levels staying in LDS) -- 6 launches per big tree
+// instead of 11 -- 129.5-129.8 proofs/s with priority 1 for the remaining levels, 124.8-125.3 with priority 0.
+constexpr int LEVEL_PRIO_BATCH = 1;
 
 static void launch_level(const u64* cur, u64* nxt, size_t m, hipStream_t st, bool single_proof) {
+  const dim3 grid((unsigned)((m + 63) / 64));
   if (m <= (single_proof ? COOP_PARENTS_SINGLE : COOP_PARENTS_BATCH)) {
     size_t th = m * coop::GROUP;
     hipLaunchKernelGGL(k_tree_level_coop, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, st, cur, nxt, m);
+  } else if (single_proof) {
+    hipLaunchKernelGGL(k_tree_level<0>, grid, dim3(64), 0, st, cur, nxt, m);
   } else {
-    hipLaunchKernelGGL(k_tree_level, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, st, cur, nxt, m);
+    hipLaunchKernelGGL(k_tree_level<LEVEL_PRIO_BATCH>, grid, dim3(64), 0, st, cur, nxt, m);
   }
 }
 // Levels from `cur` (m nodes) up to the cap: one launch per level while a cap entry has more than TOP_MAX_NODES

@@ -611,13 +611,13 @@ void build_tree(u64* tree, size_t tree_stride, size_t h, uint32_t G, hipStream_t
   unsigned l = 0;
   for (; l < log_h; l++) {
     const size_t nodes = h >> (l + 1);
-    if (nodes * G <= ((size_t)1 << 16)) break;
+    if (nodes * G <= (size_t)P3_TREE_COOP_MAX) break;
     hipLaunchKernelGGL(k_p3_tree_level, dim3((unsigned)((nodes + 255) / 256), G), dim3(256), 0, st, tree + p3_level_off(h, l),
                        tree + p3_level_off(h, l + 1), nodes, tree_stride);
   }
   for (; l < log_h; l++) {
     const size_t nodes = h >> (l + 1);
-    if (nodes <= 16) break;
+    if (nodes <= (size_t)P3_TREE_TOP_NODES) break;
     hipLaunchKernelGGL(k_p3_tree_coop, dim3((unsigned)((nodes + 15) / 16), G), dim3(256), 0, st, tree, tree_stride, h, l, 1u);
   }
   if (l < log_h) hipLaunchKernelGGL(k_p3_tree_coop, dim3(1, G), dim3(256), 0, st, tree, tree_stride, h, l, log_h - l);

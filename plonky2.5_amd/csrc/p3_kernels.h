@@ -18,6 +18,13 @@ struct P3Instr {
 // time (after the host's liveness pass) live in a per-lane array of this many words.
 constexpr uint32_t P3_MAX_LIVE = 64;
 constexpr uint32_t P3_MAX_INSTR = 1u << 20;
+// The launch forms of a Merkle tree (build_tree, kernels_p3.hip): a level with more than P3_TREE_COOP_MAX nodes over the
+// whole group runs one lane per node, a smaller one 16 lanes per node; once a proof's level has at most P3_TREE_TOP_NODES
+// nodes, one workgroup per proof finishes the tree.  FRI layers of at most 2^P3_TAIL_LOG values fold in one workgroup per
+// proof (k_p3_fri_tail).  The tests read these three from this file and derive their shapes from them.
+constexpr int P3_TREE_COOP_MAX = 1 << 16;
+constexpr int P3_TREE_TOP_NODES = 16;
+constexpr int P3_TAIL_LOG = 10;
 
 struct P3AirDevice {
   std::vector<P3Instr> instr;

@@ -149,7 +149,6 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
   s.num_queries = num_queries; s.pow_bits = pow_bits;
   s.n_instr = (uint32_t)prog_.instr.size();
   // FRI layers of at most 2^P3_TAIL_LOG values fold in one workgroup per proof
-  constexpr int P3_TAIL_LOG = 10;
   s.tail_round = L > P3_TAIL_LOG ? std::min(k, L - P3_TAIL_LOG) : 0;
   for (int i = 0; i < 26; i++) {
     s.w[i] = gl::root_of_unity(i);

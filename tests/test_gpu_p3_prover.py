@@ -153,16 +153,18 @@ def test_batch_with_pow_starts(gpu, squares5):
 
 def test_grouping_changes_no_word(gpu, squares5):
     """40 proofs under a scratch budget that holds about 8 of them (and under one that holds a single proof): group
-    boundaries fall inside the batch, every row is the one the five-proof call gave."""
+    boundaries fall inside the batch, every row is the one the five-proof call gave.  Then 41: a group of eight does not
+    divide it, the last group is short."""
     air, traces, want = squares5
-    pick = np.arange(40) % 5
-    for budget in (200_000, 1):
-        pr = gpu.P3Prover(air, 5, 1, 6, 10)
-        pr.set_scratch_budget(budget)
-        got, st = pr.prove(traces[pick], pow_starts=np.array(POW_STARTS, dtype=np.uint64)[pick])
-        assert st.tolist() == [OK] * 40
-        assert np.array_equal(got, want[pick])
-        pr.close()
+    for n in (40, 41):
+        pick = np.arange(n) % 5
+        for budget in (200_000, 1):
+            pr = gpu.P3Prover(air, 5, 1, 6, 10)
+            pr.set_scratch_budget(budget)
+            got, st = pr.prove(traces[pick], pow_starts=np.array(POW_STARTS, dtype=np.uint64)[pick])
+            assert st.tolist() == [OK] * n
+            assert np.array_equal(got, want[pick])
+            pr.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

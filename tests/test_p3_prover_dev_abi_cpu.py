@@ -5,12 +5,14 @@ The handle is host-only until its first compute call: creating it, asking its sh
 a GPU; the compute entry points then answer P25_ERR_NO_DEVICE.  What `create` accepts and refuses is what the host prover
 p25_p3_prove_air_ex accepts and refuses for the same arguments."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import pytest
 
 import air_cases
-from conftest import P
+from conftest import P, ROOT
 
 OK, INVALID_ARG, NO_DEVICE = 0, 1, 2
 
@@ -117,6 +119,107 @@ def test_create_names_the_live_value_limit(p25):
     air.when_first_row(air.sub(total, air.local(1)))
     assert _create(p25, air, 3, 1, 3, 4) == INVALID_ARG
     assert "alive" in _last(p25) and "64" in _last(p25)
+
+
+def _prove_or_status(p25, air, trace, log_blowup):
+    """The host prover's (words, OK) or (None, status) for a trace, with the arguments of the generated-AIR cases."""
+    try:
+        return p25.p3_prove_air(air, trace, num_queries=air_cases.DAG_QUERIES, pow_bits=air_cases.DAG_POW_BITS,
+                                log_blowup=log_blowup)[0], OK
+    except p25.P25Error as e:
+        return None, e.status
+
+
+def test_live_chain_boundary(p25):
+    """air_cases.live_chain(m) keeps v0 .. v_m alive until the sum starts, and the sum's first node takes the slot that
+    v0 or v_m gave back: m + 1 slots.  So the largest accepted m is P3_MAX_LIVE - 1, the accepted program uses every slot
+    index, and one more value is refused by name.  The figure is measured, not written down: a change of the allocator
+    that moves it fails here and has to state the new relation."""
+    hdr = open(os.path.join(ROOT, "plonky2.5_amd", "csrc", "p3_kernels.h")).read()
+    max_live = int(re.search(r"constexpr\s+uint32_t\s+P3_MAX_LIVE\s*=\s*(\d+)\s*;", hdr).group(1))
+    accepted = [m for m in range(1, 2 * max_live) if _create(p25, air_cases.live_chain(p25, m), 3, 1, 3, 4) == OK]
+    assert accepted and accepted == list(range(1, accepted[-1] + 1))      # one boundary, nothing accepted beyond it
+    m = accepted[-1]
+    assert m == max_live - 1
+    assert _create(p25, air_cases.live_chain(p25, m + 1), 3, 1, 3, 4) == INVALID_ARG
+    assert "alive" in _last(p25) and f"keeps {max_live + 1} " in _last(p25) and f"at most {max_live}" in _last(p25)
+    # the chains on both sides of the boundary are valid inputs: the host prover, which has no such limit, proves them
+    for mm in (m, m + 1):
+        assert _prove_or_status(p25, air_cases.live_chain(p25, mm), air_cases.live_chain_trace(mm, 3), 1)[1] == OK
+
+
+def test_slots_go_back_on_last_use(p25):
+    """air_cases.slot_churn has far more arithmetic nodes than P3_MAX_LIVE and a handful alive at a time; more than
+    P3_MAX_LIVE of them end their life as a left operand, as a right operand and as a constraint's root.  A compile that
+    forgets to give back any of the three runs out of slots and refuses it; the live chain cannot see that, since a slot
+    leaked there is a slot the chain no longer needs."""
+    air, y = air_cases.slot_churn(p25)
+    arith = [nd for nd in air.nodes if nd[0] >= 3]
+    is_arith = lambda i: air.nodes[i][0] >= 3
+    assert sum(is_arith(nd[1]) for nd in arith) > 2 * 64 and sum(is_arith(nd[2]) for nd in arith) > 2 * 64
+    assert sum(is_arith(c) for c, _w in air.constraints) > 64
+    assert _create(p25, air, 3, 1, 3, 4) == OK, _last(p25)
+    assert _prove_or_status(p25, air, air_cases.slot_churn_trace(air, y, 3), 1)[1] == OK
+
+
+def test_random_dag_cases_are_valid_and_mix_verdicts(p25):
+    """The 48 generated cases of tests/test_gpu_p3_prover_forms.py, on the host alone: every one is created (so none
+    passes P3_MAX_LIVE), the host prover accepts its trace, and the trace with DAG_BAD_CELL incremented is refused in at
+    least 12 cases and accepted in at least 6 (the cell is free where its constraint is not enforced)."""
+    refused = accepted = 0
+    for max_degree, log_blowup in air_cases.DAG_CLASSES:
+        for seed in air_cases.DAG_SEEDS:
+            air, trace = air_cases.dag_case(p25, seed, max_degree)
+            assert trace.shape == (1 << air_cases.DAG_LOG_N, 16) and (trace < P).all()
+            assert len(air.constraints) == 10 and len(air.nodes) > 160
+            assert _create(p25, air, air_cases.DAG_LOG_N, log_blowup, air_cases.DAG_QUERIES, air_cases.DAG_POW_BITS) == OK, \
+                (seed, max_degree, _last(p25))
+            assert _prove_or_status(p25, air, trace, log_blowup)[1] == OK, (seed, max_degree)
+            st = _prove_or_status(p25, air, air_cases.bump(trace, *air_cases.DAG_BAD_CELL), log_blowup)[1]
+            assert st in (OK, INVALID_ARG)
+            refused += st == INVALID_ARG
+            accepted += st == OK
+    assert refused >= 12 and accepted >= 6, (refused, accepted)
+
+
+def test_random_dag_shares_what_it_claims(p25):
+    """The properties the generated DAGs are there for, counted over the 48 cases: a node read by several later nodes, a
+    root shared by two constraints, a root that a later node reads again, the same operand twice in one node."""
+    multi_use = shared_root = root_read_later = twice = 0
+    for max_degree, _b in air_cases.DAG_CLASSES:
+        for seed in air_cases.DAG_SEEDS:
+            air, _t = air_cases.dag_case(p25, seed, max_degree)
+            roots = [air.nodes[c][1] for c, _w in air.constraints]          # constraint = sub(root, local): operand a
+            arith = {i for i, nd in enumerate(air.nodes) if nd[0] >= 3}
+            reads = [x for i in arith for x in air.nodes[i][1:3] if x in arith]
+            multi_use += any(reads.count(x) >= 3 for x in set(reads))
+            shared_root += len(set(roots)) < len(roots)
+            root_read_later += any(sum(1 for i in arith if i > r and r in air.nodes[i][1:3]) >= 2 for r in roots)
+            twice += any(air.nodes[i][1] == air.nodes[i][2] and air.nodes[i][1] in arith for i in arith)
+    assert min(multi_use, root_read_later, twice) >= 24 and shared_root >= 12, (multi_use, shared_root, root_read_later, twice)
+
+
+def test_constant_and_single_cell_inputs(p25):
+    """Inputs of the verdict tests of the GPU module, on the host alone: both constant traces are accepted and the first
+    gives a proof full of zeros; of the 24 single-cell increments of an 8-row `squares` trace the host accepts exactly the
+    free ones: y on the rows before the last."""
+    for y0 in (0, 1):
+        words = p25.p3_prove_air(air_cases.constant_pair(p25, y0), air_cases.constant_pair_trace(y0, 5), num_queries=3,
+                                 pow_bits=4)[0]
+        if y0 == 0:
+            # zero by construction: the quotient's opening at zeta (2 words) and its value at every query (3 x 2), the
+            # sibling value of 5 FRI rounds per query (3 x 5 x 2), the final polynomial (2)
+            assert np.count_nonzero(words == 0) >= 2 + 6 + 30 + 2
+    air, trace = air_cases.squares(p25), air_cases.squares_trace(3)
+    ok_cells = []
+    for r in range(8):
+        for c in range(3):
+            try:
+                p25.p3_prove_air(air, air_cases.bump(trace, r, c), num_queries=3, pow_bits=4)
+                ok_cells.append((r, c))
+            except p25.P25Error as e:
+                assert e.status == INVALID_ARG
+    assert ok_cells == [(r, 2) for r in range(7)]
 
 
 SHAPES = [("fib", 3, 1, 3, 4), ("fib", 6, 1, 100, 16), ("trib", 4, 1, 5, 0), ("cubic", 5, 1, 7, 3), ("quintic", 4, 2, 9, 5),

@@ -10,13 +10,15 @@
 #include <tuple>
 #include "gl.h"
 
-// Wave priority (s_setprio, 0..3) in the SIMDs' issue arbitration.  The bulk hash kernels (k_hash_leaves*, k_pow_search,
-// k_tree_level of a lone proof: 68 % of all VALU work, always enough of it resident to fill every issue slot) stay at 0;
+// Wave priority (s_setprio, 0..3) in the SIMDs' issue arbitration.  The bulk hash kernels (k_hash_leaves*, and k_pow_search,
+// k_tree_level, k_fri_leaf_hash of a lone proof: 68 % of all VALU work, always enough of it resident to fill every issue slot) stay at 0;
 // the kernels whose waves spend their lives waiting for memory, LDS or barriers (NTT, quotient, partial products, openings,
 // FRI) run at 2 and the single-wave chains (transcript, cooperative Merkle tops, witness levels) at 3, so that when they
 // CAN issue they do, finish, and give their registers and LDS back.  Measured: profiles/r03_pipeline_model_experiments.txt
-// item 16.  With many proofs in flight k_tree_level runs at 1 (kernels_hash.hip, LEVEL_PRIO_BATCH): a level is a short job
-// beside the other queues' millisecond sponge waves, and its in-order queue waits for it.
+// item 16.  With many proofs in flight k_tree_level runs at 1 (kernels_hash.hip, LEVEL_PRIO_BATCH), and so do the per-lane
+// k_fri_leaf_hash (kernels_fri.hip, FRI_LEAF_PRIO_BATCH) and k_pow_search (kernels_transcript.hip, POW_PRIO_BATCH): each is a
+// short job beside the other queues' millisecond sponge waves, and its in-order queue waits for it.  The leaf sponges themselves
+// stay at 0 there too, the 20- and 16-column ones included (1 for those measured level with 0, profiles/r09_fri_pow_queue_time.txt).
 #if defined(__HIP_DEVICE_COMPILE__)
 #define P25_WAVE_PRIO(n) __builtin_amdgcn_s_setprio(n)
 #else

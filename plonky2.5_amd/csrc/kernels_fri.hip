@@ -337,9 +337,12 @@ void launch_fri_fold(const u64* ca, const u64* cb, uint32_t len_out, uint32_t ar
   hipLaunchKernelGGL(k_fri_fold, dim3((len_out + 255) / 256), dim3(256), 0, st, ca, cb, len_out, arity_bits, d_beta, oa, ob);
 }
 
+// PRIO: the wave priority, chosen per launch by launch_fri_leaf_hash (as k_tree_level<PRIO>, kernels_hash.hip).
+template <int PRIO>
 __global__ __launch_bounds__(256) void k_fri_leaf_hash(const u64* __restrict__ va, const u64* __restrict__ vb,
                                                        uint32_t n_leaves, uint32_t arity_bits,
                                                        u64* __restrict__ digests) {
+  if constexpr (PRIO != 0) P25_WAVE_PRIO(PRIO);
   uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
   if (l >= n_leaves) return;
   const uint32_t arity = 1u << arity_bits, words = 2 * arity;
@@ -364,7 +367,8 @@ __global__ __launch_bounds__(256) void k_fri_leaf_hash(const u64* __restrict__ v
 }
 // Same digests, one 16-lane group per leaf (coop.h).  A FRI layer has few leaves (2^15, 2^11, 2^7 for the
 // fib-64 circuit) and each needs 4 chained permutations, so the per-lane kernel is pure latency (~250 us per
-// layer whatever its size); cooperatively the chain is ~4 x 12 us.  Used when a single proof is in flight.
+// layer whatever its size); cooperatively the chain is ~4 x 12 us.  Used when a single proof is in flight, and for the
+// small layers of a batch (launch_fri_leaf_hash).
 __global__ __launch_bounds__(256) void k_fri_leaf_hash_coop(const u64* __restrict__ va, const u64* __restrict__ vb,
                                                             uint32_t n_leaves, uint32_t arity_bits,
                                                             u64* __restrict__ digests) {
@@ -385,11 +389,28 @@ __global__ __launch_bounds__(256) void k_fri_leaf_hash_coop(const u64* __restric
   }
   if (valid && rr < 4) digests[4 * g + rr] = s;
 }
+// Which form hashes a layer.  A lone proof: the cooperative form for every layer (latency).  Many proofs in flight: the
+// cooperative form for layers of at most COOP_FRI_LEAVES_BATCH leaves, the per-lane form at LEVEL_PRIO_BATCH's priority
+// (kernels_hash.hip) in 64-lane workgroups for larger ones.  The reasoning is the one of COOP_PARENTS_BATCH and
+// LEVEL_PRIO_BATCH there: sixteen proving streams share a few in-order hardware queues, and a launch of a few dozen
+// waves that runs four chained per-lane permutations at priority 0 beside the other queues' millisecond sponge waves
+// holds its queue -- and the three other proofs behind it -- for about half a millisecond (477 us mean in the pipeline,
+// profiles/r07_fused_chain.txt section 4b, against ~250 us alone and ~50 us cooperatively).  The cooperative form costs
+// four times the instructions of the per-lane one, which rules it out at 2^15 leaves and is nothing at 2^11 + 2^7
+// (1.8 M wave-instructions, 0.05 % of a proof).  Measured: profiles/r09_fri_pow_queue_time.txt.
+// Leaves of at most four words are not hashed (hash_or_noop) and take the per-lane kernel in either case.
+constexpr uint32_t COOP_FRI_LEAVES_BATCH = 2048;
+constexpr int FRI_LEAF_PRIO_BATCH = 1;  // = LEVEL_PRIO_BATCH: the lowest priority above the leaf sponges' 0
 void launch_fri_leaf_hash(const u64* va, const u64* vb, uint32_t n_leaves, uint32_t arity_bits, u64* d_digests,
                           hipStream_t st, bool single_proof) {
-  // cooperative form only when a lone proof is in flight: it costs 4x the instructions of the per-lane form
-  if ((2u << arity_bits) <= 4 || !single_proof) {
-    hipLaunchKernelGGL(k_fri_leaf_hash, dim3((n_leaves + 255) / 256), dim3(256), 0, st, va, vb, n_leaves, arity_bits, d_digests);
+  const bool noop = (2u << arity_bits) <= 4;
+  if (single_proof ? noop : (noop || n_leaves > COOP_FRI_LEAVES_BATCH)) {
+    if (single_proof)
+      hipLaunchKernelGGL(k_fri_leaf_hash<0>, dim3((n_leaves + 255) / 256), dim3(256), 0, st, va, vb, n_leaves, arity_bits,
+                         d_digests);
+    else
+      hipLaunchKernelGGL(k_fri_leaf_hash<FRI_LEAF_PRIO_BATCH>, dim3((n_leaves + 63) / 64), dim3(64), 0, st, va, vb, n_leaves,
+                         arity_bits, d_digests);
     return;
   }
   const size_t th = (size_t)n_leaves * coop::GROUP;

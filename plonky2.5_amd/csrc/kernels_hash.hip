@@ -166,6 +166,9 @@ constexpr size_t COOP_PARENTS_BATCH = 2048, COOP_PARENTS_SINGLE = 32768;
 // lowest priority above the sponges' is kept.  (Round 3 saw "nothing" from this at 24 queues, where a slow thin launch
 // delayed nobody.)
 // A lone proof has no sponge of another proof beside its levels and keeps priority 0.
+// The per-lane FRI leaf hash and the PoW search follow the same rule (FRI_LEAF_PRIO_BATCH, kernels_fri.hip; POW_PRIO_BATCH,
+// kernels_transcript.hip).  Measured and not adopted (profiles/r09_fri_pow_queue_time.txt; tools/exp/small_sponge_priority.patch):
+// priority 1 for k_hash_leaves on the 20- and 16-column commits as well -- level with priority 0 there in three rounds.
 // Measured and not adopted on top of this (same file; tools/exp/tree_tail.patch): the levels from 2^15 nodes down in ONE
 // launch (k_tree_tail: a 256-lane block reduces 512 nodes to one, levels staying in LDS) -- 6 launches per big tree
 // instead of 11 -- 129.5-129.8 proofs/s with priority 1 for the remaining levels, 124.8-125.3 with priority 0.

@@ -149,8 +149,11 @@ void launch_transcript(Transcript* d_tr, int init, const u64* d_obs, uint32_t n_
 // increasing order and leaves as soon as a witness below its next candidate is known.  A lane only ever skips
 // candidates above a witness already found, so *result ends as the smallest witness among the first `total` candidates
 // (~0, as the launch before left it, if there is none).  No lane waits for another.
+// PRIO: the wave priority, chosen per launch by launch_pow_search.
+template <int PRIO>
 __global__ __launch_bounds__(256) void k_pow_search(const Transcript* __restrict__ tr, uint32_t pow_bits, u64 total,
                                                     u64* result) {
+  if constexpr (PRIO != 0) P25_WAVE_PRIO(PRIO);
   const u64 G = (u64)gridDim.x * blockDim.x;
   for (u64 cand = (u64)blockIdx.x * blockDim.x + threadIdx.x; cand < total; cand += G) {
     if (__hip_atomic_load(result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < cand) return;
@@ -194,15 +197,25 @@ void launch_public_inputs(const u64* d_vals, size_t B, uint32_t p, const uint32_
   hipLaunchKernelGGL(k_public_inputs, dim3(1), dim3(64), 0, st, d_vals, B, p, d_pi_slots, n, d_values_out, d_hash_out);
 }
 
-void launch_pow_search(const Transcript* d_tr, int pow_bits, u64* d_result, hipStream_t st) {
+// Wave priority of the search when many proofs are in flight (= LEVEL_PRIO_BATCH, kernels_hash.hip, and for its reason):
+// one or two sweeps of a single permutation per lane, a wave per SIMD, which at priority 0 beside the other queues'
+// leaf sponges took 631 us in the pipeline against 86 us alone (profiles/r07_fused_chain.txt section 4b) while the three
+// other proofs of its in-order queue waited.  Measured: profiles/r09_fri_pow_queue_time.txt.  A lone proof has no other
+// proof's sponge beside it and keeps priority 0.
+constexpr int POW_PRIO_BATCH = 1;
+void launch_pow_search(const Transcript* d_tr, int pow_bits, u64* d_result, hipStream_t st, bool single_proof) {
   // *d_result = ~0 comes from the transcript launch that observed the final polynomial (TR_CLOSE_POW_INIT).
   // Expected number of candidates is 2^pow_bits.  The grid is 2^16 lanes (2^12 for pow_bits <= 12), so the expected
   // work is ~1.6 x 2^pow_bits permutations; the search gives up after 2^(pow_bits + 6) candidates, which happens with
   // probability e^-64 (reported as P25_ERR_INTERNAL by the transcript launch that observes the witness).
   const int wb = pow_bits < 12 ? 12 : pow_bits;
   const int gb = wb < 16 ? wb : 16;
-  hipLaunchKernelGGL(k_pow_search, dim3(1u << (gb - 8)), dim3(256), 0, st, d_tr, (uint32_t)pow_bits, (u64)1 << (wb + 6),
-                     d_result);
+  const dim3 grid(1u << (gb - 8));
+  const u64 total = (u64)1 << (wb + 6);
+  if (single_proof)
+    hipLaunchKernelGGL(k_pow_search<0>, grid, dim3(256), 0, st, d_tr, (uint32_t)pow_bits, total, d_result);
+  else
+    hipLaunchKernelGGL(k_pow_search<POW_PRIO_BATCH>, grid, dim3(256), 0, st, d_tr, (uint32_t)pow_bits, total, d_result);
 }
 
 }  // namespace p25

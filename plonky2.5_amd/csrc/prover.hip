@@ -215,7 +215,7 @@ void fri_commit_pow_query(NttTables& tables, FriWork& w, const FriShape& sh, Tra
   }
   qy.n_layers = (uint32_t)nl;
   // "find proof-of-work witness"
-  launch_pow_search(tr, sh.pow_bits, chal + CH_POW_WITNESS, st);
+  launch_pow_search(tr, sh.pow_bits, chal + CH_POW_WITNESS, st, single_proof);
   {  // observe the witness (and store it to the proof), draw the PoW response and the query indices, check the response
     TranscriptArgs ta{};
     ta.seg[0] = TrSegment{chal + CH_POW_WITNESS, nullptr, d_proof + fo.pow_witness, 1};

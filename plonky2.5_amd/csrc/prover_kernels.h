@@ -72,7 +72,7 @@ void launch_transcript(Transcript* d_tr, const TranscriptArgs& a, hipStream_t st
 void launch_transcript(Transcript* d_tr, int init, const u64* d_obs, uint32_t n_obs, u64* d_chal_out,
                        uint32_t n_chal, hipStream_t st);
 // *d_result = the smallest PoW witness for the transcript's current state; the caller has set it to ~0 (TR_CLOSE_POW_INIT)
-void launch_pow_search(const Transcript* d_tr, int pow_bits, u64* d_result, hipStream_t st);
+void launch_pow_search(const Transcript* d_tr, int pow_bits, u64* d_result, hipStream_t st, bool single_proof);
 // Public inputs of proof p of a witness pass: values[i] = vals[pi_slots[i] * B + p] -> d_values_out[n] (the flat
 // proof's public_inputs section) and their hash_no_pad (upstream `C::InnerHasher::hash_no_pad(&public_inputs)`) ->
 // d_hash_out[4].  One wave: the sponge is a chain of ceil(n / 8) permutations.

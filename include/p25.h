@@ -46,7 +46,14 @@ enum {
   P25_REJECT_INITIAL_MERKLE = 23,  /* a Merkle path of one of the four initial oracles does not reach its cap */
   P25_REJECT_FRI_EVAL = 24,        /* a FRI layer's opened value != the value folded so far */
   P25_REJECT_FRI_MERKLE = 25,      /* a FRI layer's Merkle path does not reach its cap */
-  P25_REJECT_FINAL_POLY = 26       /* the final polynomial != the last folded value */
+  P25_REJECT_FINAL_POLY = 26,      /* the final polynomial != the last folded value */
+  /* per-proof verdicts of p25_p3_verify_batch[_dev]; P25_OK = accepted */
+  P25_P3_REJECT_MALFORMED = 30,     /* a proof word >= p, anywhere */
+  P25_P3_REJECT_POW = 31,           /* p3_check_witness: the proof-of-work bits are not zero (verifier.rs:376) */
+  P25_P3_REJECT_INPUT_MERKLE = 32,  /* a query's trace or quotient batch does not reach its commitment (:288-294) */
+  P25_P3_REJECT_FRI_MERKLE = 33,    /* a commit-phase opening does not reach the round's commitment (:471-481) */
+  P25_P3_REJECT_FINAL_POLY = 34,    /* a query's folded value != final_poly (:413) */
+  P25_P3_REJECT_CONSTRAINTS = 35    /* the quotient identity at zeta does not hold (:239) */
 };
 
 /* Last error message of the calling thread ("" if none). */
@@ -533,6 +540,43 @@ p25_status p25_p3_prove_batch_dev(p25_p3_prover* p, const uint64_t* d_traces, si
                                   uint32_t* d_status, void* stream);
 p25_status p25_p3_prover_sync(p25_p3_prover* p);
 p25_status p25_p3_prover_set_scratch_budget(p25_p3_prover* p, size_t bytes);
+
+/* ------------------------------------------------------------------------------------------
+ * Verifying inner plonky3 proofs.  The reference states its plonky3 verifier only as a circuit (src/p3/verifier.rs, built by
+ * p25_circuit_build_p3_verifier[_air]); these run the same checks natively on flat proofs -- the words p25_p3_prove_batch
+ * writes, p25_p3_proof_from_json imports and p25_prove_batch reads -- for the AIR and shape of a p25_p3_prover handle: a
+ * screen before the outer prover, which can only answer P25_ERR_WITNESS_CONFLICT.  Per proof, P25_OK or the P25_P3_REJECT_*
+ * code of the FIRST check the sequential verifier fails, in that file's statement order: a word >= p anywhere; the proof of
+ * work; the input openings (trace batch, then quotient batch) of every query in index order; then per query the Merkle
+ * opening of every FRI round in order and the comparison of the folded value with final_poly -- so a final-polynomial
+ * failure of query 0 precedes a Merkle failure of query 1 --; the quotient identity at zeta last.  A zero denominator x - z
+ * in a reduced opening (zeta in the base field, on the LDE coset) counts as that query's final-polynomial failure and is
+ * reported ahead of that query's FRI rounds.
+ *   inputs[n_proofs][input_stride_words]   proof i = num_inputs words at i * input_stride_words; stride >= num_inputs
+ *                                 (P25_ERR_INVALID_ARG below it); the words behind a proof are neither read nor written.
+ *                                 At most 2^24 proofs per call and n_proofs * input_stride_words below 2^60, as for
+ *                                 p25_p3_prove_batch (P25_ERR_INVALID_ARG beyond either).
+ *   n_proofs = 0: P25_OK, nothing touched.  Argument errors come first, then P25_ERR_NO_DEVICE: there is no CPU path.
+ * Both forms check every proof word for >= p on the device (unlike the proving *_dev entries).
+ * p25_p3_verify_batch      host buffers: copies, runs on the handle's own stream, waits.
+ * p25_p3_verify_batch_dev  d_inputs and d_status (uint32_t[n_proofs]) resident in HBM.  ENQUEUE-ONLY on `stream` (NULL = the
+ *   default stream) and nowhere else, behind the handle's earlier calls through the same event wait as the proving calls
+ *   (so p25_p3_prove_batch_dev followed by this on the same words needs no host synchronisation); p25_p3_prover_sync
+ *   waits for it.  The two blocking exceptions of p25_p3_prove_batch_dev apply: the handle's first compute call, and growth.
+ * One launch per stage over the whole batch: transcript, identity, fold chains, Merkle paths, verdict.
+ * Memory: NO proving scratch is allocated -- a handle that only verifies never takes the proving budget.  The verifier
+ * owns a buffer of 8 + 2 log_n + num_queries + 2 num_queries log_n words per proof (challenges, query indices, the folded
+ * value of every query and round: 1,320 words for fib-64 with 100 queries), at most 32 MiB or the scratch budget if that
+ * is smaller; a larger batch is checked in chunks of as many proofs as fit (at least one), which changes no verdict.  It
+ * grows only after the earlier use has finished.  The verdict key lives in d_status while a batch is checked.
+ * p25_p3_prover_scratch_bytes  host only: the device scratch the handle holds now, proving and verifying (either NULL).
+ * Threading: as for the proving calls.
+ * ------------------------------------------------------------------------------------------ */
+p25_status p25_p3_verify_batch(p25_p3_prover* p, const uint64_t* inputs, size_t n_proofs, size_t input_stride_words,
+                               p25_status* per_proof_status);
+p25_status p25_p3_verify_batch_dev(p25_p3_prover* p, const uint64_t* d_inputs, size_t n_proofs, size_t input_stride_words,
+                                   uint32_t* d_status, void* stream);
+p25_status p25_p3_prover_scratch_bytes(p25_p3_prover* p, size_t* proving_out, size_t* verifying_out);
 
 /* Witness only (parity tests): wires_out[num_wires][2^degree_bits], column-major. */
 p25_status p25_witness(p25_circuit* c, const uint64_t* inputs, uint64_t seed, uint64_t* wires_out,

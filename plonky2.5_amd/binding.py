@@ -214,6 +214,9 @@ EXPORTED_SYMBOLS = {
     "p25_p3_prove_batch": (i32, [vp, vp, sz, vp, vp, sz, vp]),
     "p25_p3_prove_batch_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, vp, vp]),
     "p25_p3_prover_sync": (i32, [vp]),
+    "p25_p3_verify_batch": (i32, [vp, vp, sz, sz, vp]),
+    "p25_p3_verify_batch_dev": (i32, [vp, vp, sz, sz, vp, vp]),
+    "p25_p3_prover_scratch_bytes": (i32, [vp, C.POINTER(sz), C.POINTER(sz)]),
     "p25_p3_prover_set_scratch_budget": (i32, [vp, sz]),
     "p25_p3_prove_air": (i32, [C.POINTER(AirC), vp, i32, i32, i32, C.c_uint64, i32, vp, sz, C.POINTER(sz),
                                C.POINTER(P3Config)]),
@@ -492,6 +495,29 @@ class P3Prover:
         """Device-resident batch (raw device addresses), enqueued on `stream` (a raw hipStream_t; 0 = the default stream)."""
         _check(lib().p25_p3_prove_batch_dev(self._h, d_traces, trace_stride, n, d_pow_starts, d_inputs, input_stride, d_status,
                                             C.c_void_p(stream) if stream else None))
+
+    def verify(self, inputs, input_stride=None):
+        """inputs: uint64[n][input_stride] (or one proof), proof i = num_inputs words at the start of row i -> int32 statuses:
+        0 = accepted, else the P25_P3_REJECT_* code of the first check src/p3/verifier.rs fails."""
+        v = _u64(inputs)
+        if v.ndim == 1:
+            v = v.reshape(1, -1)
+        stride = v.shape[1] if input_stride is None else int(input_stride)
+        if v.ndim != 2 or v.shape[1] != stride:
+            raise ValueError("inputs must be [n][input_stride]")
+        st = np.zeros(v.shape[0], dtype=np.int32)
+        _check(lib().p25_p3_verify_batch(self._h, _ptr(v), v.shape[0], stride, _ptr(st)))
+        return st
+
+    def verify_dev(self, d_inputs, n, input_stride, d_status, stream=0):
+        """Device-resident batch (raw device addresses), enqueued on `stream` (a raw hipStream_t; 0 = the default stream)."""
+        _check(lib().p25_p3_verify_batch_dev(self._h, d_inputs, n, input_stride, d_status, C.c_void_p(stream) if stream else None))
+
+    def scratch_bytes(self):
+        """(proving, verifying): bytes of device scratch the handle holds now."""
+        a, b = sz(0), sz(0)
+        _check(lib().p25_p3_prover_scratch_bytes(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def sync(self):
         _check(lib().p25_p3_prover_sync(self._h))

@@ -701,6 +701,46 @@ p25_status p25_p3_prove_batch_dev(p25_p3_prover* p, const uint64_t* d_traces, si
     return P25_OK;
   });
 }
+// the argument errors of the two verifying entry points; returns false for an empty batch
+static bool p3_verify_args(p25_p3_prover* p, const void* inputs, size_t n_proofs, size_t input_stride, void* status) {
+  if (!p) throw std::invalid_argument("null argument");
+  if (!n_proofs) return false;
+  if (!inputs || !status) throw std::invalid_argument("null argument");
+  if (input_stride < p->dev->num_inputs()) throw std::invalid_argument("input_stride smaller than the proof's num_inputs");
+  if (n_proofs > ((size_t)1 << 24) || input_stride > ((size_t)1 << 60) / n_proofs)
+    throw std::invalid_argument("batch out of range (n_proofs * stride must stay below 2^60)");
+  return true;
+}
+p25_status p25_p3_verify_batch(p25_p3_prover* p, const uint64_t* inputs, size_t n_proofs, size_t input_stride_words,
+                               p25_status* per_proof_status) {
+  return host_guarded([&]() -> p25_status {
+    if (!p3_verify_args(p, inputs, n_proofs, input_stride_words, per_proof_status)) return P25_OK;
+    const p25_status s = ensure_device();
+    if (s != P25_OK) return s;
+    P25_LOCK(p);
+    p->dev->verify_host(inputs, n_proofs, input_stride_words, reinterpret_cast<int32_t*>(per_proof_status));
+    return P25_OK;
+  });
+}
+p25_status p25_p3_verify_batch_dev(p25_p3_prover* p, const uint64_t* d_inputs, size_t n_proofs, size_t input_stride_words,
+                                   uint32_t* d_status, void* stream) {
+  return host_guarded([&]() -> p25_status {
+    if (!p3_verify_args(p, d_inputs, n_proofs, input_stride_words, d_status)) return P25_OK;
+    const p25_status s = ensure_device();
+    if (s != P25_OK) return s;
+    P25_LOCK(p);
+    p->dev->verify_dev(d_inputs, n_proofs, input_stride_words, d_status, (hipStream_t)stream);
+    return P25_OK;
+  });
+}
+p25_status p25_p3_prover_scratch_bytes(p25_p3_prover* p, size_t* proving_out, size_t* verifying_out) {
+  return host_guarded([&]() -> p25_status {
+    if (!p) throw std::invalid_argument("null argument");
+    P25_LOCK(p);
+    p->dev->scratch_bytes(proving_out, verifying_out);
+    return P25_OK;
+  });
+}
 p25_status p25_p3_prover_sync(p25_p3_prover* p) {
   return host_guarded([&]() -> p25_status {
     if (!p) throw std::invalid_argument("null argument");

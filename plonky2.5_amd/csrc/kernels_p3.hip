@@ -13,7 +13,7 @@
 // Field arithmetic is exact, so any evaluation order gives the host's words; the orders the protocol fixes (constraint
 // fold, transcript, flattening) are the host's.
 #include "coop.h"
-#include "p3_kernels.h"
+#include "p3_air_run.h"
 
 namespace p25 {
 namespace {
@@ -260,58 +260,8 @@ __global__ __launch_bounds__(64) void k_p3_chain(P3Shape sh, P3Bufs b, uint32_t 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The AIR program
+// The AIR program (run_air: p3_air_run.h)
 // ---------------------------------------------------------------------------------------------------------------------
-struct BaseF {
-  typedef u64 T;
-  __device__ static u64 cst(u64 v) { return v; }
-  __device__ static u64 add(u64 x, u64 y) { return gl::add(x, y); }
-  __device__ static u64 sub(u64 x, u64 y) { return gl::sub(x, y); }
-  __device__ static u64 mul(u64 x, u64 y) { return gl::mul(x, y); }
-  // VerifierConstraintFolder::assert_zero: acc = acc * alpha + c
-  __device__ static E2 fold(E2 acc, E2 alpha, u64 c) {
-    acc = gl::mul(acc, alpha);
-    acc.a = gl::add(acc.a, c);
-    return acc;
-  }
-};
-struct ExtF {
-  typedef E2 T;
-  __device__ static E2 cst(u64 v) { return gl::e2(v); }
-  __device__ static E2 add(E2 x, E2 y) { return gl::add(x, y); }
-  __device__ static E2 sub(E2 x, E2 y) { return gl::sub(x, y); }
-  __device__ static E2 mul(E2 x, E2 y) { return gl::mul(x, y); }
-  __device__ static E2 fold(E2 acc, E2 alpha, E2 c) { return gl::add(gl::mul(acc, alpha), c); }
-};
-// Runs the register program: `load(next, column)` reads the row, the constraints are folded in program order.
-template <class F, class Load>
-__device__ E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u64* __restrict__ consts, Load load,
-                      const typename F::T sel[4], E2 alpha) {
-  typedef typename F::T T;
-  T slot[P3_MAX_LIVE];
-  auto fetch = [&](uint32_t o) -> T {
-    const uint32_t kind = o >> 28, i = o & 0x0fffffffu;
-    switch (kind) {
-      case P3_OPND_SLOT: return slot[i];
-      case P3_OPND_LOCAL: return load(0, i);
-      case P3_OPND_NEXT: return load(1, i);
-      default: return F::cst(consts[i]);
-    }
-  };
-  E2 acc = gl::e2(0);
-  for (uint32_t pc = 0; pc < n_instr; pc++) {
-    const P3Instr in = prog[pc];
-    const T x = fetch(in.a);
-    if (in.op == P3_OP_EMIT) {
-      acc = F::fold(acc, alpha, in.dst == 0 ? x : F::mul(sel[in.dst & 3], x));
-    } else {
-      const T y = fetch(in.b);
-      slot[in.dst] = in.op == P3_OP_ADD ? F::add(x, y) : in.op == P3_OP_SUB ? F::sub(x, y) : F::mul(x, y);
-    }
-  }
-  return acc;
-}
-
 // One lane per point of the quotient coset 7 H_{n 2^lqd}.  Lane p takes the point stored at position p of the bit-reversed
 // trace LDE (j = rev(p)), so the local row is read coalesced; its chunk is rev(p >> k) and its place in the chunk, in
 // bit-reversed order, p mod n -- the order the inverse transform of the chunks takes.

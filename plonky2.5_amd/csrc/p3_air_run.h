@@ -1,0 +1,59 @@
+// Internal: the interpreter of an AIR's register program (P3AirDevice, p3_kernels.h), shared by the prover's quotient and
+// identity kernels (kernels_p3.hip) and the verifier's identity lane (p3_verify_lanes.h).  Host and device: the verifier's
+// lane functions also compile for the host.
+#pragma once
+#include "p3_kernels.h"
+
+namespace p25 {
+
+struct BaseF {
+  typedef u64 T;
+  GL_HD static u64 cst(u64 v) { return v; }
+  GL_HD static u64 add(u64 x, u64 y) { return gl::add(x, y); }
+  GL_HD static u64 sub(u64 x, u64 y) { return gl::sub(x, y); }
+  GL_HD static u64 mul(u64 x, u64 y) { return gl::mul(x, y); }
+  // VerifierConstraintFolder::assert_zero: acc = acc * alpha + c
+  GL_HD static gl::E2 fold(gl::E2 acc, gl::E2 alpha, u64 c) {
+    acc = gl::mul(acc, alpha);
+    acc.a = gl::add(acc.a, c);
+    return acc;
+  }
+};
+struct ExtF {
+  typedef gl::E2 T;
+  GL_HD static gl::E2 cst(u64 v) { return gl::e2(v); }
+  GL_HD static gl::E2 add(gl::E2 x, gl::E2 y) { return gl::add(x, y); }
+  GL_HD static gl::E2 sub(gl::E2 x, gl::E2 y) { return gl::sub(x, y); }
+  GL_HD static gl::E2 mul(gl::E2 x, gl::E2 y) { return gl::mul(x, y); }
+  GL_HD static gl::E2 fold(gl::E2 acc, gl::E2 alpha, gl::E2 c) { return gl::add(gl::mul(acc, alpha), c); }
+};
+// Runs the register program: `load(next, column)` reads the row, the constraints are folded in program order.
+template <class F, class Load>
+GL_HD gl::E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u64* __restrict__ consts, Load load,
+                         const typename F::T sel[4], gl::E2 alpha) {
+  typedef typename F::T T;
+  T slot[P3_MAX_LIVE];
+  auto fetch = [&](uint32_t o) -> T {
+    const uint32_t kind = o >> 28, i = o & 0x0fffffffu;
+    switch (kind) {
+      case P3_OPND_SLOT: return slot[i];
+      case P3_OPND_LOCAL: return load(0, i);
+      case P3_OPND_NEXT: return load(1, i);
+      default: return F::cst(consts[i]);
+    }
+  };
+  gl::E2 acc = gl::e2(0);
+  for (uint32_t pc = 0; pc < n_instr; pc++) {
+    const P3Instr in = prog[pc];
+    const T x = fetch(in.a);
+    if (in.op == P3_OP_EMIT) {
+      acc = F::fold(acc, alpha, in.dst == 0 ? x : F::mul(sel[in.dst & 3], x));
+    } else {
+      const T y = fetch(in.b);
+      slot[in.dst] = in.op == P3_OP_ADD ? F::add(x, y) : in.op == P3_OP_SUB ? F::sub(x, y) : F::mul(x, y);
+    }
+  }
+  return acc;
+}
+
+}  // namespace p25

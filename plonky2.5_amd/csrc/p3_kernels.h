@@ -94,7 +94,10 @@ void p3_launch_gather(const P3Shape& s, const P3Bufs& b, u64* d_out, size_t out_
 // ---- the prover handle's device side (p3_prover_dev.hip) ----
 // Default scratch budget of a prover: a batch runs in groups of as many proofs as fit (at least one).
 constexpr size_t P3_SCRATCH_BUDGET_BYTES = (size_t)12 << 30;
+// The verifier's buffer never grows past this: a larger batch is checked in chunks.
+constexpr size_t P3_VERIFY_SCRATCH_BYTES = (size_t)32 << 20;
 struct P3ProverImpl;
+struct P3VerifyArgs;   // p3_verify_lanes.h
 class P3ProverDev {
  public:
   // host only: validates as p3_prove_air does and compiles the AIR; throws std::invalid_argument
@@ -113,6 +116,20 @@ class P3ProverDev {
   void prove_host(const u64* traces, size_t n_proofs, const u64* pow_starts, u64* inputs_out, size_t input_stride,
                   int32_t* statuses);
   void sync();
+  // The verifying side (p3_verify_dev.hip, kernels_p3_verify.hip): src/p3/verifier.rs on flat proofs of this handle's AIR and
+  // shape.  Takes none of the proving scratch; its own buffer holds verify_scratch_words_per_proof() words per proof of a
+  // chunk, and a chunk is what fits min(the scratch budget, P3_VERIFY_SCRATCH_BYTES) -- at least one proof.
+  size_t verify_scratch_words_per_proof() const;
+  size_t verify_chunk(size_t n_proofs) const;
+  // enqueue-only on `st`; d_status[i] = 0 or a P25_P3_REJECT_* code
+  void verify_dev(const u64* d_inputs, size_t n_proofs, size_t input_stride, uint32_t* d_status, hipStream_t st);
+  // host buffers (checked by the caller): copies, verifies on the handle's own stream, waits
+  void verify_host(const u64* inputs, size_t n_proofs, size_t input_stride, int32_t* statuses);
+  // the batch description without the batch (host pointers to the AIR program): also what the host driver of the lane
+  // functions starts from (tests/native/p3_verify_lanes.cpp)
+  P3VerifyArgs verify_args() const;
+  // bytes of device scratch the handle holds now, by side
+  void scratch_bytes(size_t* proving, size_t* verifying) const;
 
  private:
   void ensure_impl();

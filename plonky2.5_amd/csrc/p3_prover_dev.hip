@@ -2,8 +2,7 @@
 // group of proofs, which mirrors p3_prove_air (p3_prover.cpp) stage by stage.  The kernels are in kernels_p3.hip.
 #include <algorithm>
 #include <functional>
-#include "p3_kernels.h"
-#include "prover.h"
+#include "p3_prover_impl.h"
 
 namespace p25 {
 
@@ -104,21 +103,6 @@ P3AirDevice P3AirDevice::compile(const AirProgram& air) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-struct P3ProverImpl {
-  NttTables tables;
-  DevMem prog, consts, zfirst, scratch;
-  hipStream_t own_stream = nullptr;
-  // Recorded behind the last launch of every compute call.  The next call's stream waits for it before it touches the
-  // scratch, so calls on different streams take the one scratch region in turn; each call's record sits behind its wait
-  // for the call before, so the latest record covers everything the prover has enqueued.
-  hipEvent_t done = nullptr;
-  bool recorded = false;
-  ~P3ProverImpl() {
-    if (done) (void)hipEventDestroy(done);
-    if (own_stream) (void)hipStreamDestroy(own_stream);
-  }
-};
-
 P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int num_queries, int pow_bits) {
   // exactly p3_prove_air's checks (p3_prover.cpp:194-230)
   if (log_n < 1 || log_n > 22 || log_blowup < 1 || log_blowup > 4 || log_n + log_blowup > 24 || num_queries < 1 || pow_bits < 0 ||
@@ -234,13 +218,7 @@ void P3ProverDev::prove_dev(const u64* d_traces, size_t trace_stride, size_t n_p
   // the scratch is one region: wait, on the device, for the call before, whichever stream it went to; and leave the
   // record for the next call behind whatever this one managed to enqueue, also when it throws half way
   if (impl_->recorded) P25_HIP(hipStreamWaitEvent(st, impl_->done, 0));
-  struct Record {
-    P3ProverImpl* im;
-    hipStream_t st;
-    ~Record() {
-      if (hipEventRecord(im->done, st) == hipSuccess) im->recorded = true;
-    }
-  } record{impl_, st};
+  P3CallRecord record{impl_, st};
   for (size_t g0 = 0; g0 < n_proofs; g0 += G) {
     const size_t cnt = std::min(G, n_proofs - g0);
     run_group(d_traces + g0 * trace_stride, trace_stride, (uint32_t)cnt, d_pow_starts ? d_pow_starts + g0 : nullptr,

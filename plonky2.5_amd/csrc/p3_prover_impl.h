@@ -1,0 +1,34 @@
+// Internal: the device state of a p25_p3_prover handle, shared by its proving side (p3_prover_dev.hip) and its verifying
+// side (p3_verify_dev.hip).
+#pragma once
+#include "p3_kernels.h"
+#include "prover.h"
+
+namespace p25 {
+
+struct P3ProverImpl {
+  NttTables tables;
+  DevMem prog, consts, zfirst, scratch;
+  DevMem vscratch;   // the verifier's: challenge blocks and folded values (p3_verify_dev.hip)
+  hipStream_t own_stream = nullptr;
+  // Recorded behind the last launch of every compute call.  The next call's stream waits for it before it touches the
+  // scratch, so calls on different streams take the one scratch region in turn; each call's record sits behind its wait
+  // for the call before, so the latest record covers everything the prover has enqueued.
+  hipEvent_t done = nullptr;
+  bool recorded = false;
+  ~P3ProverImpl() {
+    if (done) (void)hipEventDestroy(done);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
+};
+
+// Leaves the record for the next call behind whatever a compute call managed to enqueue, also when it throws half way.
+struct P3CallRecord {
+  P3ProverImpl* im;
+  hipStream_t st;
+  ~P3CallRecord() {
+    if (hipEventRecord(im->done, st) == hipSuccess) im->recorded = true;
+  }
+};
+
+}  // namespace p25

@@ -769,7 +769,7 @@ class Circuit:
         _check(lib().p25_circuit_wait_mark(self._h, producer._h, slot))
 
     def set_streams(self, n):
-        """Proofs kept in flight by the batch entry points (1..32, default 16)."""
+        """Proofs kept in flight by the batch entry points (1..32; default 16, or 32 where the host exports four or more hardware queues)."""
         _check(lib().p25_circuit_set_streams(self._h, n))
 
     def kernel_stats(self, enable=True, reset=False):

@@ -82,6 +82,15 @@ static bool apply_hw_queues(int hw_queues) {
   }
   return g_hwq.requested > 0 && !g_hwq.host_exported && g_hwq.runtime_was_up;
 }
+// Proofs in flight of a circuit whose host set none (inflight.h), from the hardware-queue count this process runs with: the
+// value the host exported, or the library's own request (apply_hw_queues has placed it in the environment).  A request that
+// came too late, or none at all, leaves the count unknown.  Call after ensure_device / p25_device_init[_ex].
+static int default_streams() {
+  std::lock_guard<std::mutex> l(g_hwq.mu);
+  const char* e = getenv("GPU_MAX_HW_QUEUES");
+  const bool known = g_hwq.decided && e && (g_hwq.host_exported || !g_hwq.runtime_was_up);
+  return default_inflight(known ? (int)strtol(e, nullptr, 10) : 0);
+}
 static const char* const HWQ_LATE_MSG =
     "warning: GPU_MAX_HW_QUEUES was not in the environment and the GPU runtime was already open in this process when libp25 "
     "first ran (the host, torch or a profiler touched HIP first): if HIP had been initialised too the setting has no effect "
@@ -153,7 +162,7 @@ struct p25_circuit {
   std::unique_ptr<p25::DeviceCircuit> dev;
   std::unique_ptr<p25::WitnessProgram> wp_info;
   bool moved = false;
-  int streams = 16;  // proofs in flight (p25_circuit_set_streams)
+  int streams = 0;   // proofs in flight (p25_circuit_set_streams); 0 = not set: default_streams() at the first device use
   // Entry points that touch the device state of ONE circuit are serialised: upstream's `prove(&self)` is re-entrant,
   // so a host with a thread pool may call into the same circuit concurrently; here those calls queue up instead of
   // racing for the circuit's streams and contexts.  Different circuits never contend.
@@ -162,7 +171,7 @@ struct p25_circuit {
   p25::DeviceCircuit& device() {
     if (!dev) {
       dev.reset(new p25::DeviceCircuit(std::move(circuit)));
-      dev->set_streams(streams);
+      dev->set_streams(streams ? streams : p25::default_streams());
       moved = true;
     }
     return *dev;
@@ -481,7 +490,7 @@ p25_status p25_runtime_info(p25_runtime_info_t* out) {
   }
   const char* e = getenv("GPU_MAX_HW_QUEUES");
   out->hw_queues_env = e ? (int32_t)strtol(e, nullptr, 10) : 0;
-  out->proving_streams = 16;
+  out->proving_streams = (int32_t)proving_pool_width();   // 16 until a circuit has proved at a greater depth
   out->main_streams = 2;
   return P25_OK;
 }
@@ -972,7 +981,7 @@ p25_status p25_circuit_stream_wait_mark(p25_circuit* c, uint32_t slot, void* str
 p25_status p25_circuit_set_streams(p25_circuit* c, int32_t n_streams) {
   return host_guarded([&]() -> p25_status {
     if (!c) throw std::invalid_argument("null argument");
-    if (n_streams < 1 || n_streams > 32) throw std::invalid_argument("n_streams must be in 1..32");
+    if (n_streams < 1 || n_streams > INFLIGHT_MAX) throw std::invalid_argument("n_streams must be in 1..32");
     P25_LOCK(c);
     c->streams = n_streams;
     if (c->dev) c->dev->set_streams(n_streams);

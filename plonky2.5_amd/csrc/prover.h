@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "builder.h"
+#include "inflight.h"
 #include "prover_kernels.h"
 
 namespace p25 {
@@ -70,6 +71,9 @@ struct MainStreamLease {
   ~MainStreamLease();
 };
 
+// Width of the process-wide pool of proving streams (prover.hip: StreamPool): 16 until a circuit has asked for more.
+size_t proving_pool_width();
+
 class DeviceCircuit {
  public:
   explicit DeviceCircuit(Circuit c);
@@ -124,8 +128,8 @@ class DeviceCircuit {
   void mark(int slot);
   void wait_mark(DeviceCircuit& producer, int slot);
   void stream_wait_mark(hipStream_t ext, int slot);   // a caller's stream waits for mark(slot) (stream_join, but lag-able)
-  // proofs kept in flight by prove_batch* (one HIP stream + working set each), 1..16
-  void set_streams(int k) { streams_ = k < 1 ? 1 : (k > 32 ? 32 : k); }
+  // proofs kept in flight by prove_batch* (one HIP stream + working set each), 1..32
+  void set_streams(int k) { streams_ = k < 1 ? 1 : (k > INFLIGHT_MAX ? INFLIGHT_MAX : k); }
   hipStream_t stream() const { return stream_; }
   // Isolated stages (host buffers; parity tests of SURVEY 8a7 / 8a8 through p25_partial_products / p25_quotient):
   // wires[num_wires][n] -> out[NC*(1+NP)][n];  wires + zs_pp values -> out[NC*8][n] quotient chunk coefficients
@@ -169,6 +173,7 @@ class DeviceCircuit {
   DevMem vals_[2];             // witness values of a pass, slot-major [slot][proof of the pass]; double-buffered
   size_t vals_batch_[2] = {0, 0};
   size_t pass_counter_ = 0;    // witness passes issued so far (parity = buffer)
+  size_t proof_counter_ = 0;   // proofs handed to the contexts so far (inflight.h: ctx_for_proof)
   std::vector<DevMem> owned_;
   DevMem verify_scratch_;      // verify_batch_dev: challenge blocks and vanishing partials of a batch, caller's verifier data
   bool kstats_on_ = false;

@@ -82,6 +82,10 @@ struct StreamPool {
 // never destroyed: circuits of static storage duration in a host may outlive any static of this library
 StreamPool& g_stream_pool = *new StreamPool;
 }  // namespace
+size_t proving_pool_width() {
+  std::lock_guard<std::mutex> l(g_stream_pool.mu);
+  return g_stream_pool.width;
+}
 MainStreamLease::~MainStreamLease() {
   if (slot >= 0) g_stream_pool.main_release(*this);
 }
@@ -942,7 +946,7 @@ void DeviceCircuit::prove_batch_dev(const u64* d_inputs, size_t n_proofs, const 
       if (K > fit) K = fit;
     }
   }
-  ensure_ctx(K);
+  ensure_ctx(K);   // K: what the clamp granted; it is the modulus of the assignment below
   single_proof_ = K == 1;  // a lone proof in flight: latency-oriented kernel forms
   // Witness generation runs for up to 64 proofs per pass on the main stream into one of TWO value buffers, so the
   // pass for proofs [k+64, k+128) runs underneath the proving pipelines of [k, k+64): a context stream only waits for
@@ -975,9 +979,15 @@ void DeviceCircuit::prove_batch_dev(const u64* d_inputs, size_t n_proofs, const 
       (void)hipEventDestroy(e0);
       (void)hipEventDestroy(e1);
     }
-    for (size_t k = 0; k < K && k < bsz; k++) P25_HIP(hipStreamWaitEvent(ctxs_[k]->st, ev_witness_[buf], 0));
-    for (size_t p = 0; p < bsz; p++)
-      prove_one(*ctxs_[p % K], buf, bsz, (uint32_t)p, d_proofs + (base + p) * proof_stride, d_status + base + p, times);
+    // Proof p of the pass goes to context (proof_counter_ + p) mod K (inflight.h): the start rotates from pass to pass, so a
+    // short pass touches a rotated subset of the contexts.  The first K proofs of a pass land on K different contexts:
+    // each of those waits for the pass's witness event before its first proof of the pass.
+    for (size_t p = 0; p < bsz; p++) {
+      Ctx& x = *ctxs_[ctx_for_proof(proof_counter_ + p, K)];
+      if (p < K) P25_HIP(hipStreamWaitEvent(x.st, ev_witness_[buf], 0));
+      prove_one(x, buf, bsz, (uint32_t)p, d_proofs + (base + p) * proof_stride, d_status + base + p, times);
+    }
+    proof_counter_ += bsz;
   }
   pass_counter_ += pass;
   P25_HIP(hipGetLastError());

@@ -186,18 +186,6 @@ struct p25_p3_prover {
 
 namespace p25 {
 namespace {
-struct DevBuf {
-  u64* p = nullptr;
-  explicit DevBuf(size_t words) {
-    if (words) P25_HIP(hipMalloc(&p, words * sizeof(u64)));
-  }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
 // guard: host-only entry points
 template <class F>
 p25_status host_guarded(F&& f) {
@@ -273,7 +261,7 @@ p25_status permute_host(uint64_t* states, size_t n, void (*launch)(u64*, size_t,
     if (!any_u64)
       for (size_t i = 0; i < n * 12; i++)
         if (states[i] >= gl::P) throw std::invalid_argument("non-canonical field element in states");
-    DevBuf d(n * 12);
+    DevMem d(n * 12);
     P25_HIP(hipMemcpy(d.p, states, n * 96, hipMemcpyHostToDevice));
     launch(d.p, n, 0);
     P25_HIP(hipGetLastError());
@@ -508,9 +496,9 @@ p25_status p25_merkle_commit(const uint64_t* leaves_cm, size_t n_leaves, size_t 
     // refused, not reduced: a leaf of at most 4 words is its own digest (hash_or_noop), so its words ARE tree words
     for (size_t i = 0; i < n_leaves * width; i++)
       if (leaves_cm[i] >= gl::P) throw std::invalid_argument("p25_merkle_commit: non-canonical field element");
-    DevBuf d(n_leaves * width);
+    DevMem d(n_leaves * width);
     size_t tw = merkle_tree_words(n_leaves, cap_height);
-    DevBuf t(tw);
+    DevMem t(tw);
     P25_HIP(hipMemcpy(d.p, leaves_cm, n_leaves * width * 8, hipMemcpyHostToDevice));
     u64* cap = launch_merkle_tree(d.p, n_leaves, (int)width, n_leaves, cap_height, t.p, 0);
     P25_HIP(hipGetLastError());
@@ -535,9 +523,9 @@ p25_status p25_lde_commit(const uint64_t* polys, unsigned log_n, size_t n_polys,
     for (size_t i = 0; i < n * n_polys; i++)
       if (polys[i] >= gl::P) throw std::invalid_argument("p25_lde_commit: non-canonical field element");
     std::lock_guard<std::mutex> lk(g_primitives_mutex);
-    DevBuf in(n * n_polys), co(n * n_polys), tmp(n * n_polys), lde(big * n_polys);
+    DevMem in(n * n_polys), co(n * n_polys), tmp(n * n_polys), lde(big * n_polys);
     size_t tw = merkle_tree_words(big, cap_height);
-    DevBuf tree(tw);
+    DevMem tree(tw);
     P25_HIP(hipMemcpy(in.p, polys, n * n_polys * 8, hipMemcpyHostToDevice));
     lde_commit_dev(in.p, log_n, n_polys, from_coeffs != 0, rate_bits, cap_height, co.p, tmp.p, lde.p,
                    tree.p, 0);
@@ -1042,7 +1030,7 @@ p25_status p25_eval_polys(const uint64_t* coeffs, size_t n_polys, unsigned log_n
     for (size_t i = 0; i < n_polys * n; i++)
       if (coeffs[i] >= gl::P) throw std::invalid_argument("non-canonical coefficient");
     const size_t chunks = log_n > 16 ? ((size_t)1 << (log_n - 16)) : 1;
-    DevBuf d_c(n_polys * n), d_pt(2), d_scr(2 * 1026 + 2 * n_polys * chunks), d_out(2 * n_polys);
+    DevMem d_c(n_polys * n), d_pt(2), d_scr(2 * 1026 + 2 * n_polys * chunks), d_out(2 * n_polys);
     P25_HIP(hipMemcpy(d_c.p, coeffs, n_polys * n * 8, hipMemcpyHostToDevice));
     P25_HIP(hipMemcpy(d_pt.p, point, 16, hipMemcpyHostToDevice));
     launch_eval_polys(d_c.p, (uint32_t)n_polys, log_n, d_pt.p, scale, d_scr.p, d_out.p, 0);

@@ -34,7 +34,6 @@ struct Rccl {
   ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
   ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
   ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*CommAbort)(ncclComm_t) = nullptr;
   ncclResult_t (*GroupStart)() = nullptr;
   ncclResult_t (*GroupEnd)() = nullptr;
   ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
@@ -65,7 +64,6 @@ Rccl& rccl() {
     r.GetUniqueId = (decltype(r.GetUniqueId))sym("ncclGetUniqueId");
     r.CommInitRank = (decltype(r.CommInitRank))sym("ncclCommInitRank");
     r.CommDestroy = (decltype(r.CommDestroy))sym("ncclCommDestroy");
-    r.CommAbort = (decltype(r.CommAbort))sym("ncclCommAbort");
     r.GroupStart = (decltype(r.GroupStart))sym("ncclGroupStart");
     r.GroupEnd = (decltype(r.GroupEnd))sym("ncclGroupEnd");
     r.Send = (decltype(r.Send))sym("ncclSend");
@@ -133,8 +131,8 @@ void copy_words(const T* src, T* dst, size_t n, hipStream_t st) {
 struct p25_comm {
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1, device = 0;
-  hipStream_t stream = nullptr;   // every collective of this communicator runs here, in issue order
-  u64* d_scratch = nullptr;       // 2 words: barrier / max-reduction operand
+  DevStream stream;               // every collective of this communicator runs here, in issue order
+  DevMem scratch;                 // 2 words: barrier / max-reduction operand
   std::mutex mu;                  // RCCL calls on one communicator are issued by one thread at a time
 };
 
@@ -160,16 +158,11 @@ p25_status p25_comm_init(const uint8_t* id, int32_t rank, int32_t world, p25_com
     c->rank = rank;
     c->world = world;
     P25_HIP(hipGetDevice(&c->device));   // ensure_device() has put the thread on the device p25_device_init selected
+    c->stream = DevStream(hipStreamNonBlocking);
+    c->scratch = DevMem(4);
     ncclUniqueId uid;
     memcpy(uid.internal, id, P25_COMM_ID_BYTES);
-    P25_NCCL(r.CommInitRank(&c->comm, world, uid, rank));
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&c->d_scratch, 4 * sizeof(u64));
-    if (e != hipSuccess) {
-      if (c->stream) (void)hipStreamDestroy(c->stream);
-      (void)r.CommAbort(c->comm);
-      P25_HIP(e);
-    }
+    P25_NCCL(r.CommInitRank(&c->comm, world, uid, rank));   // last: what can fail after it would have to abort it
     *out = c.release();
     return P25_OK;
   });
@@ -180,19 +173,16 @@ p25_status p25_comm_destroy(p25_comm* c) {
   p25_status s = comm_guarded([&](Rccl& r) -> p25_status {
     std::lock_guard<std::mutex> l(c->mu);
     (void)hipStreamSynchronize(c->stream);
-    ncclResult_t e = r.CommDestroy(c->comm);
-    (void)hipStreamDestroy(c->stream);
-    (void)hipFree(c->d_scratch);
-    nccl_check(e, "ncclCommDestroy");
+    P25_NCCL(r.CommDestroy(c->comm));
     return P25_OK;
   });
-  delete c;
+  delete c;   // the stream and the scratch, after the communicator
   return s;
 }
 
 int32_t p25_comm_rank(const p25_comm* c) { return c ? c->rank : -1; }
 int32_t p25_comm_world(const p25_comm* c) { return c ? c->world : 0; }
-void* p25_comm_stream(p25_comm* c) { return c ? (void*)c->stream : nullptr; }
+void* p25_comm_stream(p25_comm* c) { return c ? (void*)c->stream.s : nullptr; }
 
 p25_status p25_comm_sync(p25_comm* c) {
   return comm_guarded([&](Rccl&) -> p25_status {
@@ -208,9 +198,9 @@ p25_status p25_comm_max_f64(p25_comm* c, double* value) {
     if (!c) throw std::invalid_argument("null argument");
     std::lock_guard<std::mutex> l(c->mu);
     double v = value ? *value : 0.0;
-    P25_HIP(hipMemcpyAsync(c->d_scratch, &v, sizeof v, hipMemcpyHostToDevice, c->stream));
-    P25_NCCL(r.AllReduce(c->d_scratch, c->d_scratch + 1, 1, ncclDouble, ncclMax, c->comm, c->stream));
-    P25_HIP(hipMemcpyAsync(&v, c->d_scratch + 1, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    P25_HIP(hipMemcpyAsync(c->scratch.p, &v, sizeof v, hipMemcpyHostToDevice, c->stream));
+    P25_NCCL(r.AllReduce(c->scratch.p, c->scratch.p + 1, 1, ncclDouble, ncclMax, c->comm, c->stream));
+    P25_HIP(hipMemcpyAsync(&v, c->scratch.p + 1, sizeof v, hipMemcpyDeviceToHost, c->stream));
     P25_HIP(hipStreamSynchronize(c->stream));
     if (value) *value = v;
     return P25_OK;

@@ -8,6 +8,7 @@
 #include <vector>
 #include <map>
 #include <tuple>
+#include "dev_res.h"
 #include "gl.h"
 
 // Wave priority (s_setprio, 0..3) in the SIMDs' issue arbitration.  The bulk hash kernels (k_hash_leaves*, and k_pow_search,
@@ -27,17 +28,6 @@
 #define P25_PRIO_BULK 2
 #define P25_PRIO_CHAIN 3
 namespace p25 {
-
-struct HipError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-#define P25_HIP(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess)                                                                     \
-      throw p25::HipError(std::string(#expr) + ": " + hipGetErrorString(_e) + " at " +        \
-                          __FILE__ + ":" + std::to_string(__LINE__));                         \
-  } while (0)
 
 // ---------------- hashing (kernels_hash.hip) ----------------
 void launch_poseidon_permute(u64* d_states, size_t n, hipStream_t st);
@@ -82,7 +72,6 @@ double measure_shader_clock_hz(hipStream_t st);
 
 class NttTables {
  public:
-  ~NttTables();
   // device table of w^e, e < 2^log_n, w = primitive 2^log_n-th root (or its inverse)
   const u64* pow_table(int log_n, bool inverse);
   // device table of base^e for e < len (cached by (base, len))
@@ -95,7 +84,7 @@ class NttTables {
   CosetCache coset_;
   std::map<std::pair<int, bool>, u64*> pow_;
   std::map<std::tuple<u64, u64, size_t>, u64*> geom_;
-  std::vector<u64*> owned_;
+  std::vector<DevMem> owned_;
 };
 
 // values (natural order) -> coefficients (natural order); in/out/tmp are [n_polys][n] with the

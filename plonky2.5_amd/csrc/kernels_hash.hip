@@ -232,19 +232,16 @@ __global__ __launch_bounds__(64) void k_clock_probe(u64* sink, int reps, unsigne
 }
 double measure_shader_clock_hz(hipStream_t st) {
   const unsigned blocks = 8192, probes = blocks / 1024;
-  u64* d = nullptr;
-  P25_HIP(hipMalloc(&d, (64 + 2 * probes) * 8));
-  unsigned long long* clk = (unsigned long long*)(d + 64);
+  DevMem d(64 + 2 * probes);
+  unsigned long long* clk = (unsigned long long*)(d.p + 64);
   int dev = 0, khz = 0;
   P25_HIP(hipGetDevice(&dev));
   P25_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
   unsigned long long h[2 * probes];
   for (int it = 0; it < 2; it++)  // first pass warms the clocks up
-    hipLaunchKernelGGL(k_clock_probe, dim3(blocks), dim3(64), 0, st, d, 64, clk);
-  hipError_t e = hipMemcpyAsync(h, clk, sizeof(h), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(d);
-  P25_HIP(e);
+    hipLaunchKernelGGL(k_clock_probe, dim3(blocks), dim3(64), 0, st, d.p, 64, clk);
+  P25_HIP(hipMemcpyAsync(h, clk, sizeof(h), hipMemcpyDeviceToHost, st));
+  P25_HIP(hipStreamSynchronize(st));
   double cyc = 0, ticks = 0;
   for (unsigned i = 0; i < probes; i++) {
     cyc += (double)h[2 * i];

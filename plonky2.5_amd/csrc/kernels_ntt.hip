@@ -337,13 +337,9 @@ void ntt_inverse_then_lde(NttTables& tb, const u64* d_vals, size_t val_stride, u
   ntt_lde_bitrev(tb, d_coeffs, coeff_stride, d_lde, lde_stride, log_n, rate_bits, n_polys, shift, st);
 }
 
-NttTables::~NttTables() {
-  for (u64* p : owned_) (void)hipFree(p);
-}
 const u64* NttTables::upload(const std::vector<u64>& host) {
-  u64* d = nullptr;
-  P25_HIP(hipMalloc(&d, host.size() * sizeof(u64)));
-  owned_.push_back(d);
+  owned_.emplace_back(host.size());
+  u64* d = owned_.back().p;
   P25_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(u64), hipMemcpyHostToDevice));
   return d;
 }

@@ -174,12 +174,37 @@ P3ProverDev::~P3ProverDev() {
   }
 }
 
-size_t P3ProverDev::scratch_words_per_proof() const {
-  const P3Shape& s = shape_;
+// The carve-up of a group's scratch, written once: the buffers of G proofs from `base`, and the words they take.  A null
+// base gives the size alone (no pointer is formed).  Every term is linear in G.
+struct P3Carve {
+  P3Bufs b;
+  size_t words;
+};
+static P3Carve carve_scratch(const P3Shape& s, size_t G, u64* base) {
   const size_t n = (size_t)1 << s.k, N2 = (size_t)1 << s.L, W = s.W, Q2 = 2 * (size_t)s.Q;
-  // run_group's carve-up: state, header; tvals, tcoef, tmp, qv, qcoef over n; tlde, qlde, two trees, layers, layer trees over N2
-  return (sizeof(P3State) + 7) / 8 + s.hdr_stride + (2 * W + std::max(W, Q2) + 2 * Q2) * n + (W + Q2 + 8 + 8 + 4 + 8) * N2;
+  P3Carve c{};
+  auto take = [&](size_t words) {
+    u64* r = base ? base + c.words : nullptr;
+    c.words += words;
+    return r;
+  };
+  static_assert(sizeof(P3State) % 8 == 0, "P3State is an array of words");
+  c.b.state = reinterpret_cast<P3State*>(take(G * (sizeof(P3State) / 8)));
+  c.b.hdr = take(G * s.hdr_stride);
+  c.b.tvals = take(G * W * n);
+  c.b.tmp = take(G * std::max(W, Q2) * n);
+  c.b.tcoef = take(G * W * n);
+  c.b.qv = take(G * Q2 * n);
+  c.b.qcoef = take(G * Q2 * n);
+  c.b.tlde = take(G * W * N2);
+  c.b.qlde = take(G * Q2 * N2);
+  c.b.ttree = take(G * 8 * N2);
+  c.b.qtree = take(G * 8 * N2);
+  c.b.layers = take(G * 4 * N2);
+  c.b.ftrees = take(G * 8 * N2);
+  return c;
 }
+size_t P3ProverDev::scratch_words_per_proof() const { return carve_scratch(shape_, 1, nullptr).words; }
 size_t P3ProverDev::group_size(size_t n_proofs) const {
   size_t g = budget_bytes_ / (scratch_words_per_proof() * 8);
   g = std::max<size_t>(1, std::min<size_t>(g, 4096));
@@ -200,7 +225,7 @@ void P3ProverDev::ensure_impl() {
     P25_HIP(hipMemcpy(im->prog.p, prog_.instr.data(), prog_.instr.size() * sizeof(P3Instr), hipMemcpyHostToDevice));
     P25_HIP(hipMemcpy(im->consts.p, prog_.consts.data(), prog_.consts.size() * 8, hipMemcpyHostToDevice));
     P25_HIP(hipMemcpy(im->zfirst.p, zfirst_inv_.data(), zfirst_inv_.size() * 8, hipMemcpyHostToDevice));
-    P25_HIP(hipEventCreateWithFlags(&im->done, hipEventDisableTiming));
+    im->done.create(hipEventDisableTiming);
     impl_ = im.release();
   }
 }
@@ -210,10 +235,9 @@ void P3ProverDev::prove_dev(const u64* d_traces, size_t trace_stride, size_t n_p
   if (!n_proofs) return;
   ensure_impl();
   const size_t G = group_size(n_proofs), need = G * scratch_words_per_proof();
-  if (impl_->scratch.words < need) {   // as verify_scratch_ (verify.hip): 0 words after a failed growth, so the next call allocates
+  if (impl_->scratch.words < need) {
     sync();   // an earlier call may still be using the old allocation
-    impl_->scratch = DevMem();
-    impl_->scratch = DevMem(need);
+    impl_->scratch.regrow(need);
   }
   // the scratch is one region: wait, on the device, for the call before, whichever stream it went to; and leave the
   // record for the next call behind whatever this one managed to enqueue, also when it throws half way
@@ -234,28 +258,10 @@ void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, uint32_t G
   const int k = s.k, B = s.B;
   const size_t n = (size_t)1 << k, N2 = (size_t)1 << s.L, W = s.W, Q = s.Q, Q2 = 2 * Q;
   NttTables& tb = impl_->tables;
-  // scratch of the group
-  P3Bufs b{};
-  u64* p = impl_->scratch.p;
-  auto take = [&](size_t words) {
-    u64* r = p;
-    p += words;
-    return r;
-  };
-  b.state = reinterpret_cast<P3State*>(take(G * ((sizeof(P3State) + 7) / 8)));
-  static_assert(sizeof(P3State) % 8 == 0, "P3State is an array of words");
-  b.hdr = take(G * s.hdr_stride);
-  b.tvals = take(G * W * n);
-  b.tmp = take(G * std::max(W, Q2) * n);
-  b.tcoef = take(G * W * n);
-  b.qv = take(G * Q2 * n);
-  b.qcoef = take(G * Q2 * n);
-  b.tlde = take(G * W * N2);
-  b.qlde = take(G * Q2 * N2);
-  b.ttree = take(G * 8 * N2);
-  b.qtree = take(G * 8 * N2);
-  b.layers = take(G * 4 * N2);
-  b.ftrees = take(G * 8 * N2);
+  const P3Carve carve = carve_scratch(s, G, impl_->scratch.p);
+  if (carve.words != G * scratch_words_per_proof() || carve.words > impl_->scratch.words)
+    throw std::logic_error("p3 device prover: a group's scratch is out of step with the per-proof figure");
+  P3Bufs b = carve.b;
   b.prog = reinterpret_cast<const P3Instr*>(impl_->prog.p);
   b.consts = impl_->consts.p;
   b.zfirst_inv = impl_->zfirst.p;
@@ -303,8 +309,7 @@ void P3ProverDev::prove_host(const u64* traces, size_t n_proofs, const u64* pow_
   if (!n_proofs) return;
   const size_t tw = trace_words(), ni = num_inputs();
   ensure_impl();
-  if (!impl_->own_stream) P25_HIP(hipStreamCreateWithFlags(&impl_->own_stream, hipStreamNonBlocking));
-  hipStream_t st = impl_->own_stream;
+  hipStream_t st = impl_->host_stream();
   DevMem d_traces(n_proofs * tw), d_pow(n_proofs), d_out(n_proofs * ni), d_status((n_proofs + 1) / 2);
   P25_HIP(hipMemcpyAsync(d_traces.p, traces, n_proofs * tw * 8, hipMemcpyHostToDevice, st));
   if (pow_starts) P25_HIP(hipMemcpyAsync(d_pow.p, pow_starts, n_proofs * 8, hipMemcpyHostToDevice, st));

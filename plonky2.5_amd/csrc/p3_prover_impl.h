@@ -10,15 +10,15 @@ struct P3ProverImpl {
   NttTables tables;
   DevMem prog, consts, zfirst, scratch;
   DevMem vscratch;   // the verifier's: challenge blocks and folded values (p3_verify_dev.hip)
-  hipStream_t own_stream = nullptr;
+  DevStream own_stream;   // the host entry points' (prove_host, verify_host): created by the first of them
   // Recorded behind the last launch of every compute call.  The next call's stream waits for it before it touches the
   // scratch, so calls on different streams take the one scratch region in turn; each call's record sits behind its wait
   // for the call before, so the latest record covers everything the prover has enqueued.
-  hipEvent_t done = nullptr;
+  DevEvent done;
   bool recorded = false;
-  ~P3ProverImpl() {
-    if (done) (void)hipEventDestroy(done);
-    if (own_stream) (void)hipStreamDestroy(own_stream);
+  hipStream_t host_stream() {
+    if (!own_stream) own_stream = DevStream(hipStreamNonBlocking);
+    return own_stream;
   }
 };
 

@@ -60,10 +60,9 @@ void P3ProverDev::verify_dev(const u64* d_inputs, size_t n_proofs, size_t input_
   a.zfirst_inv = impl_->zfirst.p;
 
   const size_t C = verify_chunk(n_proofs), per = verify_scratch_words_per_proof(), need = C * per;
-  if (impl_->vscratch.words < need) {   // as the prover's: 0 words after a failed growth, so the next call allocates
+  if (impl_->vscratch.words < need) {
     sync();   // an earlier call may still be using the old allocation
-    impl_->vscratch = DevMem();
-    impl_->vscratch = DevMem(need);
+    impl_->vscratch.regrow(need);
   }
   // one buffer: wait, on the device, for the handle's call before, whichever stream it went to (also a proving call whose
   // proofs these may be); chunks follow each other on `st`
@@ -85,8 +84,7 @@ void P3ProverDev::verify_host(const u64* inputs, size_t n_proofs, size_t input_s
   if (!n_proofs) return;
   const size_t ni = num_inputs();
   ensure_impl();
-  if (!impl_->own_stream) P25_HIP(hipStreamCreateWithFlags(&impl_->own_stream, hipStreamNonBlocking));
-  hipStream_t st = impl_->own_stream;
+  hipStream_t st = impl_->host_stream();
   DevMem d_in(n_proofs * ni), d_status((n_proofs + 1) / 2);
   // the input_stride - num_inputs words behind a proof stay on the host: they are not read
   P25_HIP(hipMemcpy2DAsync(d_in.p, ni * 8, inputs, input_stride * 8, ni * 8, n_proofs, hipMemcpyHostToDevice, st));

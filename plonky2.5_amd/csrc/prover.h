@@ -23,18 +23,6 @@ struct ProofLayout {
 };
 ProofLayout make_proof_layout(const Circuit& c);
 
-struct DevMem {  // owning device allocation
-  u64* p = nullptr;
-  size_t words = 0;
-  DevMem() {}
-  explicit DevMem(size_t w);
-  ~DevMem();
-  DevMem(DevMem&& o) noexcept : p(o.p), words(o.words) { o.p = nullptr; }
-  DevMem& operator=(DevMem&& o) noexcept;
-  DevMem(const DevMem&) = delete;
-  DevMem& operator=(const DevMem&) = delete;
-};
-
 // FRI working set and shape: shared by the whole-proof pipeline and the standalone p25_fri_prove entry point.
 struct FriWork {
   DevMem coeffs[9], vals[9], tree[9];
@@ -143,14 +131,21 @@ class DeviceCircuit {
 
  private:
   struct Ctx;  // per-proof working set
-  void prove_one(Ctx& cx, int buf, size_t B, uint32_t p, u64* d_proof, uint32_t* d_status, PhaseTimes* t);
+  // A witness pass as its proofs see it: value buffer vals_[buf] holding `batch` proofs (the slot stride), and whether
+  // the call keeps one proof in flight only (latency-oriented kernel forms).
+  struct Pass {
+    int buf;
+    size_t batch;
+    bool single_proof;
+  };
+  void prove_one(Ctx& cx, const Pass& pass, uint32_t p, u64* d_proof, uint32_t* d_status, PhaseTimes* t);
   void enqueue_partial_products(Ctx& cx, hipStream_t st);
   // alpha_table: launch the alpha-power table kernel first (prove_one gets the table from its transcript launch)
   void enqueue_quotient(Ctx& cx, hipStream_t st, bool alpha_table = true);
   void set_challenges(Ctx& cx, const u64* betas, const u64* gammas, const u64* alphas);
   size_t ctx_bytes() const;
   void ensure_ctx(size_t count);
-  void ensure_vals(int buf, size_t batch);
+  void ensure_vals(int buf, size_t batch);   // vals_[buf] holds at least `batch` proofs
 
   MainStreamLease main_lease_;   // first member: given back also when the constructor throws further down
   Circuit c_;
@@ -163,21 +158,20 @@ class DeviceCircuit {
   QuotientArgs qa_proto_;
   hipStream_t stream_ = nullptr;
   std::vector<std::unique_ptr<Ctx>> ctxs_;   // proofs in flight: one working set + HIP stream each
-  hipEvent_t ev_witness_[2] = {nullptr, nullptr};  // witness pass into vals_[b] finished
-  hipEvent_t ev_ext_ = nullptr, ev_main_ = nullptr;  // stream_join / wait_stream
-  std::vector<hipEvent_t> marks_[MAX_MARKS];         // mark(slot): [0] the main stream, [1 + k] proving stream k
-  size_t marks_recorded_[MAX_MARKS] = {0};           // how many of them the latest mark(slot) recorded
+  DevEvent ev_witness_[2];                  // witness pass into vals_[b] finished
+  DevEvent ev_ext_, ev_main_;               // stream_join / wait_stream
+  std::vector<DevEvent> marks_[MAX_MARKS];  // mark(slot): [0] the main stream, [1 + k] proving stream k
+  size_t marks_recorded_[MAX_MARKS] = {0};  // how many of them the latest mark(slot) recorded
   int streams_ = 16;
   size_t pool_first_ = 0;      // this circuit's first position in the process-wide stream pool (prover.hip)
-  bool single_proof_ = false;  // set per prove call: one proof in flight -> latency-oriented kernel forms
+  bool pool_reserved_ = false; // ... taken once, by the first ensure_ctx, whether or not its context then came to be
   DevMem vals_[2];             // witness values of a pass, slot-major [slot][proof of the pass]; double-buffered
-  size_t vals_batch_[2] = {0, 0};
   size_t pass_counter_ = 0;    // witness passes issued so far (parity = buffer)
   size_t proof_counter_ = 0;   // proofs handed to the contexts so far (inflight.h: ctx_for_proof)
   std::vector<DevMem> owned_;
   DevMem verify_scratch_;      // verify_batch_dev: challenge blocks and vanishing partials of a batch, caller's verifier data
   bool kstats_on_ = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> kstats_pending_, kstats_free_;
+  std::vector<std::pair<DevEvent, DevEvent>> kstats_pending_, kstats_free_;
   double kstats_ms_ = 0;
   u64 kstats_launches_ = 0;
 };

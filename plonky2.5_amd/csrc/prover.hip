@@ -90,22 +90,6 @@ MainStreamLease::~MainStreamLease() {
   if (slot >= 0) g_stream_pool.main_release(*this);
 }
 
-DevMem::DevMem(size_t w) : words(w) {
-  if (w) P25_HIP(hipMalloc(&p, w * sizeof(u64)));
-}
-DevMem::~DevMem() {
-  if (p) (void)hipFree(p);
-}
-DevMem& DevMem::operator=(DevMem&& o) noexcept {
-  if (this != &o) {
-    if (p) (void)hipFree(p);
-    p = o.p;
-    words = o.words;
-    o.p = nullptr;
-  }
-  return *this;
-}
-
 static uint32_t final_poly_len(const Circuit& c) {
   int db = c.degree_bits;
   for (int a : c.fri_reduction_arity_bits) db -= a;
@@ -252,20 +236,55 @@ struct DeviceCircuit::Ctx {
   DevMem fri_comp, fri_scan;
   FriWork fri;
   DevMem proof, status;
-  hipEvent_t ev[12];
-  hipStream_t st = nullptr;   // a stream of the process-wide pool (never destroyed)
+  DevEvent ev[12];             // PhaseTimes marks
+  hipStream_t st = nullptr;    // a stream of the process-wide pool (never destroyed)
   // done[b]: recorded after the context's latest read of witness-value buffer b (DeviceCircuit::vals_[b])
-  hipEvent_t done[2] = {nullptr, nullptr};
-  hipEvent_t join = nullptr;   // DeviceCircuit::stream_join
-  bool have_events = false;
-  ~Ctx() {
-    if (have_events)
-      for (auto& e : ev) (void)hipEventDestroy(e);
-    for (auto& e : done)
-      if (e) (void)hipEventDestroy(e);
-    if (join) (void)hipEventDestroy(join);
-  }
+  DevEvent done[2];
+  DevEvent join;               // DeviceCircuit::stream_join: created by its first call
+  // Everything a context owns: a constructor that throws half way gives back what it had made.
+  Ctx(const DeviceCircuit& dc, hipStream_t stream);
 };
+
+DeviceCircuit::Ctx::Ctx(const DeviceCircuit& dc, hipStream_t stream) : st(stream) {
+  const Circuit& c = dc.c_;
+  const ProofLayout& L = dc.layout_;
+  for (auto& e : done) e.create(hipEventDisableTiming);
+  const size_t n = c.degree(), B = dc.big();
+  const int W = c.cfg.num_wires, NC = c.cfg.num_challenges, NP = c.num_partial_products;
+  const int nz = NC * (1 + NP), nq = NC * c.cfg.max_quotient_degree_factor;
+  const size_t tw = merkle_tree_words(B, c.cfg.cap_height);
+  wires_vals = DevMem((size_t)W * n);
+  wires_coeffs = DevMem((size_t)W * n);
+  tmp = DevMem((size_t)W * n);
+  wires_lde = DevMem((size_t)W * B);
+  wires_tree = DevMem(tw);
+  zs_vals = DevMem((size_t)nz * n);
+  zs_coeffs = DevMem((size_t)nz * n);
+  zs_lde = DevMem((size_t)nz * B);
+  zs_tree = DevMem(tw);
+  zpp_chunk = DevMem((size_t)NC * (NP + 1) * n);
+  zpp_tot = DevMem((size_t)NC * n);
+  zpp_btot = DevMem((size_t)NC * ((n + 255) / 256) + 16);
+  q_vals = DevMem((size_t)NC * B);
+  q_tmp = DevMem((size_t)NC * B);
+  q_coeffs = DevMem((size_t)NC * B);
+  q_lde = DevMem((size_t)nq * B);
+  q_tree = DevMem(tw);
+  preamble = DevMem(8);
+  P25_HIP(hipMemcpy(preamble.p, dc.preamble_.p, 64, hipMemcpyDeviceToDevice));  // digest | hash_no_pad([]) = zeros
+  transcript = DevMem(sizeof(Transcript) / 8 + 1);
+  chal = DevMem(CH_WORDS);
+  alpha_pows = DevMem(2 * ALPHA_POWS);
+  // the power tables of zeta and g zeta, followed by the per-chunk partial sums of the openings (launch_eval_jobs)
+  eval_pows = DevMem(eval_scratch_words(2, (size_t)L.oracle_width[0] + W + nz + nq + NC, (uint32_t)c.degree_bits));
+  fri_comp = DevMem(4 * n);
+  const size_t total_polys = L.oracle_width[0] + L.oracle_width[1] + L.oracle_width[2] + L.oracle_width[3];
+  fri_scan = DevMem(2 * (total_polys + 1) + 8 * (n + 1) + 4 * ((n + 255) / 256) + 64);
+  fri.alloc(c.degree_bits, c.cfg.rate_bits, c.cfg.cap_height, c.fri_reduction_arity_bits);
+  proof = DevMem(L.total);
+  status = DevMem(1);
+  for (auto& e : ev) e.create();
+}
 
 DeviceCircuit::DeviceCircuit(Circuit c) : c_(std::move(c)) {
   if (c_.cfg.num_challenges != 2 || c_.cfg.rate_bits > 3 || c_.gates.size() > 16)
@@ -400,18 +419,6 @@ DeviceCircuit::~DeviceCircuit() {
   for (auto& c : ctxs_)
     if (c->st) (void)hipStreamSynchronize(c->st);
   if (stream_) (void)hipStreamSynchronize(stream_);
-  ctxs_.clear();
-  for (auto& e : ev_witness_)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& v : marks_)
-    for (auto& e : v) (void)hipEventDestroy(e);
-  if (ev_ext_) (void)hipEventDestroy(ev_ext_);
-  if (ev_main_) (void)hipEventDestroy(ev_main_);
-  for (auto* v : {&kstats_pending_, &kstats_free_})
-    for (auto& pr : *v) {
-      (void)hipEventDestroy(pr.first);
-      (void)hipEventDestroy(pr.second);
-    }
 }
 
 void DeviceCircuit::commitment_to_host(std::vector<u64>& coeffs, std::vector<u64>& lde, std::vector<u64>& tree) {
@@ -425,62 +432,25 @@ void DeviceCircuit::commitment_to_host(std::vector<u64>& coeffs, std::vector<u64
 }
 
 void DeviceCircuit::ensure_ctx(size_t count) {
-  for (auto& e : ev_witness_)
-    if (!e) P25_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& e : ev_witness_) e.ensure(hipEventDisableTiming);
   while (ctxs_.size() < count) {
-  ctxs_.emplace_back(new Ctx());
-  Ctx& x = *ctxs_.back();
-  if (ctxs_.size() == 1) pool_first_ = g_stream_pool.reserve(count, (size_t)streams_);
-  else g_stream_pool.widen((size_t)streams_);
-  x.st = g_stream_pool.at(pool_first_ + ctxs_.size() - 1);
-  for (auto& e : x.done) P25_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  const size_t n = c_.degree(), B = big();
-  const int W = c_.cfg.num_wires, NC = c_.cfg.num_challenges, NP = c_.num_partial_products;
-  const int nz = NC * (1 + NP), nq = NC * c_.cfg.max_quotient_degree_factor;
-  const size_t tw = merkle_tree_words(B, c_.cfg.cap_height);
-  x.wires_vals = DevMem((size_t)W * n);
-  x.wires_coeffs = DevMem((size_t)W * n);
-  x.tmp = DevMem((size_t)W * n);
-  x.wires_lde = DevMem((size_t)W * B);
-  x.wires_tree = DevMem(tw);
-  x.zs_vals = DevMem((size_t)nz * n);
-  x.zs_coeffs = DevMem((size_t)nz * n);
-  x.zs_lde = DevMem((size_t)nz * B);
-  x.zs_tree = DevMem(tw);
-  x.zpp_chunk = DevMem((size_t)NC * (NP + 1) * n);
-  x.zpp_tot = DevMem((size_t)NC * n);
-  x.zpp_btot = DevMem((size_t)NC * ((n + 255) / 256) + 16);
-  x.q_vals = DevMem((size_t)NC * B);
-  x.q_tmp = DevMem((size_t)NC * B);
-  x.q_coeffs = DevMem((size_t)NC * B);
-  x.q_lde = DevMem((size_t)nq * B);
-  x.q_tree = DevMem(tw);
-  x.preamble = DevMem(8);
-  P25_HIP(hipMemcpy(x.preamble.p, preamble_.p, 64, hipMemcpyDeviceToDevice));  // digest | hash_no_pad([]) = zeros
-  x.transcript = DevMem(sizeof(Transcript) / 8 + 1);
-  x.chal = DevMem(CH_WORDS);
-  x.alpha_pows = DevMem(2 * ALPHA_POWS);
-  {
-    // the power tables of zeta and g zeta, followed by the per-chunk partial sums of the openings (launch_eval_jobs)
-    x.eval_pows = DevMem(eval_scratch_words(2, (size_t)layout_.oracle_width[0] + W + nz + nq + NC, (uint32_t)c_.degree_bits));
-  }
-  x.fri_comp = DevMem(4 * n);
-  size_t total_polys = layout_.oracle_width[0] + layout_.oracle_width[1] + layout_.oracle_width[2] + layout_.oracle_width[3];
-  x.fri_scan = DevMem(2 * (total_polys + 1) + 8 * (n + 1) + 4 * ((n + 255) / 256) + 64);
-  x.fri.alloc(c_.degree_bits, c_.cfg.rate_bits, c_.cfg.cap_height, c_.fri_reduction_arity_bits);
-  x.proof = DevMem(layout_.total);
-  x.status = DevMem(1);
-  for (auto& e : x.ev) P25_HIP(hipEventCreate(&e));
-  x.have_events = true;
+    if (!pool_reserved_) {
+      pool_first_ = g_stream_pool.reserve(count, (size_t)streams_);
+      pool_reserved_ = true;
+    } else {
+      g_stream_pool.widen((size_t)streams_);
+    }
+    // built first, appended only whole: a growth that fails leaves the circuit with the contexts it had
+    std::unique_ptr<Ctx> x(new Ctx(*this, g_stream_pool.at(pool_first_ + ctxs_.size())));
+    ctxs_.push_back(std::move(x));
   }
 }
 
 void DeviceCircuit::ensure_vals(int buf, size_t batch) {
-  if (batch <= vals_batch_[buf]) return;
+  const size_t need = (size_t)wp_.num_slots * batch;
+  if (need <= vals_[buf].words) return;
   sync();  // nothing in flight may still read the old allocation
-  vals_[buf] = DevMem();
-  vals_[buf] = DevMem((size_t)wp_.num_slots * batch);
-  vals_batch_[buf] = batch;
+  vals_[buf].regrow(need);
 }
 
 void DeviceCircuit::sync() {
@@ -490,11 +460,11 @@ void DeviceCircuit::sync() {
 
 void DeviceCircuit::stream_join(hipStream_t ext) {
   // one event per proving stream: a context's `join` event is re-recorded here, after the stream's latest work
-  if (!ev_main_) P25_HIP(hipEventCreateWithFlags(&ev_main_, hipEventDisableTiming));
+  ev_main_.ensure(hipEventDisableTiming);
   P25_HIP(hipEventRecord(ev_main_, stream_));
   P25_HIP(hipStreamWaitEvent(ext, ev_main_, 0));
   for (auto& c : ctxs_) {
-    if (!c->join) P25_HIP(hipEventCreateWithFlags(&c->join, hipEventDisableTiming));
+    c->join.ensure(hipEventDisableTiming);
     P25_HIP(hipEventRecord(c->join, c->st));
     P25_HIP(hipStreamWaitEvent(ext, c->join, 0));
   }
@@ -502,7 +472,7 @@ void DeviceCircuit::stream_join(hipStream_t ext) {
 void DeviceCircuit::wait_stream(hipStream_t ext) {
   // the main stream waits; every proving stream waits for a witness event the main stream records AFTER this point
   // before it touches a proof of a later call
-  if (!ev_ext_) P25_HIP(hipEventCreateWithFlags(&ev_ext_, hipEventDisableTiming));
+  ev_ext_.ensure(hipEventDisableTiming);
   P25_HIP(hipEventRecord(ev_ext_, ext));
   P25_HIP(hipStreamWaitEvent(stream_, ev_ext_, 0));
 }
@@ -511,9 +481,9 @@ void DeviceCircuit::mark(int slot) {
   if (slot < 0 || slot >= MAX_MARKS) throw std::invalid_argument("mark slot out of range");
   auto& ev = marks_[slot];
   while (ev.size() < 1 + ctxs_.size()) {
-    hipEvent_t e = nullptr;
-    P25_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ev.push_back(e);
+    DevEvent e;
+    e.create(hipEventDisableTiming);
+    ev.push_back(std::move(e));
   }
   P25_HIP(hipEventRecord(ev[0], stream_));
   for (size_t k = 0; k < ctxs_.size(); k++) P25_HIP(hipEventRecord(ev[1 + k], ctxs_[k]->st));
@@ -536,7 +506,7 @@ void DeviceCircuit::kernel_stats(double* ms, u64* launches, bool reset) {
     P25_HIP(hipEventElapsedTime(&t, pr.first, pr.second));
     kstats_ms_ += t;
     kstats_launches_++;
-    kstats_free_.push_back(pr);
+    kstats_free_.push_back(std::move(pr));
   }
   kstats_pending_.clear();
   if (ms) *ms = kstats_ms_;
@@ -548,8 +518,10 @@ void DeviceCircuit::kernel_stats(double* ms, u64* launches, bool reset) {
 }
 
 // One proof, fully enqueued on the stream; no host synchronisation inside.
-void DeviceCircuit::prove_one(Ctx& x, int buf, size_t Bstride, uint32_t p, u64* d_proof,
-                              uint32_t* d_status, PhaseTimes* t) {
+void DeviceCircuit::prove_one(Ctx& x, const Pass& pass, uint32_t p, u64* d_proof, uint32_t* d_status, PhaseTimes* t) {
+  const int buf = pass.buf;
+  const size_t Bstride = pass.batch;
+  const bool single_proof = pass.single_proof;
   const u64* d_vals = vals_[buf].p;
   hipStream_t st = x.st;
   const size_t n = c_.degree(), B = big();
@@ -595,17 +567,19 @@ void DeviceCircuit::prove_one(Ctx& x, int buf, size_t Bstride, uint32_t p, u64* 
   {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (kstats_on_) {
+      std::pair<DevEvent, DevEvent> pr;
       if (kstats_free_.empty()) {
-        P25_HIP(hipEventCreate(&e0));
-        P25_HIP(hipEventCreate(&e1));
+        pr.first.create();
+        pr.second.create();
       } else {
-        e0 = kstats_free_.back().first;
-        e1 = kstats_free_.back().second;
+        pr = std::move(kstats_free_.back());
         kstats_free_.pop_back();
       }
-      kstats_pending_.push_back({e0, e1});
+      e0 = pr.first;
+      e1 = pr.second;
+      kstats_pending_.push_back(std::move(pr));
     }
-    launch_merkle_tree(x.wires_lde.p, B, W, B, cap_h, x.wires_tree.p, st, e0, e1, single_proof_);
+    launch_merkle_tree(x.wires_lde.p, B, W, B, cap_h, x.wires_tree.p, st, e0, e1, single_proof);
   }
   const u64* wires_cap = x.wires_tree.p + tw - capw;
   observe_cap(wires_cap, L.wires_cap, chal + CH_BETAS, 2 * NC, TR_CLOSE_NONE, 0, nullptr, true);  // preamble first; betas, gammas
@@ -615,7 +589,7 @@ void DeviceCircuit::prove_one(Ctx& x, int buf, size_t Bstride, uint32_t p, u64* 
   mark();  // 3
   // "commit to partial products, Z's"
   ntt_inverse_then_lde(tables_, x.zs_vals.p, n, x.tmp.p, n, x.zs_coeffs.p, n, x.zs_lde.p, B, db, rb, nz, gl::GENERATOR, st);
-  launch_merkle_tree(x.zs_lde.p, B, nz, B, cap_h, x.zs_tree.p, st, nullptr, nullptr, single_proof_);
+  launch_merkle_tree(x.zs_lde.p, B, nz, B, cap_h, x.zs_tree.p, st, nullptr, nullptr, single_proof);
   const u64* zs_cap = x.zs_tree.p + tw - capw;
   // alphas; the same wave writes the quotient kernel's alpha-power table (NC = 2: checked by the constructor)
   observe_cap(zs_cap, L.zs_cap, chal + CH_ALPHAS, NC, TR_CLOSE_ALPHA_POWS, 0, x.alpha_pows.p);
@@ -625,7 +599,7 @@ void DeviceCircuit::prove_one(Ctx& x, int buf, size_t Bstride, uint32_t p, u64* 
   mark();  // 5
   // "split up quotient polys" (chunks of n are contiguous: [NC][8][n] == [16][n]) + "commit to quotient polys"
   ntt_lde_bitrev(tables_, x.q_coeffs.p, n, x.q_lde.p, B, db, rb, nq, gl::GENERATOR, st);
-  launch_merkle_tree(x.q_lde.p, B, nq, B, cap_h, x.q_tree.p, st, nullptr, nullptr, single_proof_);
+  launch_merkle_tree(x.q_lde.p, B, nq, B, cap_h, x.q_tree.p, st, nullptr, nullptr, single_proof);
   const u64* q_cap = x.q_tree.p + tw - capw;
   observe_cap(q_cap, L.quotient_cap, chal + CH_ZETA, 2, TR_CLOSE_CHECK_ZETA, (uint32_t)db, nullptr);  // zeta, not in the subgroup
   mark();  // 6
@@ -682,7 +656,7 @@ void DeviceCircuit::prove_one(Ctx& x, int buf, size_t Bstride, uint32_t p, u64* 
     }
     FriShape sh{db, rb, cap_h, c_.fri_reduction_arity_bits, c_.cfg.proof_of_work_bits, c_.cfg.num_query_rounds};
     FriOffsets fo{L.fri_caps, L.final_poly, L.pow_witness, L.queries, L.query_stride};
-    fri_commit_pow_query(tables_, x.fri, sh, tr, chal, qy, d_proof, fo, d_status, st, single_proof_);
+    fri_commit_pow_query(tables_, x.fri, sh, tr, chal, qy, d_proof, fo, d_status, st, single_proof);
   }
   mark();  // 8
   P25_HIP(hipGetLastError());
@@ -915,7 +889,7 @@ void fri_prove_standalone(NttTables& tables, const u64* coeffs, const FriShape& 
 // parallel ACROSS proofs), then each proof's commit/quotient/FRI pipeline on one of K streams so that
 // the latency-bound stretches of one proof (transcript, Merkle-cap levels, FRI tail) overlap with the
 // throughput-bound kernels of the others.
-// Approximate device bytes of one proof context (see ensure_ctx): the LDE matrices dominate.
+// Approximate device bytes of one proof context (see Ctx::Ctx): the LDE matrices dominate.
 size_t DeviceCircuit::ctx_bytes() const {
   const size_t n = c_.degree(), B = (size_t)1 << (c_.degree_bits + c_.cfg.rate_bits);
   const size_t W = c_.cfg.num_wires, NC = c_.cfg.num_challenges, NP = c_.num_partial_products;
@@ -938,7 +912,7 @@ void DeviceCircuit::prove_batch_dev(const u64* d_inputs, size_t n_proofs, const 
       const size_t pass = n_proofs < 64 ? n_proofs : 64;
       size_t vals_need = 0;
       for (int b = 0; b < (n_proofs > 64 ? 2 : 1); b++)
-        if (pass > vals_batch_[b]) vals_need += (size_t)wp_.num_slots * pass * 8;
+        if ((size_t)wp_.num_slots * pass > vals_[b].words) vals_need += (size_t)wp_.num_slots * pass * 8;
       const size_t reserve = total_b / 20;
       const size_t avail = free_b > vals_need + reserve ? free_b - vals_need - reserve : 0;
       size_t fit = ctxs_.size() + avail / ctx_bytes();
@@ -947,7 +921,6 @@ void DeviceCircuit::prove_batch_dev(const u64* d_inputs, size_t n_proofs, const 
     }
   }
   ensure_ctx(K);   // K: what the clamp granted; it is the modulus of the assignment below
-  single_proof_ = K == 1;  // a lone proof in flight: latency-oriented kernel forms
   // Witness generation runs for up to 64 proofs per pass on the main stream into one of TWO value buffers, so the
   // pass for proofs [k+64, k+128) runs underneath the proving pipelines of [k, k+64): a context stream only waits for
   // the witness event of its own pass, and the main stream only waits -- before it overwrites buffer b -- for the
@@ -958,12 +931,13 @@ void DeviceCircuit::prove_batch_dev(const u64* d_inputs, size_t n_proofs, const 
     size_t bsz = n_proofs - base < MAXB ? n_proofs - base : MAXB;
     const int buf = (int)((pass_counter_ + pass) & 1);
     ensure_vals(buf, bsz);
+    const Pass ps{buf, bsz, K == 1};   // a lone proof in flight: latency-oriented kernel forms
     for (auto& c : ctxs_) P25_HIP(hipStreamWaitEvent(stream_, c->done[buf], 0));
     P25_HIP(hipMemsetAsync(d_status + base, 0, bsz * 4, stream_));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevEvent e0, e1;
     if (times) {
-      P25_HIP(hipEventCreate(&e0));
-      P25_HIP(hipEventCreate(&e1));
+      e0.create();
+      e1.create();
       P25_HIP(hipEventRecord(e0, stream_));
     }
     launch_witgen(wp_, d_inputs, d_seeds + base, vals_[buf].p, bsz, (uint32_t)bsz, d_status + base,
@@ -976,8 +950,6 @@ void DeviceCircuit::prove_batch_dev(const u64* d_inputs, size_t n_proofs, const 
       P25_HIP(hipEventElapsedTime(&ms, e0, e1));
       times->witness += ms;
       times->total += ms;
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
     }
     // Proof p of the pass goes to context (proof_counter_ + p) mod K (inflight.h): the start rotates from pass to pass, so a
     // short pass touches a rotated subset of the contexts.  The first K proofs of a pass land on K different contexts:
@@ -985,7 +957,7 @@ void DeviceCircuit::prove_batch_dev(const u64* d_inputs, size_t n_proofs, const 
     for (size_t p = 0; p < bsz; p++) {
       Ctx& x = *ctxs_[ctx_for_proof(proof_counter_ + p, K)];
       if (p < K) P25_HIP(hipStreamWaitEvent(x.st, ev_witness_[buf], 0));
-      prove_one(x, buf, bsz, (uint32_t)p, d_proofs + (base + p) * proof_stride, d_status + base + p, times);
+      prove_one(x, ps, (uint32_t)p, d_proofs + (base + p) * proof_stride, d_status + base + p, times);
     }
     proof_counter_ += bsz;
   }

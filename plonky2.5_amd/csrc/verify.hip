@@ -99,8 +99,7 @@ void DeviceCircuit::verify_batch_dev(const u64* digest4, const u64* cs_cap, cons
   const size_t need = vd_words + n_proofs * (VCH_WORDS + part_words);
   if (verify_scratch_.words < need) {
     sync();   // an earlier batch may still be using the old allocation
-    verify_scratch_ = DevMem();
-    verify_scratch_ = DevMem(need);
+    verify_scratch_.regrow(need);
   }
   a.proofs = d_proofs;
   a.stride = proof_stride;

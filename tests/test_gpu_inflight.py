@@ -131,3 +131,36 @@ def test_two_circuits_interleave_batches_on_the_shared_pool(gpu, oracle, ref):
         assert not bad, (name, bad[:8])
         c.close()
 
+
+def test_one_live_circuit_grows_from_1_to_3_to_24_contexts(gpu, ref):
+    """set_streams(1) and 1 proof, set_streams(3) and 5, set_streams(24) and 25, on one circuit that is never closed in
+    between: its contexts are built 0 -> 1 -> 3 -> 24 beside the ones already proving, and its share of the stream pool
+    is reserved once and widened twice.  Every proof is the oracle's for its seed."""
+    c = gpu.Circuit.build_gadget(ref["kind"], ref["param"])
+    try:
+        for step, (depth, n) in enumerate([(1, 1), (3, 5), (24, 25)]):
+            c.set_streams(depth)
+            seeds = _seeds(n, step)
+            proofs, st = c.prove(np.stack([ref["inp"]] * n), seeds=seeds)
+            assert st.tolist() == [0] * n, (depth, n)
+            bad = [i for i in range(n) if (proofs[i] != ref["oracle"][seeds[i]]).any()]
+            assert not bad, f"depth {depth}: proofs {bad[:8]} differ from the oracle's"
+    finally:
+        c.close()
+
+
+def test_phase_timings_of_one_proof(gpu, ref):
+    """prove(timings=True): the proof is the oracle's, and the nine phase times (HIP events that live for the call or
+    belong to the context) are finite, non-negative, and none exceeds the total."""
+    c = gpu.Circuit.build_gadget(ref["kind"], ref["param"])
+    try:
+        proofs, st, tm = c.prove(ref["inp"][None, :], seeds=[3], timings=True)
+    finally:
+        c.close()
+    assert st.tolist() == [0]
+    assert (proofs[0] == ref["oracle"][3]).all()
+    t = tm.as_dict()
+    print("phase ms:", {k: round(v, 4) for k, v in t.items()})
+    assert len(t) == 9 and "total_ms" in t
+    assert all(np.isfinite(v) and v >= 0 for v in t.values()), t
+    assert all(t["total_ms"] >= v for v in t.values()), t

@@ -22,11 +22,15 @@
 //   kind 0 ("t-contiguous"): addr = t + imap(i) * NT
 //   kind 1 ("i-contiguous"): addr = tmap(t) * R + imap(i)
 // where imap/tmap are the identity or a bit reversal.  All values are canonical field elements.
+// A pass's kinds and reversals are template parameters of the kernel (its addressing FORM, ntt_index.h): a lane walks its
+// elements with a cursor that adds where the closed form would shift, reverse and multiply, and launch_ntt_pass picks
+// the instantiation -- one per form the library issues, nothing generic behind them.
 #include <mutex>
 #include <set>
 #include <tuple>
 #include "kernels.h"
 #include "ntt16.h"
+#include "ntt_index.h"
 
 // (Phase priorities -- load / store phases of k_ntt_tile above or below its butterflies -- were measured in round 4 and
 // change nothing: profiles/r04_ab_ntt_phase_priority.txt.)
@@ -67,188 +71,203 @@ __device__ __forceinline__ void dif_group(u64* col, const u64* wl, int step, int
 // the stage-by-stage factors w_R^(((k mod hk) << lstride + l) << (s0 + m)) of the radix-2 network split into the
 // 16th-root part (compile-time, above) and w_R^(l << (s0 + m)) on every difference branch, which accumulates to
 // w_R^((l * rev4(k')) << s0) at output k' -- 15 general multiplications per 16 elements instead of 32, none in the
-// last group of a sub-transform (l = 0).  `wl` holds w_R^e for e < R.
-template <bool INV>
+// last group of a sub-transform (l = 0).  `wl` holds w_R^e for e < R.  STEP > 0 is the column stride known at compile
+// time (the LDS accesses then take immediate offsets on one base); the 15 twiddle addresses are 15 additions of l << s0.
+template <bool INV, int STEP>
 __device__ __forceinline__ void dif16_group(u64* col, const u64* wl, int step, int l, int s0) {
+  const int st = STEP > 0 ? STEP : step;
   u64 x[16];
 #pragma unroll
-  for (int k = 0; k < 16; k++) x[k] = col[k * step];
+  for (int k = 0; k < 16; k++) x[k] = col[k * st];
   dft16<INV>(x);
   if (l != 0) {
+    const u64* wf[16];
+    wf[0] = wl;
+#pragma unroll
+    for (int f = 1; f < 16; f++) wf[f] = wf[f - 1] + (l << s0);
 #pragma unroll
     for (int k = 1; k < 16; k++) {
       const int f = ((k & 1) << 3) | ((k & 2) << 1) | ((k & 4) >> 1) | ((k & 8) >> 3);
-      x[k] = gl::mul_nc(x[k], wl[(l * f) << s0]);
+      x[k] = gl::mul_nc(x[k], *wf[f]);
     }
   }
 #pragma unroll
-  for (int k = 0; k < 16; k++) col[k * step] = x[k];
+  for (int k = 0; k < 16; k++) col[k * st] = x[k];
+}
+
+// One group of up to four DIF stages from stage s0 on, over the whole tile.
+template <bool INV, bool FULL, int STEP>
+__device__ __forceinline__ void dif_stages(u64* lds, const u64* wl, int log_r, int log_t, int s0, int g, int tid, int nth) {
+  const int T = 1 << log_t, TP = (int)nttix::row_pitch(log_t);
+  const int lstride = log_r - s0 - g;
+  const int items = T << (log_r - g);
+  for (int b = tid; b < items; b += nth) {
+    const int t = b & (T - 1), q = b >> log_t;
+    const int l = q & ((1 << lstride) - 1), h = q >> lstride;
+    u64* col = lds + ((h << (log_r - s0)) + l) * TP + t;
+    switch (g) {
+      case 4:
+        if (FULL)
+          dif16_group<INV, STEP>(col, wl, TP << lstride, l, s0);
+        else
+          dif_group<4>(col, wl, TP << lstride, l, lstride, s0);
+        break;
+      case 3: dif_group<3>(col, wl, TP << lstride, l, lstride, s0); break;
+      case 2: dif_group<2>(col, wl, TP << lstride, l, lstride, s0); break;
+      default: dif_group<1>(col, wl, TP << lstride, l, lstride, s0); break;
+    }
+  }
+  __syncthreads();
+}
+// The whole network of a tile whose shape is a template parameter: every count, stride and stage number is a constant.
+template <bool INV, int NTH, int LR, int LT, int S0>
+__device__ __forceinline__ void dif_network_static(u64* lds, const u64* wl, int tid) {
+  if constexpr (S0 < LR) {
+    constexpr int g = LR - S0 < 4 ? LR - S0 : 4;
+    constexpr int TP = LT ? (1 << LT) + 1 : 1;
+    dif_stages<INV, (LR <= 10), (g == 4 ? TP << (LR - S0 - g) : 0)>(lds, wl, LR, LT, S0, g, tid, NTH);
+    dif_network_static<INV, NTH, LR, LT, S0 + g>(lds, wl, tid);
+  }
+}
+
+// a word at a 32-bit word offset from a wave-uniform base: the scalar base + 32-bit lane offset form of the global access
+__device__ __forceinline__ u64 ld_w(const u64* base, u32 woff) {
+  return *reinterpret_cast<const u64*>(reinterpret_cast<const char*>(base) + (woff << 3));
+}
+__device__ __forceinline__ void st_w(u64* base, u32 woff, u64 v) {
+  *reinterpret_cast<u64*>(reinterpret_cast<char*>(base) + (woff << 3)) = v;
 }
 
 // PRE: how the input is pre-scaled -- 0 not at all, 1 by one table entry per element (a.pre), 2 by the product of two
 // factor-table entries (a.pre_t, a.pre_i).  A template parameter: as run-time branches in the load loop the three forms
 // cost the fib-64 shapes 8 % of the kernel (iNTT + LDE of 135 columns 0.95 -> 1.03 ms, round 4).
-template <bool INV, int NTH, int PRE>
+// IN, OUT, MUL (ntt_index.h) and LAZY (NttPass::lazy_out) are the pass's addressing form, compile-time for the same
+// reason: with both kinds evaluated and selected per element, and every position re-derived from the element number,
+// index work was 40 % of the kernel's instructions (profiles/r11_ntt_addressing.txt).  LR, LT >= 0: the tile shape
+// (log_r, log_t) as constants -- the 2^16-point shapes, R = 256, T = 16 in both passes -- or -1: read from the pass.
+template <bool INV, int NTH, int PRE, int IN, int OUT, int MUL, bool LAZY, int LR, int LT>
 __global__ __launch_bounds__(NTH) void k_ntt_tile(NttPass a) {
   P25_WAVE_PRIO(P25_PRIO_BULK);
   extern __shared__ u64 lds[];
-  const int R = 1 << a.log_r, T = 1 << a.log_t;
-  const int TP = T > 1 ? T + 1 : 1;  // row padding: conflict-free for both access directions
+  const int log_r = LR >= 0 ? LR : a.log_r, log_t = LT >= 0 ? LT : a.log_t;
+  const int R = 1 << log_r, T = 1 << log_t;
+  const int TP = (int)nttix::row_pitch(log_t);  // row padding: conflict-free for both access directions
+  const int TR = T * R;
   u64* wl = lds + (size_t)R * TP;    // twiddles of the sub-transform: w_R^e, e < R/2 (e < R with full_table)
-  const u32 NT = 1u << a.log_nt;
-  const int tid = threadIdx.x, nth = blockDim.x;
-  const int wstride_log = a.log_n_table - a.log_r;  // w_R^k = w_N^(k * N/R)
-  for (int k = tid; k < (a.full_table ? R : R / 2); k += nth) wl[k] = a.pow_table[(size_t)k << wstride_log];
-  // Block -> (tile, polynomial, coset), ONE decode for every launch.  The grid is 1-D and workgroups are dealt round-robin
-  // to the 8 XCDs, each with its own 4 MB L2: the low log_g bits of the block index (g = min(8, tiles)) pick the tile's
-  // residue, so an XCD only ever touches tiles = xcd (mod 8) -- 1/8 of the per-coset pre-scale table, which then stays
-  // L2-resident across polynomials -- and the n_cosets blocks reading the SAME coefficient tile run on the same XCD back to
-  // back (the tile is fetched from HBM once, not once per coset).  With one coset this is tile = L mod tiles, poly = L / tiles.
-  const u32 L = blockIdx.x;
-  const u32 m = L >> a.log_g;
-  const u32 tiles_g = a.n_tiles >> a.log_g;
-  const u32 coset = m % a.n_cosets;
-  const u32 r = m / a.n_cosets;
-  const u32 tile = (r % tiles_g) * (1u << a.log_g) + (L & ((1u << a.log_g) - 1u));
-  const u32 poly = r / tiles_g;
-  const u32 tg0 = tile * T;
-  const u64* in = a.in + (size_t)poly * a.in_poly_stride;
-  u64* out = a.out + (size_t)poly * a.out_poly_stride + a.coset_out_off[coset];
+  const int tid = threadIdx.x;
+  const int wstride_log = a.log_n_table - log_r;  // w_R^k = w_N^(k * N/R)
+  const bool full_table = log_r <= 10;
+  for (int k = tid; k < (full_table ? R : R / 2); k += NTH) wl[k] = a.pow_table[(size_t)k << wstride_log];
+  // Block -> (tile, polynomial, coset), ONE decode for every launch (nttix::decode_block).  The grid is 1-D and workgroups
+  // are dealt round-robin to the 8 XCDs, each with its own 4 MB L2: the low log_g bits of the block index (g = min(8, tiles))
+  // pick the tile's residue, so an XCD only ever touches tiles = xcd (mod 8) -- 1/8 of the per-coset pre-scale table, which
+  // then stays L2-resident across polynomials -- and the n_cosets blocks reading the SAME coefficient tile run on the same XCD
+  // back to back (the tile is fetched from HBM once, not once per coset).  With one coset this is tile = L mod tiles,
+  // poly = L / tiles.
+  const nttix::BlockId blk = nttix::decode_block(blockIdx.x, a.log_g, a.n_tiles, a.n_cosets);
+  const nttix::Tile tile{log_r, log_t, a.log_nt, blk.tile << log_t};
+  // wave-uniform bases; a lane's part of every address is a 32-bit offset inside the polynomial (ntt_index.h)
+  const u64* in = a.in + (size_t)blk.poly * a.in_poly_stride;
+  u64* out = a.out + (size_t)blk.poly * a.out_poly_stride + a.coset_out_off[blk.coset];
   // coset pre-scale: one table entry per input coefficient (shift_c^k at the coefficient's address k) ...
-  const u64* pre = PRE == 1 ? a.pre + ((size_t)coset << (a.log_r + a.log_nt)) : nullptr;
+  const u64* pre = PRE == 1 ? a.pre + ((size_t)blk.coset << (log_r + a.log_nt)) : nullptr;
   // ... or its two factors shift_c^t * (shift_c^NT)^i when N is too large for the table to live in L2 (2^19-row circuits:
   // 8 cosets x 4 MB, re-fetched for every polynomial).  A lane's elements all have the same t (the block size is a multiple
   // of the tile width), so the t factor is loaded once; the i factors (R entries per coset) stay cached.
-  const u64* pre_i = PRE == 2 ? a.pre_i + ((size_t)coset << a.log_r) : nullptr;
-  const u64 pre_tv = PRE == 2 ? a.pre_t[((size_t)coset << a.log_nt) + tg0 + (tid & (T - 1))] : 1;
-  auto in_slot = [&](int e, size_t& addr, int& slot, int& ii) {
-    int t, i;
-    if (a.in_kind == 0) {
-      t = e & (T - 1);
-      i = e >> a.log_t;
-      u32 ipos = a.in_br_i ? gl::bitrev(i, a.log_r) : i;
-      addr = (size_t)(tg0 + t) + (size_t)ipos * NT;
-    } else {
-      int off = e & (R - 1);
-      t = e >> a.log_r;
-      i = a.in_br_i ? (int)gl::bitrev(off, a.log_r) : off;
-      u32 trow = a.in_br_t ? gl::bitrev(tg0 + t, a.log_nt) : tg0 + t;
-      addr = (size_t)trow * R + off;
-    }
-    slot = i * TP + t;
-    ii = i;
-  };
+  const u64* pre_i = PRE == 2 ? a.pre_i + ((size_t)blk.coset << log_r) : nullptr;
+  const u64 pre_tv = PRE == 2 ? a.pre_t[((size_t)blk.coset << a.log_nt) + tile.tg0 + (tid & (T - 1))] : 1;
   // Eight elements per lane at a time: their loads (value + pre-scale factor) are all issued before the first is used.
   // (One element per iteration, as the loop was written first, is one exposed memory round trip per element: the
   // compiler puts s_waitcnt vmcnt(0) right behind each load.)
   constexpr int LB = 8;
-  int e = tid;
-  for (; e + (LB - 1) * nth < T * R; e += LB * nth) {
-    u64 xv[LB], pv[LB];
-    int slot[LB];
+  {
+    nttix::LoadCursor<IN> lc;
+    lc.init(tile, tid, NTH);
+    int e = tid;
+    for (; e + (LB - 1) * NTH < TR; e += LB * NTH) {
+      u64 xv[LB], pv[LB];
+      u32 slot[LB];
 #pragma unroll
-    for (int k = 0; k < LB; k++) {
-      size_t addr;
-      int ii;
-      in_slot(e + k * nth, addr, slot[k], ii);
-      xv[k] = in[addr];
-      if constexpr (PRE == 1) pv[k] = pre[addr];
-      else if constexpr (PRE == 2) pv[k] = pre_i[ii];
-      else pv[k] = 1;
-    }
+      for (int k = 0; k < LB; k++) {
+        const u32 g = lc.goff();
+        slot[k] = lc.slot();
+        xv[k] = ld_w(in, g);
+        if constexpr (PRE == 1) pv[k] = ld_w(pre, g);
+        else if constexpr (PRE == 2) pv[k] = pre_i[lc.idx()];
+        else pv[k] = 1;
+        lc.next();
+      }
 #pragma unroll
-    for (int k = 0; k < LB; k++) {
-      if constexpr (PRE == 1) lds[slot[k]] = gl::mul_nc(xv[k], pv[k]);
-      else if constexpr (PRE == 2) lds[slot[k]] = gl::mul_nc(gl::mul_nc(xv[k], pre_tv), pv[k]);
-      else lds[slot[k]] = xv[k];
+      for (int k = 0; k < LB; k++) {
+        if constexpr (PRE == 1) lds[slot[k]] = gl::mul_nc(xv[k], pv[k]);
+        else if constexpr (PRE == 2) lds[slot[k]] = gl::mul_nc(gl::mul_nc(xv[k], pre_tv), pv[k]);
+        else lds[slot[k]] = xv[k];
+      }
     }
-  }
-  for (; e < T * R; e += nth) {
-    size_t addr;
-    int slot, ii;
-    in_slot(e, addr, slot, ii);
-    u64 x = in[addr];
-    if constexpr (PRE == 1) x = gl::mul_nc(x, pre[addr]);
-    if constexpr (PRE == 2) x = gl::mul_nc(gl::mul_nc(x, pre_tv), pre_i[ii]);
-    lds[slot] = x;
+    for (; e < TR; e += NTH) {
+      const u32 g = lc.goff();
+      u64 x = ld_w(in, g);
+      if constexpr (PRE == 1) x = gl::mul_nc(x, ld_w(pre, g));
+      if constexpr (PRE == 2) x = gl::mul_nc(gl::mul_nc(x, pre_tv), pre_i[lc.idx()]);
+      lds[lc.slot()] = x;
+      lc.next();
+    }
   }
   __syncthreads();
 
   // DIF network, natural in -> bit-reversed out, up to 4 stages (radix 16) per LDS round trip:
   // a work item holds the 2^g elements {base + k*stride} of one sub-transform in registers.
-  for (int s0 = 0; s0 < a.log_r;) {
-    const int g = a.log_r - s0 < 4 ? a.log_r - s0 : 4;
-    const int lstride = a.log_r - s0 - g;
-    const int items = T << (a.log_r - g);
-    for (int b = tid; b < items; b += nth) {
-      const int t = b & (T - 1), q = b >> a.log_t;
-      const int l = q & ((1 << lstride) - 1), h = q >> lstride;
-      u64* col = lds + ((h << (a.log_r - s0)) + l) * TP + t;
-      switch (g) {
-        case 4:
-          if (a.full_table)
-            dif16_group<INV>(col, wl, TP << lstride, l, s0);
-          else
-            dif_group<4>(col, wl, TP << lstride, l, lstride, s0);
-          break;
-        case 3: dif_group<3>(col, wl, TP << lstride, l, lstride, s0); break;
-        case 2: dif_group<2>(col, wl, TP << lstride, l, lstride, s0); break;
-        default: dif_group<1>(col, wl, TP << lstride, l, lstride, s0); break;
-      }
+  if constexpr (LR >= 0) {
+    dif_network_static<INV, NTH, LR, LT, 0>(lds, wl, tid);
+  } else {
+    for (int s0 = 0; s0 < log_r;) {
+      const int g = log_r - s0 < 4 ? log_r - s0 : 4;
+      if (full_table)
+        dif_stages<INV, true, 0>(lds, wl, log_r, log_t, s0, g, tid, NTH);
+      else
+        dif_stages<INV, false, 0>(lds, wl, log_r, log_t, s0, g, tid, NTH);
+      s0 += g;
     }
-    __syncthreads();
-    s0 += g;
   }
 
-  auto out_slot = [&](int e, size_t& addr, int& slot, u32& tw, u32& j) {
-    int t, q;
-    if (a.out_kind == 0) {
-      t = e & (T - 1);
-      q = e >> a.log_t;
-      j = gl::bitrev(q, a.log_r);   // frequency index held at LDS position q
-      u32 ipos = a.out_br_i ? (u32)q : j;
-      addr = (size_t)(tg0 + t) + (size_t)ipos * NT;
-    } else {
-      int off = e & (R - 1);
-      t = e >> a.log_r;
-      q = a.out_br_i ? off : (int)gl::bitrev(off, a.log_r);
-      j = gl::bitrev(q, a.log_r);
-      u32 trow = a.out_br_t ? gl::bitrev(tg0 + t, a.log_nt) : tg0 + t;
-      addr = (size_t)trow * R + off;
+  // Store phase, eight at a time like the loads: the LDS reads and the multiplier gathers (the four-step twiddle from the
+  // power table, or the post-scale's i factor) are issued together.  In the t-contiguous kinds tw is the lane's own.
+  nttix::StoreCursor<OUT> sc;
+  sc.init(tile, tid, NTH);
+  constexpr bool T_KIND = OUT == nttix::OUT_T || OUT == nttix::OUT_T_BR;
+  const u64 post_tv = (MUL == nttix::MUL_POST && T_KIND) ? a.post_t[sc.tw()] : 1;
+  auto multiplier = [&](u64& w, u64& pt) {
+    // both factors of the twiddle index are below 2^11: a 24-bit product
+    if constexpr (MUL == nttix::MUL_TWIDDLE) w = ld_w(a.pow_table, __umul24(sc.tw(), sc.j()));
+    if constexpr (MUL == nttix::MUL_POST) {
+      w = a.post_i[sc.j()];
+      pt = T_KIND ? post_tv : a.post_t[sc.tw()];
     }
-    slot = q * TP + t;
-    tw = (u32)(tg0 + t);
   };
-  // the four-step twiddles (a gather from the power table) likewise eight at a time
+  auto finish = [&](u64 x, u64 w, u64 pt) {
+    if constexpr (MUL == nttix::MUL_TWIDDLE) x = gl::mul_nc(x, w);
+    if constexpr (MUL == nttix::MUL_POST) x = gl::mul_nc(x, gl::mul_nc(pt, w));
+    return LAZY ? x : gl::canon(x);
+  };
   int eo = tid;
-  if (a.use_twiddle && !a.post_t) {
-    for (; eo + (LB - 1) * nth < T * R; eo += LB * nth) {
-      u64 wv[LB], xv[LB];
-      size_t addr[LB];
+  for (; eo + (LB - 1) * NTH < TR; eo += LB * NTH) {
+    u64 wv[LB], ptv[LB], xv[LB];
+    u32 g[LB];
 #pragma unroll
-      for (int k = 0; k < LB; k++) {
-        int slot;
-        u32 tw, j;
-        out_slot(eo + k * nth, addr[k], slot, tw, j);
-        wv[k] = a.pow_table[(size_t)tw * j];
-        xv[k] = lds[slot];
-      }
-#pragma unroll
-      for (int k = 0; k < LB; k++) {
-        const u64 y = gl::mul_nc(xv[k], wv[k]);
-        out[addr[k]] = a.lazy_out ? y : gl::canon(y);
-      }
+    for (int k = 0; k < LB; k++) {
+      g[k] = sc.goff();
+      multiplier(wv[k], ptv[k]);
+      xv[k] = lds[sc.slot()];   // any u64 (lazy network)
+      sc.next();
     }
+#pragma unroll
+    for (int k = 0; k < LB; k++) st_w(out, g[k], finish(xv[k], wv[k], ptv[k]));
   }
-  for (; eo < T * R; eo += nth) {
-    size_t addr;
-    int slot;
-    u32 tw, j;
-    out_slot(eo, addr, slot, tw, j);
-    u64 x = lds[slot];   // any u64 (lazy network)
-    if (a.use_twiddle) x = gl::mul_nc(x, a.pow_table[(size_t)tw * j]);
-    if (a.post_t) x = gl::mul_nc(x, gl::mul_nc(a.post_t[tw], a.post_i[j]));
-    out[addr] = a.lazy_out ? x : gl::canon(x);
+  for (; eo < TR; eo += NTH) {
+    u64 w = 1, pt = 1;
+    multiplier(w, pt);
+    st_w(out, sc.goff(), finish(lds[sc.slot()], w, pt));
+    sc.next();
   }
 }
 
@@ -259,6 +278,7 @@ static size_t tile_lds_bytes(int log_r, int log_t) {
 }
 
 void launch_ntt_pass(const NttPass& p, int n_polys, int n_cosets, hipStream_t st) {
+  using namespace nttix;
   NttPass q = p;
   // the radix-16 groups index a full table of R twiddles; a 2^11-point sub-transform (2^22-point transforms) would
   // not fit the LDS a block may take with it and keeps the half table and the radix-2 network
@@ -270,9 +290,10 @@ void launch_ntt_pass(const NttPass& p, int n_polys, int n_cosets, hipStream_t st
   while (q.log_g < 3 && (2u << q.log_g) <= q.n_tiles) q.log_g++;
   const dim3 grid(q.n_tiles * (uint32_t)n_polys * (uint32_t)n_cosets);
   // tiles of 2^13 elements (16-wide tiles of 512-point sub-transforms: 2^19-point transforms, BASELINE config 5) take
-  // 512 threads, so that a CU's two resident blocks still give every SIMD four waves; above 64 KB of dynamic LDS the
-  // function attribute has to allow it (a workgroup may take up to 160 KB on gfx950)
+  // 512 threads, so that a CU's two resident blocks still give every SIMD four waves
   const bool wide = p.log_r + p.log_t >= 13;
+  // the 2^16-point transforms' tile (both passes): its own instantiation with the shape as constants
+  const bool hot = p.log_r == 8 && p.log_t == 4;
   const int pre_mode = q.pre ? 1 : (q.pre_t ? 2 : 0);
   auto launch = [&](auto kernel, int nth) {
     if (lds > 64 * 1024) {   // above 64 KB of dynamic LDS the function attribute has to allow it (160 KB per workgroup on gfx950)
@@ -287,18 +308,40 @@ void launch_ntt_pass(const NttPass& p, int n_polys, int n_cosets, hipStream_t st
     }
     hipLaunchKernelGGL(kernel, grid, dim3(nth), lds, st, q);
   };
-#define P25_NTT_LAUNCH(INV, NTH)                                                            \
-  switch (pre_mode) {                                                                       \
-    case 1: launch(k_ntt_tile<INV, NTH, 1>, NTH); break;                                    \
-    case 2: launch(k_ntt_tile<INV, NTH, 2>, NTH); break;                                    \
-    default: launch(k_ntt_tile<INV, NTH, 0>, NTH); break;                                   \
+  // The pass's addressing form.  A bit-reversed input is reversed in the row number and in the position (a single pass
+  // has one row); outputs are never reversed in the row number.
+  int in = -1, out = -1;
+  if (p.in_kind == 0 && !p.in_br_i) in = IN_T;
+  if (p.in_kind == 1 && !p.in_br_t && !p.in_br_i) in = IN_I;
+  if (p.in_kind == 1 && p.in_br_i && (p.in_br_t || p.log_nt == 0)) in = IN_I_BR;
+  if (!p.out_br_t) out = p.out_kind == 0 ? (p.out_br_i ? OUT_T_BR : OUT_T) : (p.out_br_i ? OUT_I_BR : OUT_I);
+  const int mul = p.post_t ? MUL_POST : (p.use_twiddle ? MUL_TWIDDLE : MUL_NONE);
+  const bool both = p.post_t && p.use_twiddle;
+  // one line per form the library issues (ntt_inverse, ntt_lde_bitrev); WIDE / HOT: which block sizes and whether the
+  // constant-shape instantiation exist for it
+#define P25_NTT_FORM(INV, PRE, IN, OUT, MUL, LAZY, WIDE, HOT)                                                         \
+  if (!both && (bool)q.inverse == INV && pre_mode == PRE && in == IN && out == OUT && mul == MUL && (bool)q.lazy_out == LAZY && \
+      (WIDE || !wide)) {                                                                                              \
+    if (wide) {                                                                                                       \
+      if constexpr (WIDE) launch(k_ntt_tile<INV, 512, PRE, IN, OUT, MUL, LAZY, -1, -1>, 512);                         \
+    } else if (HOT && hot) {                                                                                          \
+      if constexpr (HOT) launch(k_ntt_tile<INV, 256, PRE, IN, OUT, MUL, LAZY, 8, 4>, 256);                            \
+    } else {                                                                                                          \
+      launch(k_ntt_tile<INV, 256, PRE, IN, OUT, MUL, LAZY, -1, -1>, 256);                                             \
+    }                                                                                                                 \
+    return;                                                                                                           \
   }
-  if (wide) {
-    if (q.inverse) { P25_NTT_LAUNCH(true, 512) } else { P25_NTT_LAUNCH(false, 512) }
-  } else {
-    if (q.inverse) { P25_NTT_LAUNCH(true, 256) } else { P25_NTT_LAUNCH(false, 256) }
-  }
-#undef P25_NTT_LAUNCH
+  P25_NTT_FORM(true, 0, IN_T, OUT_T, MUL_TWIDDLE, true, true, true)         // inverse pass 1
+  P25_NTT_FORM(true, 0, IN_I_BR, OUT_T, MUL_TWIDDLE, true, true, false)     // inverse pass 1 of the quotient (bit-reversed input)
+  P25_NTT_FORM(true, 0, IN_I, OUT_T, MUL_POST, false, true, true)           // inverse pass 2
+  P25_NTT_FORM(true, 0, IN_I, OUT_I, MUL_POST, false, false, false)         // single-pass inverse
+  P25_NTT_FORM(true, 0, IN_I_BR, OUT_I, MUL_POST, false, false, false)      //   from bit-reversed input
+  P25_NTT_FORM(false, 1, IN_T, OUT_T_BR, MUL_TWIDDLE, true, true, true)     // LDE pass 1
+  P25_NTT_FORM(false, 2, IN_T, OUT_T_BR, MUL_TWIDDLE, true, true, false)    //   with the factored pre-scale
+  P25_NTT_FORM(false, 0, IN_I, OUT_I_BR, MUL_NONE, false, true, true)       // LDE pass 2
+  P25_NTT_FORM(false, 1, IN_I, OUT_I_BR, MUL_NONE, false, false, false)     // single-pass LDE
+#undef P25_NTT_FORM
+  throw std::runtime_error("NTT pass of a form the library has no kernel for");
 }
 
 // Tile width.  A pass whose tile is STRIDED in memory (kind 0: T adjacent words per row of the tile, rows NT words

@@ -207,7 +207,28 @@ p25_status p25_circuit_build_p3_verifier(const p25_p3_config* cfg, int32_t air, 
  * (log_quotient_degree = 1; round 5): the reference's verifier (verifier.rs:115-221) and its shape derivation (mod.rs:76)
  * handle any power of two, only that `(0..1)` fixes the count -- the flat input then carries the second chunk's two
  * openings right behind the first's, and every query's quotient batch holds one row per chunk.  The FibonacciAir of
- * src/p3/mod.rs:176-221 in this form builds the very same circuit (same digest) as P25_AIR_FIBONACCI. */
+ * src/p3/mod.rs:176-221 in this form builds the very same circuit (same digest) as P25_AIR_FIBONACCI.
+ *
+ * PUBLIC VALUES (this library's extension: the reference's `Air` trait, src/p3/air.rs:10-27, has none; uni-stark's AIRs read
+ * them through `builder.public_values()`).  An AIR declares n_public of them, 0..P25_AIR_MAX_PUBLIC, and reads them with
+ * node.op 6 PUBLIC(a): public value a < n_public of the proof being made or checked -- degree 0 and free like CONST, usable
+ * wherever a CONST is, under every `when`.  An index >= n_public and n_public > 64 are P25_ERR_INVALID_ARG.  n_public = 0 is
+ * the AIR form as it was, word for word and gate for gate.
+ *   Layout     a proof's public values are the LAST n_public words of its flat input, behind the words of `add_virtual_to`
+ *              order.  num_inputs (p25_p3_prover_config, p25_circuit_info_t) and every stride count them: num_inputs = the
+ *              words p25_p3_config describes + n_public.  p25_p3_config itself does not change.
+ *   Transcript the challenger observes the n_public values, in order, right after the trace commitment and before alpha is
+ *              sampled: where uni-stark's prover and verifier have `challenger.observe_slice(public_values)`.  Restated from
+ *              the absent crate, so UNPINNED like the rest of the plonky3 prover (tools/upstream_check/README).
+ *   Circuit    p25_circuit_build_p3_verifier_air allocates n_public input targets behind the proof's, observes them in the
+ *              in-circuit challenger at the same place, hands them to the AIR as base elements embedded in the extension,
+ *              and registers them as the circuit's public inputs, in order: the outer proof's public_inputs ARE the inner
+ *              proof's public values.  A flat input whose tail differs from what the inner proof was made with fails the
+ *              outer proof with P25_ERR_WITNESS_CONFLICT.
+ *   Proving    p25_p3_prove_air_pv, p25_p3_prove_batch_pv[_dev].  The forms without public values (p25_p3_prove_air[_ex],
+ *              p25_p3_prove_batch[_dev]) return P25_ERR_INVALID_ARG for an AIR with n_public > 0; the message names the _pv
+ *              form.  p25_p3_verify_batch[_dev] read the values from the proof's tail. */
+enum { P25_AIR_MAX_PUBLIC = 64 };
 typedef struct {
   uint32_t op, a, b, reserved;
   uint64_t value;
@@ -216,7 +237,7 @@ typedef struct {
   uint32_t node, when;
 } p25_air_constraint;
 typedef struct {
-  uint32_t width, n_nodes, n_constraints, reserved;
+  uint32_t width, n_nodes, n_constraints, n_public;   /* n_public: 0..P25_AIR_MAX_PUBLIC (the former `reserved`, zero) */
   const p25_air_node* nodes;
   const p25_air_constraint* constraints;
 } p25_air;
@@ -239,6 +260,12 @@ p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t l
 p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t log_blowup, int32_t num_queries,
                                int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
                                size_t* n_out, p25_p3_config* cfg_out);
+/* The same for an AIR with public values: public_values[air->n_public], every word < p (else P25_ERR_INVALID_ARG); NULL is
+ * allowed when n_public = 0, and the words are then p25_p3_prove_air_ex's.  *n_out = the proof's words + n_public: the values
+ * follow the proof.  P25_ERR_INVALID_ARG if the trace does not satisfy the AIR under these public values. */
+p25_status p25_p3_prove_air_pv(const p25_air* air, const uint64_t* trace, const uint64_t* public_values, int32_t log_n,
+                               int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start, int32_t threads,
+                               uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out);
 
 /* Small circuits mirroring the reference's gadget tests (src/p3/mod.rs:271-494 test_p3_and / xor / lsh /
  * rsh / reverse, src/p3/commit.rs:173-198 test_compress): kind 0 and(x,y) 1 xor(x,y) 2 lsh(x,param)
@@ -494,7 +521,7 @@ p25_status p25_verify_batch_dev(p25_circuit* c, const uint64_t* digest4, const u
  * p25_p3_prover_create   host only, works without a GPU.  Replaces the shape half of p25_p3_prove_air_ex: validates exactly
  *     what that function validates, with the same P25_ERR_INVALID_ARG cases (the AIR itself; log_n 1..22, log_blowup 1..4,
  *     log_n + log_blowup <= 24; num_queries >= 1; pow_bits 0..30; log_quotient_degree <= log_blowup), and compiles the AIR
- *     into the register program the quotient kernel interprets.  LOCAL / NEXT / CONST nodes cost nothing; the device form's
+ *     into the register program the quotient kernel interprets.  LOCAL / NEXT / CONST / PUBLIC nodes cost nothing; the device form's
  *     own limits are 64 arithmetic-node values alive at the same time (after a liveness pass over the DAG in constraint
  *     order), 2^20 instructions and 65535 queries: an AIR beyond them is refused HERE, with a message naming the limit,
  *     never later.  Width 64 and 512 nodes are within them.  No device memory is touched before the first compute call.
@@ -527,6 +554,15 @@ p25_status p25_verify_batch_dev(p25_circuit* c, const uint64_t* digest4, const u
  *       p25_circuit_wait_stream(c, s);  p25_prove_batch_dev(c, d_inputs, n, d_seeds, d_proofs, stride, d_status, NULL);
  * p25_p3_prover_sync     host waits for everything this prover has enqueued.
  *
+ * p25_p3_prove_batch_pv[_dev]  the two forms above for an AIR with public values (p25_air.n_public > 0; with n_public = 0
+ *   they ARE the forms above and public_values may be NULL).  public_values[n_proofs][n_public], packed: row i belongs to
+ *   proof i, whatever group of the batch it runs in.  Proof i's num_inputs words end in its n_public values; a failed
+ *   proof's words are zeros, that tail included.  A trace that does not satisfy the AIR under ITS public values fails that
+ *   proof only (P25_ERR_INVALID_ARG).  The host form checks every public value < p (else the whole call is
+ *   P25_ERR_INVALID_ARG and nothing is launched); the device form checks nothing.  Everything else -- enqueue-only on
+ *   `stream`, the two blocking exceptions, groups that change no word -- is as stated above.  The forms above return
+ *   P25_ERR_INVALID_ARG on a prover whose AIR has public values.
+ *
  * Memory: the handle owns its scratch (trees, LDEs, FRI layers: about 40 words = 320 bytes per LDE point, ~660 MB for a
  * 2^20-row width-3 proof) and reuses it across calls; it grows only after the earlier use has finished, and a growth that
  * fails (P25_ERR_HIP) leaves the handle without scratch but usable: the next call allocates what it needs.  A batch runs in groups of as
@@ -547,6 +583,12 @@ p25_status p25_p3_prove_batch(p25_p3_prover* p, const uint64_t* traces, size_t n
 p25_status p25_p3_prove_batch_dev(p25_p3_prover* p, const uint64_t* d_traces, size_t trace_stride_words, size_t n_proofs,
                                   const uint64_t* d_pow_starts, uint64_t* d_inputs, size_t input_stride_words,
                                   uint32_t* d_status, void* stream);
+p25_status p25_p3_prove_batch_pv(p25_p3_prover* p, const uint64_t* traces, const uint64_t* public_values, size_t n_proofs,
+                                 const uint64_t* pow_starts, uint64_t* inputs_out, size_t input_stride_words,
+                                 p25_status* per_proof_status);
+p25_status p25_p3_prove_batch_pv_dev(p25_p3_prover* p, const uint64_t* d_traces, size_t trace_stride_words,
+                                     const uint64_t* d_public_values, size_t n_proofs, const uint64_t* d_pow_starts,
+                                     uint64_t* d_inputs, size_t input_stride_words, uint32_t* d_status, void* stream);
 p25_status p25_p3_prover_sync(p25_p3_prover* p);
 p25_status p25_p3_prover_set_scratch_budget(p25_p3_prover* p, size_t bytes);
 
@@ -560,7 +602,9 @@ p25_status p25_p3_prover_set_scratch_budget(p25_p3_prover* p, size_t bytes);
  * opening of every FRI round in order and the comparison of the folded value with final_poly -- so a final-polynomial
  * failure of query 0 precedes a Merkle failure of query 1 --; the quotient identity at zeta last.  A zero denominator x - z
  * in a reduced opening (zeta in the base field, on the LDE coset) counts as that query's final-polynomial failure and is
- * reported ahead of that query's FRI rounds.
+ * reported ahead of that query's FRI rounds.  The public values of an AIR that has some are the proof's last n_public words:
+ * they are part of the scan for a word >= p (P25_P3_REJECT_MALFORMED), are observed behind the trace commitment, and enter
+ * the identity, so a changed one shows as a later check failing (as a rule the proof of work).  The order of verdicts is as above.
  *   inputs[n_proofs][input_stride_words]   proof i = num_inputs words at i * input_stride_words; stride >= num_inputs
  *                                 (P25_ERR_INVALID_ARG below it); the words behind a proof are neither read nor written.
  *                                 At most 2^24 proofs per call and n_proofs * input_stride_words below 2^60, as for
@@ -680,7 +724,9 @@ p25_status p25_fri_prove(const uint64_t* coeffs, unsigned log_n, unsigned rate_b
  * ------------------------------------------------------------------------------------------ */
 /* plonky3 proof JSON (serde form of src/p3/serde/proof.rs:349-355, e.g. artifacts/proof_fibonacci.json)
  * -> input vector + shape.  Replaces serde_json::from_str::<P3ProofField> + set_witness
- * (src/p3/mod.rs:233-234, 254-257).  inputs_out may be NULL to query *n_out. */
+ * (src/p3/mod.rs:233-234, 254-257).  inputs_out may be NULL to query *n_out.  Covers the proof's words only: plonky3's
+ * `Proof` holds no public values (its verifier takes them beside the proof), so for an AIR with n_public > 0 the caller
+ * appends them to reach num_inputs. */
 p25_status p25_p3_proof_from_json(const char* json, size_t len, uint64_t* inputs_out, size_t cap, size_t* n_out,
                                   p25_p3_config* cfg_out);
 /* Native plonky3 prover for the Fibonacci AIR of src/p3/mod.rs:160-221 (host code):
@@ -692,7 +738,8 @@ p25_status p25_p3_proof_from_json(const char* json, size_t len, uint64_t* inputs
 p25_status p25_p3_prove_fibonacci(int32_t log_n, int32_t num_queries, int32_t pow_bits, uint64_t pow_start,
                                   int32_t threads, uint64_t* inputs_out, size_t cap, size_t* n_out,
                                   p25_p3_config* cfg_out);
-/* Input vector -> plonky3 proof JSON in the reference's serde format (src/p3/serde/proof.rs:16-355). */
+/* Input vector -> plonky3 proof JSON in the reference's serde format (src/p3/serde/proof.rs:16-355).  The proof's words
+ * only: for an AIR with public values pass the first num_inputs - n_public words (n = that count). */
 p25_status p25_p3_inputs_to_json(const uint64_t* inputs, size_t n, const p25_p3_config* cfg, char* buf,
                                  size_t cap, size_t* len_out);
 /* Flat proof -> JSON shaped like serde_json::to_string(&ProofWithPublicInputs) (src/p3/mod.rs:261).

@@ -54,7 +54,7 @@ class AirConstraint(C.Structure):
 
 
 class AirC(C.Structure):
-    _fields_ = [("width", C.c_uint32), ("n_nodes", C.c_uint32), ("n_constraints", C.c_uint32), ("reserved", C.c_uint32),
+    _fields_ = [("width", C.c_uint32), ("n_nodes", C.c_uint32), ("n_constraints", C.c_uint32), ("n_public", C.c_uint32),
                 ("nodes", C.POINTER(AirNode)), ("constraints", C.POINTER(AirConstraint))]
 
 
@@ -64,11 +64,14 @@ class Air:
 
         air = Air(3); a, b, c = air.local(0), air.local(1), air.local(2)
         air.assert_zero(air.sub(air.add(a, b), c)); air.when_first_row(air.sub(air.const(1), a)); ...
+
+    n_public (0..64): the proof's public values, read with air.public(i) wherever a constant could stand
+    (`builder.public_values()[i]` in a uni-stark AIR); they are the last n_public words of the proof's flat input.
     """
     ALWAYS, FIRST_ROW, LAST_ROW, TRANSITION = 0, 1, 2, 3
 
-    def __init__(self, width):
-        self.width, self.nodes, self.constraints = width, [], []
+    def __init__(self, width, n_public=0):
+        self.width, self.n_public, self.nodes, self.constraints = width, int(n_public), [], []
 
     def _n(self, op, a=0, b=0, value=0):
         self.nodes.append((op, a, b, value))
@@ -77,6 +80,7 @@ class Air:
     def local(self, col): return self._n(0, col)
     def next(self, col): return self._n(1, col)
     def const(self, v): return self._n(2, 0, 0, int(v))
+    def public(self, i): return self._n(6, int(i))
     def add(self, x, y): return self._n(3, x, y)
     def sub(self, x, y): return self._n(4, x, y)
     def mul(self, x, y): return self._n(5, x, y)
@@ -102,7 +106,7 @@ class Air:
     def to_c(self):
         nodes = (AirNode * len(self.nodes))(*[AirNode(op, a, b, 0, v) for op, a, b, v in self.nodes])
         cons = (AirConstraint * len(self.constraints))(*[AirConstraint(n, w) for n, w in self.constraints])
-        c = AirC(self.width, len(self.nodes), len(self.constraints), 0, nodes, cons)
+        c = AirC(self.width, len(self.nodes), len(self.constraints), self.n_public, nodes, cons)
         c._keep = (nodes, cons)
         return c
 
@@ -213,6 +217,10 @@ EXPORTED_SYMBOLS = {
     "p25_p3_prover_config": (i32, [vp, C.POINTER(P3Config), C.POINTER(sz)]),
     "p25_p3_prove_batch": (i32, [vp, vp, sz, vp, vp, sz, vp]),
     "p25_p3_prove_batch_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, vp, vp]),
+    "p25_p3_prove_air_pv": (i32, [C.POINTER(AirC), vp, vp, i32, i32, i32, i32, C.c_uint64, i32, vp, sz, C.POINTER(sz),
+                                  C.POINTER(P3Config)]),
+    "p25_p3_prove_batch_pv": (i32, [vp, vp, vp, sz, vp, vp, sz, vp]),
+    "p25_p3_prove_batch_pv_dev": (i32, [vp, vp, sz, vp, sz, vp, vp, sz, vp, vp]),
     "p25_p3_prover_sync": (i32, [vp]),
     "p25_p3_verify_batch": (i32, [vp, vp, sz, sz, vp]),
     "p25_p3_verify_batch_dev": (i32, [vp, vp, sz, sz, vp, vp]),
@@ -443,9 +451,22 @@ def p3_prove_fibonacci(log_n=6, num_queries=100, pow_bits=16, pow_start=0, threa
     return out, cfg
 
 
-def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=None, log_blowup=1):
+def _public_rows(public_values, n, n_public):
+    """public_values -> uint64[n][n_public] (None allowed when the AIR has none)."""
+    if public_values is None:
+        if n_public:
+            raise ValueError("the AIR has %d public values: pass public_values" % n_public)
+        return None
+    pv = _u64(public_values)
+    if pv.size != n * n_public:
+        raise ValueError("public_values must hold n_public words per proof")
+    return np.ascontiguousarray(pv.reshape(n, n_public)) if pv.size else None
+
+
+def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=None, log_blowup=1, public_values=None):
     """Native plonky3 proof of `air` (binding.Air) on `trace` (uint64[2^log_n][width]) -> (inputs, P3Config).
-    log_blowup: FriConfig.log_blowup (1 = the reference's; 2 / 3 for AIRs of constraint degree up to 5 / 9)."""
+    log_blowup: FriConfig.log_blowup (1 = the reference's; 2 / 3 for AIRs of constraint degree up to 5 / 9).
+    public_values: the air.n_public values of this proof; they end up as the last words of `inputs`."""
     threads = threads or min(16, os.cpu_count() or 1)
     t = np.ascontiguousarray(trace, dtype=np.uint64)
     if t.ndim != 2 or t.shape[1] != air.width or t.shape[0] & (t.shape[0] - 1) or t.shape[0] < 2:
@@ -453,8 +474,15 @@ def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=
     log_n = int(t.shape[0]).bit_length() - 1
     ac = air.to_c()
     cfg = P3Config()
-    out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_ex(C.byref(ac), _ptr(t), log_n, log_blowup, num_queries, pow_bits,
-                                                               pow_start, threads, buf, cap, n, C.byref(cfg)), np.uint64)
+    if air.n_public == 0 and public_values is None:
+        out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_ex(C.byref(ac), _ptr(t), log_n, log_blowup, num_queries,
+                                                                   pow_bits, pow_start, threads, buf, cap, n, C.byref(cfg)),
+                     np.uint64)
+        return out, cfg
+    pv = _public_rows(public_values, 1, air.n_public)
+    out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_pv(C.byref(ac), _ptr(t), _ptr(pv), log_n, log_blowup, num_queries,
+                                                               pow_bits, pow_start, threads, buf, cap, n, C.byref(cfg)),
+                 np.uint64)
     return out, cfg
 
 
@@ -467,15 +495,16 @@ class P3Prover:
         h = vp()
         _check(lib().p25_p3_prover_create(C.byref(ac), log_n, log_blowup, num_queries, pow_bits, C.byref(h)))
         self._h = vp(h.value)
-        self.width, self.log_n = air.width, log_n
+        self.width, self.log_n, self.n_public = air.width, log_n, air.n_public
         self.config = P3Config()
         n = sz(0)
         _check(lib().p25_p3_prover_config(self._h, C.byref(self.config), C.byref(n)))
         self.num_inputs = int(n.value)
 
-    def prove(self, traces, pow_starts=None, input_stride=None):
+    def prove(self, traces, public_values=None, pow_starts=None, input_stride=None):
         """traces: uint64[n][2^log_n][width] (or one trace) -> (inputs[n][num_inputs], int32 statuses).  A failed proof's
-        row is zeros.  input_stride (>= num_inputs): rows of that length, the words behind a proof left as made."""
+        row is zeros.  public_values: uint64[n][n_public] for an AIR that has some; proof i's row ends in them.
+        input_stride (>= num_inputs): rows of that length, the words behind a proof left as made."""
         t = _u64(traces)
         if t.ndim == 2:
             t = t.reshape((1,) + t.shape)
@@ -488,13 +517,24 @@ class P3Prover:
         stride = self.num_inputs if input_stride is None else int(input_stride)
         out = np.zeros((n, stride), dtype=np.uint64)
         st = np.zeros(n, dtype=np.int32)
-        _check(lib().p25_p3_prove_batch(self._h, _ptr(t), n, _ptr(ps), _ptr(out), stride, _ptr(st)))
+        if self.n_public == 0 and public_values is None:
+            _check(lib().p25_p3_prove_batch(self._h, _ptr(t), n, _ptr(ps), _ptr(out), stride, _ptr(st)))
+        else:
+            pv = _public_rows(public_values, n, self.n_public)
+            _check(lib().p25_p3_prove_batch_pv(self._h, _ptr(t), _ptr(pv), n, _ptr(ps), _ptr(out), stride, _ptr(st)))
         return out, st
 
-    def prove_dev(self, d_traces, trace_stride, n, d_pow_starts, d_inputs, input_stride, d_status, stream=0):
-        """Device-resident batch (raw device addresses), enqueued on `stream` (a raw hipStream_t; 0 = the default stream)."""
-        _check(lib().p25_p3_prove_batch_dev(self._h, d_traces, trace_stride, n, d_pow_starts, d_inputs, input_stride, d_status,
-                                            C.c_void_p(stream) if stream else None))
+    def prove_dev(self, d_traces, trace_stride, n, d_pow_starts, d_inputs, input_stride, d_status, stream=0, *,
+                  d_public_values=0):
+        """Device-resident batch (raw device addresses), enqueued on `stream` (a raw hipStream_t; 0 = the default stream).
+        d_public_values: uint64[n][n_public] on the device, for an AIR that has public values."""
+        st = C.c_void_p(stream) if stream else None
+        if self.n_public == 0 and not d_public_values:
+            _check(lib().p25_p3_prove_batch_dev(self._h, d_traces, trace_stride, n, d_pow_starts, d_inputs, input_stride,
+                                                d_status, st))
+        else:
+            _check(lib().p25_p3_prove_batch_pv_dev(self._h, d_traces, trace_stride, d_public_values or None, n, d_pow_starts,
+                                                   d_inputs, input_stride, d_status, st))
 
     def verify(self, inputs, input_stride=None):
         """inputs: uint64[n][input_stride] (or one proof), proof i = num_inputs words at the start of row i -> int32 statuses:

@@ -300,6 +300,8 @@ AirProgram air_from_c(const p25_air* air) {
   if (air->n_nodes > (1u << 20) || air->n_constraints > (1u << 16)) throw std::invalid_argument("AIR too large");
   AirProgram p;
   p.width = (int)air->width;
+  if (air->n_public > (uint32_t)AirProgram::MAX_PUBLIC) throw std::invalid_argument("AIR: more than 64 public values (n_public)");
+  p.n_public = (int)air->n_public;
   for (uint32_t i = 0; i < air->n_nodes; i++)
     p.nodes.push_back(AirProgram::Node{air->nodes[i].op, air->nodes[i].a, air->nodes[i].b, air->nodes[i].value});
   for (uint32_t i = 0; i < air->n_constraints; i++)
@@ -318,14 +320,14 @@ P3Config p3_shape(const P3ProveParams& prm) {
   pc.opening_matrix_log_max_height = prm.log_n + prm.log_blowup;
   return pc;
 }
-// Their output: a size query (inputs_out NULL) is answered from the shape pc alone, without proving; otherwise prove()
-// completes pc and returns the inputs.
+// Their output: a size query (inputs_out NULL) is answered from the shape pc alone (and the n_public words behind the
+// proof's), without proving; otherwise prove() completes pc and returns the inputs.
 template <class F>
 p25_status p3_prove_out(const P3ProveParams& prm, P3Config& pc, F&& prove, uint64_t* inputs_out, size_t cap, size_t* n_out,
-                        p25_p3_config* cfg_out) {
+                        p25_p3_config* cfg_out, size_t n_public = 0) {
   if (!inputs_out) {
     if (prm.log_n < 1 || prm.log_n > 22 || prm.num_queries < 1) throw std::invalid_argument("bad parameters");
-    *n_out = pc.num_inputs();
+    *n_out = pc.num_inputs() + n_public;
     pc.fri_config.proof_of_work_bits = prm.pow_bits;
   } else {
     const std::vector<u64> v = prove();
@@ -607,12 +609,15 @@ p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t l
                             size_t* n_out, p25_p3_config* cfg_out) {
   return p25_p3_prove_air_ex(air, trace, log_n, 1, num_queries, pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
-p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t log_blowup, int32_t num_queries,
-                               int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
-                               size_t* n_out, p25_p3_config* cfg_out) {
+// p25_p3_prove_air_ex (pv_form false: refuses an AIR with public values) and p25_p3_prove_air_pv
+static p25_status p3_prove_air_host(bool pv_form, const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
+                                    int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start,
+                                    int32_t threads, uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out) {
   return host_guarded([&]() -> p25_status {
     if (!air || !n_out) throw std::invalid_argument("null argument");
     AirProgram prog = air_from_c(air);
+    if (!pv_form && prog.n_public > 0)
+      throw std::invalid_argument("the AIR has public values (n_public > 0): use p25_p3_prove_air_pv");
     if (log_blowup < 1 || log_blowup > 4) throw std::invalid_argument("log_blowup must be 1..4");
     if (prog.log_quotient_degree() > log_blowup)
       throw std::invalid_argument("an AIR of constraint degree " + std::to_string(prog.max_constraint_degree()) + " needs log_blowup >= " +
@@ -628,14 +633,29 @@ p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_
       std::vector<std::vector<u64>> col(prog.width, std::vector<u64>(n));
       for (size_t r = 0; r < n; r++)
         for (int c = 0; c < prog.width; c++) col[c][r] = trace[r * prog.width + c];
+      if (prog.n_public && !public_values) throw std::invalid_argument("null public_values");
+      std::vector<u64> pub;
+      if (prog.n_public) pub.assign(public_values, public_values + prog.n_public);
       try {
-        return p3_prove_air(prog, col, prm, pc);
+        return p3_prove_air_pv(prog, col, pub, prm, pc);
       } catch (const std::logic_error& e) {  // "quotient identity does not hold": the trace violates the AIR
         throw std::invalid_argument(e.what());
       }
     };
-    return p3_prove_out(prm, pc, prove, inputs_out, cap, n_out, cfg_out);
+    return p3_prove_out(prm, pc, prove, inputs_out, cap, n_out, cfg_out, (size_t)prog.n_public);
   });
+}
+p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t log_blowup, int32_t num_queries,
+                               int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
+                               size_t* n_out, p25_p3_config* cfg_out) {
+  return p3_prove_air_host(false, air, trace, nullptr, log_n, log_blowup, num_queries, pow_bits, pow_start, threads, inputs_out,
+                           cap, n_out, cfg_out);
+}
+p25_status p25_p3_prove_air_pv(const p25_air* air, const uint64_t* trace, const uint64_t* public_values, int32_t log_n,
+                               int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start, int32_t threads,
+                               uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out) {
+  return p3_prove_air_host(true, air, trace, public_values, log_n, log_blowup, num_queries, pow_bits, pow_start, threads,
+                           inputs_out, cap, n_out, cfg_out);
 }
 
 // ---- the plonky3 prover on the device -------------------------------------------------------------------------------
@@ -667,11 +687,21 @@ p25_status p25_p3_prover_set_scratch_budget(p25_p3_prover* p, size_t bytes) {
     return P25_OK;
   });
 }
-p25_status p25_p3_prove_batch(p25_p3_prover* p, const uint64_t* traces, size_t n_proofs, const uint64_t* pow_starts,
-                              uint64_t* inputs_out, size_t input_stride_words, p25_status* per_proof_status) {
+// the forms without public values refuse a prover whose AIR has some
+static void p3_no_public(const p25_p3_prover* p, const char* pv_form) {
+  if (p && p->dev->n_public() > 0)
+    throw std::invalid_argument(std::string("the prover's AIR has public values (n_public > 0): use ") + pv_form);
+}
+static p25_status p3_prove_batch_host(p25_p3_prover* p, const uint64_t* traces, const uint64_t* public_values, size_t n_proofs,
+                                      const uint64_t* pow_starts, uint64_t* inputs_out, size_t input_stride_words,
+                                      p25_status* per_proof_status) {
   return host_guarded([&]() -> p25_status {
     if (!p3_prove_args(p, traces, n_proofs, inputs_out, input_stride_words, per_proof_status, p ? p->dev->trace_words() : 0))
       return P25_OK;
+    const size_t np = n_proofs * p->dev->n_public();
+    if (np && !public_values) throw std::invalid_argument("null public_values");
+    for (size_t i = 0; i < np; i++)
+      if (public_values[i] >= gl::P) throw std::invalid_argument("non-canonical field element in public_values");
     const size_t tw = n_proofs * p->dev->trace_words();
     for (size_t i = 0; i < tw; i++)
       if (traces[i] >= gl::P) throw std::invalid_argument("non-canonical field element in a trace");
@@ -681,22 +711,51 @@ p25_status p25_p3_prove_batch(p25_p3_prover* p, const uint64_t* traces, size_t n
     if (s != P25_OK) return s;
     P25_LOCK(p);
     static_assert(sizeof(p25_status) == sizeof(int32_t), "p25_status is a 32-bit enum");
-    p->dev->prove_host(traces, n_proofs, pow_starts, inputs_out, input_stride_words, reinterpret_cast<int32_t*>(per_proof_status));
+    p->dev->prove_host(traces, public_values, n_proofs, pow_starts, inputs_out, input_stride_words,
+                       reinterpret_cast<int32_t*>(per_proof_status));
     return P25_OK;
   });
+}
+static p25_status p3_prove_batch_device(p25_p3_prover* p, const uint64_t* d_traces, size_t trace_stride_words,
+                                        const uint64_t* d_public_values, size_t n_proofs, const uint64_t* d_pow_starts,
+                                        uint64_t* d_inputs, size_t input_stride_words, uint32_t* d_status, void* stream) {
+  return host_guarded([&]() -> p25_status {
+    if (!p3_prove_args(p, d_traces, n_proofs, d_inputs, input_stride_words, d_status, trace_stride_words)) return P25_OK;
+    if (p->dev->n_public() && !d_public_values) throw std::invalid_argument("null d_public_values");
+    const p25_status s = ensure_device();
+    if (s != P25_OK) return s;
+    P25_LOCK(p);
+    p->dev->prove_dev(d_traces, trace_stride_words, d_public_values, n_proofs, d_pow_starts, d_inputs, input_stride_words,
+                      d_status, (hipStream_t)stream);
+    return P25_OK;
+  });
+}
+p25_status p25_p3_prove_batch(p25_p3_prover* p, const uint64_t* traces, size_t n_proofs, const uint64_t* pow_starts,
+                              uint64_t* inputs_out, size_t input_stride_words, p25_status* per_proof_status) {
+  return host_guarded([&]() -> p25_status {
+    p3_no_public(p, "p25_p3_prove_batch_pv");
+    return p3_prove_batch_host(p, traces, nullptr, n_proofs, pow_starts, inputs_out, input_stride_words, per_proof_status);
+  });
+}
+p25_status p25_p3_prove_batch_pv(p25_p3_prover* p, const uint64_t* traces, const uint64_t* public_values, size_t n_proofs,
+                                 const uint64_t* pow_starts, uint64_t* inputs_out, size_t input_stride_words,
+                                 p25_status* per_proof_status) {
+  return p3_prove_batch_host(p, traces, public_values, n_proofs, pow_starts, inputs_out, input_stride_words, per_proof_status);
 }
 p25_status p25_p3_prove_batch_dev(p25_p3_prover* p, const uint64_t* d_traces, size_t trace_stride_words, size_t n_proofs,
                                   const uint64_t* d_pow_starts, uint64_t* d_inputs, size_t input_stride_words,
                                   uint32_t* d_status, void* stream) {
   return host_guarded([&]() -> p25_status {
-    if (!p3_prove_args(p, d_traces, n_proofs, d_inputs, input_stride_words, d_status, trace_stride_words)) return P25_OK;
-    const p25_status s = ensure_device();
-    if (s != P25_OK) return s;
-    P25_LOCK(p);
-    p->dev->prove_dev(d_traces, trace_stride_words, n_proofs, d_pow_starts, d_inputs, input_stride_words, d_status,
-                      (hipStream_t)stream);
-    return P25_OK;
+    p3_no_public(p, "p25_p3_prove_batch_pv_dev");
+    return p3_prove_batch_device(p, d_traces, trace_stride_words, nullptr, n_proofs, d_pow_starts, d_inputs, input_stride_words,
+                                 d_status, stream);
   });
+}
+p25_status p25_p3_prove_batch_pv_dev(p25_p3_prover* p, const uint64_t* d_traces, size_t trace_stride_words,
+                                     const uint64_t* d_public_values, size_t n_proofs, const uint64_t* d_pow_starts,
+                                     uint64_t* d_inputs, size_t input_stride_words, uint32_t* d_status, void* stream) {
+  return p3_prove_batch_device(p, d_traces, trace_stride_words, d_public_values, n_proofs, d_pow_starts, d_inputs,
+                               input_stride_words, d_status, stream);
 }
 // the argument errors of the two verifying entry points; returns false for an empty batch
 static bool p3_verify_args(p25_p3_prover* p, const void* inputs, size_t n_proofs, size_t input_stride, void* status) {

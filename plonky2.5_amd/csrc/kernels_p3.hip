@@ -202,6 +202,10 @@ __global__ __launch_bounds__(64) void k_p3_chain(P3Shape sh, P3Bufs b, uint32_t 
       u64* dst = hdr + 4 * phase;
       if (lane < 4) dst[lane] = root[lane];
       ch.observe_digest(root);
+      if (phase == P3_CH_TRACE) {   // the proof's public values, between the trace root and alpha (p3_prover.cpp)
+        const u64* pub = b.pub + (size_t)g * sh.n_public;
+        for (uint32_t i = 0; i < sh.n_public; i++) ch.observe(pub[i]);
+      }
       const E2 c = ch.sample_ext();
       if (lane == 0) {
         if (phase == P3_CH_TRACE) {
@@ -282,7 +286,8 @@ __global__ __launch_bounds__(256) void k_p3_quotient(P3Shape sh, P3Bufs b) {
   const u64 sel[4] = {0, gl::mul(zhx, gl::inv(gl::sub(x, 1))), gl::mul(zhx, gl::inv(is_trans)), is_trans};
   const E2 alpha = ld_e2(b.state[g].alpha);
   auto load = [&](int next, uint32_t c) -> u64 { return lde[(size_t)c * N2 + (next ? pos1 : p)]; };
-  const E2 acc = run_air<BaseF>(b.prog, sh.n_instr, b.consts, load, sel, alpha);
+  // every lane of the block reads the row of proof g: a plain load at a uniform address
+  const E2 acc = run_air<BaseF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, load, sel, alpha);
   const E2 q = gl::mul(acc, sh.zh_inv[chunk]);
   u64* dst = b.qv + (((size_t)chunk * sh.G + g) * 2) * n + (p & (n - 1));
   dst[0] = q.a;
@@ -342,7 +347,7 @@ __global__ __launch_bounds__(64) void k_p3_identity(P3Shape sh, P3Bufs b) {
   const E2 is_trans = gl::sub(zeta, gl::e2(sh.g_inv));
   const E2 sel[4] = {gl::e2(0), gl::mul(z_h, gl::inv(gl::sub(zeta, gl::e2(1)))), gl::mul(z_h, gl::inv(is_trans)), is_trans};
   auto load = [&](int next, uint32_t c) -> E2 { return ld_e2(open + 2 * ((next ? sh.W : 0) + c)); };
-  const E2 acc = run_air<ExtF>(b.prog, sh.n_instr, b.consts, load, sel, alpha);
+  const E2 acc = run_air<ExtF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, load, sel, alpha);
   const E2 lhs = gl::mul(acc, gl::inv(z_h));
   E2 at_zeta[8];
   for (uint32_t j = 0; j < sh.Q; j++) at_zeta[j] = gl::sub(gl::exp_pow2(gl::mul(zeta, sh.s_inv[j]), sh.k), gl::e2(1));
@@ -485,8 +490,8 @@ __global__ __launch_bounds__(256) void k_p3_pow_search(P3Shape sh, P3Bufs b, con
   }
 }
 
-// Flattening (p3_prover.cpp:423-445).  Block q of a proof writes query q's two sections, block 0 the fixed words as well.  A
-// failed proof's words are zeros.
+// Flattening (p3_prover.cpp:423-445).  Block q of a proof writes query q's two sections, block 0 the fixed words and the
+// public values behind the last query's section as well.  A failed proof's words are zeros, that tail included.
 __global__ __launch_bounds__(64) void k_p3_gather(P3Shape sh, P3Bufs b, u64* __restrict__ out_base, size_t out_stride,
                                                   uint32_t* __restrict__ d_status) {
   const uint32_t qi = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
@@ -499,11 +504,13 @@ __global__ __launch_bounds__(64) void k_p3_gather(P3Shape sh, P3Bufs b, u64* __r
   u64* pa = out + H + (size_t)qi * sh.sz_a;
   const size_t mid = (size_t)H + (size_t)sh.num_queries * sh.sz_a;
   u64* pb = out + mid + 3 + (size_t)qi * sh.sz_b;
+  u64* tail = out + mid + 3 + (size_t)sh.num_queries * sh.sz_b;
   if (qi == 0 && t == 0) d_status[g] = status;
   if (status != 0) {
     if (qi == 0) {
       for (uint32_t i = t; i < H; i += 64) out[i] = 0;
       if (t < 3) out[mid + t] = 0;
+      for (uint32_t i = t; i < sh.n_public; i += 64) tail[i] = 0;
     }
     for (uint32_t i = t; i < sh.sz_a; i += 64) pa[i] = 0;
     for (uint32_t i = t; i < sh.sz_b; i += 64) pb[i] = 0;
@@ -513,6 +520,7 @@ __global__ __launch_bounds__(64) void k_p3_gather(P3Shape sh, P3Bufs b, u64* __r
     for (uint32_t i = t; i < H; i += 64) out[i] = hdr[i];
     if (t < 2) out[mid + t] = s->final_poly[t];
     if (t == 2) out[mid + 2] = s->pow_witness;
+    for (uint32_t i = t; i < sh.n_public; i += 64) tail[i] = b.pub[(size_t)g * sh.n_public + i];
   }
   const uint32_t ix = reinterpret_cast<const uint32_t*>(hdr + sh.o_idx)[qi];
   {

@@ -92,6 +92,7 @@ __global__ __launch_bounds__(64) void k_p3v_transcript(P3VerifyArgs a) {
     }
   };
   ch.observe_digest(proof);
+  for (uint32_t i = 0; i < a.n_public; i++) ch.observe(proof[a.o_public + i]);   // one address per group: the value is uniform in it
   draw(P3VC_ALPHA, 2);
   ch.observe_digest(proof + 4);
   draw(P3VC_ZETA, 2);

@@ -27,10 +27,11 @@ struct ExtF {
   GL_HD static gl::E2 mul(gl::E2 x, gl::E2 y) { return gl::mul(x, y); }
   GL_HD static gl::E2 fold(gl::E2 acc, gl::E2 alpha, gl::E2 c) { return gl::add(gl::mul(acc, alpha), c); }
 };
-// Runs the register program: `load(next, column)` reads the row, the constraints are folded in program order.
+// Runs the register program: `load(next, column)` reads the row, `pub` is the proof's own row of public values (read only
+// by P3_OPND_PUBLIC operands: may be null without them), the constraints are folded in program order.
 template <class F, class Load>
-GL_HD gl::E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u64* __restrict__ consts, Load load,
-                         const typename F::T sel[4], gl::E2 alpha) {
+GL_HD gl::E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u64* __restrict__ consts,
+                     const u64* __restrict__ pub, Load load, const typename F::T sel[4], gl::E2 alpha) {
   typedef typename F::T T;
   T slot[P3_MAX_LIVE];
   auto fetch = [&](uint32_t o) -> T {
@@ -39,6 +40,7 @@ GL_HD gl::E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u
       case P3_OPND_SLOT: return slot[i];
       case P3_OPND_LOCAL: return load(0, i);
       case P3_OPND_NEXT: return load(1, i);
+      case P3_OPND_PUBLIC: return F::cst(pub[i]);
       default: return F::cst(consts[i]);
     }
   };

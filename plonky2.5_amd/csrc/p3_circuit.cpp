@@ -380,40 +380,46 @@ void FibonacciAir::eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) co
 }
 
 // ---------------------------------------------------------------- AIR programs
-int AirProgram::node_degree(uint32_t i) const {
-  std::vector<int> deg(i + 1, 0);
-  for (uint32_t k = 0; k <= i; k++) {
+// Nodes refer to earlier nodes only (validate), so one pass in index order has every operand's degree at hand.  CONST and
+// PUBLIC are the degree-0 leaves; a product's degree saturates, so that no chain of squarings wraps it.
+std::vector<int> AirProgram::node_degrees() const {
+  std::vector<int> deg(nodes.size(), 0);
+  for (size_t k = 0; k < nodes.size(); k++) {
     const Node& nd = nodes[k];
     if (nd.op == LOCAL || nd.op == NEXT) deg[k] = 1;
-    else if (nd.op == CONST) deg[k] = 0;
-    else if (nd.op == MUL) deg[k] = deg[nd.a] + deg[nd.b];
+    else if (nd.op == CONST || nd.op == PUBLIC) deg[k] = 0;
+    else if (nd.op == MUL) deg[k] = std::min(deg[nd.a] + deg[nd.b], DEGREE_SAT);
     else deg[k] = std::max(deg[nd.a], deg[nd.b]);
   }
-  return deg[i];
+  return deg;
 }
 void AirProgram::validate() const {
   if (width < 1 || width > 1024) throw std::invalid_argument("AIR: width out of range");
+  if (n_public < 0 || n_public > MAX_PUBLIC) throw std::invalid_argument("AIR: more than 64 public values (n_public)");
   if (nodes.empty() || constraints.empty()) throw std::invalid_argument("AIR: empty program");
   for (size_t i = 0; i < nodes.size(); i++) {
     const Node& nd = nodes[i];
-    if (nd.op > MUL) throw std::invalid_argument("AIR: unknown node op");
+    if (nd.op > PUBLIC) throw std::invalid_argument("AIR: unknown node op");
     if ((nd.op == LOCAL || nd.op == NEXT) && nd.a >= (uint32_t)width) throw std::invalid_argument("AIR: column out of range");
-    if (nd.op >= ADD && (nd.a >= i || nd.b >= i)) throw std::invalid_argument("AIR: node refers to a later node");
+    if (nd.op == PUBLIC && nd.a >= (uint32_t)n_public) throw std::invalid_argument("AIR: public value index >= n_public");
+    if (nd.op >= ADD && nd.op <= MUL && (nd.a >= i || nd.b >= i)) throw std::invalid_argument("AIR: node refers to a later node");
     if (nd.op == CONST && nd.value >= gl::P) throw std::invalid_argument("AIR: non-canonical constant");
   }
+  const std::vector<int> deg = node_degrees();
   for (const Constraint& c : constraints) {
     if (c.node >= nodes.size() || c.when > TRANSITION) throw std::invalid_argument("AIR: bad constraint");
     // degree <= 2: one quotient chunk, the reference's proof model (serde/proof.rs:41-48).  Degree 3: two chunks -- the
     // reference's verifier (verifier.rs:115-221) and its P3Config (mod.rs:76) already handle any power of two, only
     // `OpenedValues::add_virtual_to` fixes the count; round 5 lifted that.  Degree 4..5 (four chunks) needs log_blowup >= 2,
     // 6..9 (eight) log_blowup 3: the quotient domain 7*H_{n 2^lqd} must lie inside the LDE domain (round 6).
-    if (node_degree(c.node) + (c.when == ALWAYS ? 0 : 1) > 9)
+    if (deg[c.node] + (c.when == ALWAYS ? 0 : 1) > 9)
       throw std::invalid_argument("AIR: constraint degree > 9 needs more than eight quotient chunks");
   }
 }
 int AirProgram::max_constraint_degree() const {
+  const std::vector<int> deg = node_degrees();
   int d = 1;
-  for (const Constraint& c : constraints) d = std::max(d, node_degree(c.node) + (c.when == ALWAYS ? 0 : 1));
+  for (const Constraint& c : constraints) d = std::max(d, deg[c.node] + (c.when == ALWAYS ? 0 : 1));
   return d;
 }
 int AirProgram::log_quotient_degree() const {
@@ -442,14 +448,16 @@ AirProgram AirProgram::fibonacci() {
 namespace {
 struct CircuitExtOps {
   CircuitBuilder& cb;
+  const std::vector<Ext>& public_values;
   Ext cst(u64 v) { return p3_field_to_arr(cb, p3_constant(cb, v)); }
+  Ext pub(uint32_t i) { return public_values.at(i); }
   Ext add(const Ext& x, const Ext& y) { return p3_ext_add(cb, x, y); }
   Ext sub(const Ext& x, const Ext& y) { return p3_ext_sub(cb, x, y); }
   Ext mul(const Ext& x, const Ext& y) { return p3_ext_mul(cb, x, y); }
 };
 }  // namespace
 void ProgramAir::eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const {
-  CircuitExtOps ops{cb};
+  CircuitExtOps ops{cb, folder.public_values};
   const Ext sel[4] = {Ext{}, folder.is_first_row, folder.is_last_row, folder.is_transition};
   prog.fold<Ext>(folder.trace_local, folder.trace_next, sel, ops, [&](const Ext& c) { folder.assert_zero(cb, c); });
 }
@@ -658,6 +666,15 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
     challenger.sponge_state.assign(st.begin(), st.end());
   }
   P3ProofTarget proof = add_virtual_proof(cb, config);
+  // The proof's public values: input targets behind the proof's words (the tail of the flat input), exposed as the
+  // circuit's public inputs.  None for the reference's AIRs, whose circuit this leaves as it was.
+  std::vector<Target> public_values;
+  for (int i = 0; i < air.n_public(); i++) {
+    Target t = cb.add_virtual_target();
+    cb.input_targets.push_back(t);
+    public_values.push_back(t);
+  }
+  if (!public_values.empty()) cb.register_public_inputs(public_values);
 
   const int degree_bits = proof.degree_bits;
   const size_t degree = (size_t)1 << degree_bits;
@@ -691,6 +708,8 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
   if (!valid_shape) throw std::logic_error("Invalid Proof Shape");  // verifier.rs:131-133
 
   p3_observe(cb, challenger, proof.trace_commit.begin(), proof.trace_commit.end());
+  // uni-stark's `challenger.observe_slice(public_values)`: between the trace commitment and alpha (unpinned: include/p25.h)
+  p3_observe(cb, challenger, public_values.begin(), public_values.end());
   Ext alpha = p3_sample_ext(cb, challenger);
   p3_observe(cb, challenger, proof.quotient_commit.begin(), proof.quotient_commit.end());
   Ext zeta = p3_sample_ext(cb, challenger);
@@ -749,6 +768,7 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
   VerifierConstraintFolder folder;
   folder.trace_local = proof.trace_local;
   folder.trace_next = proof.trace_next;
+  for (Target t : public_values) folder.public_values.push_back(p3_field_to_arr(cb, t));
   folder.is_first_row = sels.is_first_row;
   folder.is_last_row = sels.is_last_row;
   folder.is_transition = sels.is_transition;

@@ -51,6 +51,7 @@ struct P3ProofTarget {
 // src/p3/air.rs:20-27
 struct VerifierConstraintFolder {
   std::vector<Ext> trace_local, trace_next;
+  std::vector<Ext> public_values;   // this library's extension (AirProgram::PUBLIC): base elements embedded in the extension
   Ext is_first_row, is_last_row, is_transition, alpha, accumulator;
   // air.rs:69-88, 90-118
   void assert_zero(CircuitBuilder& cb, Ext x);
@@ -62,6 +63,8 @@ struct Air {
   virtual ~Air() {}
   virtual std::string name() const = 0;
   virtual int width() const = 0;
+  // public values of a proof (uni-stark's `public_values`); the reference's trait has none
+  virtual int n_public() const { return 0; }
   virtual void eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const = 0;
 };
 // src/p3/mod.rs:160-221 (the test's FibonacciAir)
@@ -78,23 +81,29 @@ struct FibonacciAir : Air {
 // otherwise assert_zero(selector * node).  Used by BOTH sides of the path's input: the in-circuit
 // verifier (ProgramAir below) and the native plonky3 prover (p3_prover.h).
 struct AirProgram {
-  enum Op : uint32_t { LOCAL = 0, NEXT = 1, CONST = 2, ADD = 3, SUB = 4, MUL = 5 };
+  // PUBLIC(a): public value a < n_public of the proof (uni-stark's `builder.public_values()[a]`): degree 0 like CONST
+  enum Op : uint32_t { LOCAL = 0, NEXT = 1, CONST = 2, ADD = 3, SUB = 4, MUL = 5, PUBLIC = 6 };
+  static constexpr int MAX_PUBLIC = 64;   // P25_AIR_MAX_PUBLIC
   enum When : uint32_t { ALWAYS = 0, FIRST_ROW = 1, LAST_ROW = 2, TRANSITION = 3 };
   struct Node {
-    uint32_t op, a, b;  // LOCAL/NEXT: a = column; ADD/SUB/MUL: a, b = earlier node indices
+    uint32_t op, a, b;  // LOCAL/NEXT: a = column; PUBLIC: a = index; ADD/SUB/MUL: a, b = earlier node indices
     u64 value;          // CONST
   };
   struct Constraint {
     uint32_t node, when;
   };
   int width = 0;
+  int n_public = 0;
   std::vector<Node> nodes;
   std::vector<Constraint> constraints;
-  // throws std::invalid_argument on malformed programs and on constraint degree > 9 (selector included; eight quotient
-  // chunks).  The reference's proof model carries exactly one chunk (serde/proof.rs:41-48, degree <= 2); more chunks are this
+  // throws std::invalid_argument on malformed programs (a PUBLIC index >= n_public and n_public > MAX_PUBLIC among them)
+  // and on constraint degree > 9 (selector included; eight quotient chunks).  The reference's proof model carries exactly one chunk (serde/proof.rs:41-48, degree <= 2); more chunks are this
   // library's extension of it, and log_quotient_degree() of them must not exceed the FRI log_blowup (checked by the callers).
   void validate() const;
-  int node_degree(uint32_t i) const;
+  // the degree of every node in one pass over the DAG, saturating at DEGREE_SAT (a chain of squarings overflows any integer)
+  static constexpr int DEGREE_SAT = 1 << 16;
+  std::vector<int> node_degrees() const;
+  int node_degree(uint32_t i) const { return node_degrees()[i]; }
   // max over the constraints of their degree with the selector's counted, and uni-stark's get_log_quotient_degree of it:
   // log2_ceil(max(degree, 2) - 1) -- 0 for degree <= 2, 1 for 3, 2 for 4..5, 3 for 6..9
   int max_constraint_degree() const;
@@ -103,7 +112,7 @@ struct AirProgram {
   static AirProgram fibonacci();
 
   // Generic evaluation, nodes computed on demand in constraint order (so that the circuit form emits
-  // its gates in the order the reference's hand-written `eval` does).  ops: cst(u64), add, sub, mul.
+  // its gates in the order the reference's hand-written `eval` does).  ops: cst(u64), pub(index), add, sub, mul.
   template <class T, class Ops, class Emit>
   void fold(const std::vector<T>& local, const std::vector<T>& next, const T sel[4], Ops& ops, Emit&& emit) const {
     std::vector<T> val(nodes.size());
@@ -124,6 +133,8 @@ struct AirProgram {
           val[i] = next[nd.a];
         } else if (nd.op == CONST) {
           val[i] = ops.cst(nd.value);
+        } else if (nd.op == PUBLIC) {
+          val[i] = ops.pub(nd.a);
         } else {
           if (!have[nd.a]) {
             stack.push_back(nd.a);
@@ -147,11 +158,14 @@ struct ProgramAir : Air {
   explicit ProgramAir(AirProgram p) : prog(std::move(p)) { prog.validate(); }
   std::string name() const override { return "Program"; }
   int width() const override { return prog.width; }
+  int n_public() const override { return prog.n_public; }
   void eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const override;
 };
 
 // CircuitBuilderP3Arithmetic::p3_verify_proof (src/p3/mod.rs:66-94).  Registers the proof's virtual
-// targets as the circuit's per-proof inputs (cb.input_targets, `add_virtual_to` order).
+// targets as the circuit's per-proof inputs (cb.input_targets, `add_virtual_to` order).  An AIR with public values adds
+// air.n_public() input targets behind the proof's, observes them after the trace commitment (where uni-stark's verifier has
+// `challenger.observe_slice(public_values)`) and registers them as the circuit's public inputs, in order.
 P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const Air& air);
 
 // gadget-level entry points (src/p3/mod.rs:40-45, 96-147), exposed for the gadget tests

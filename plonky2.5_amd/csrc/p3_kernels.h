@@ -8,8 +8,9 @@
 namespace p25 {
 
 // ---- the AIR as a register program (compiled by P3AirDevice::compile from the AirProgram DAG) ----
-// Operands: kind << 28 | index.  LOCAL / NEXT / CONST nodes never take a slot: they are re-read where they are used.
-enum : uint32_t { P3_OPND_SLOT = 0, P3_OPND_LOCAL = 1, P3_OPND_NEXT = 2, P3_OPND_CONST = 3 };
+// Operands: kind << 28 | index.  LOCAL / NEXT / CONST / PUBLIC nodes never take a slot: they are re-read where they are
+// used (PUBLIC: from the proof's own row of public values).
+enum : uint32_t { P3_OPND_SLOT = 0, P3_OPND_LOCAL = 1, P3_OPND_NEXT = 2, P3_OPND_CONST = 3, P3_OPND_PUBLIC = 4 };
 enum : uint32_t { P3_OP_ADD = 3, P3_OP_SUB = 4, P3_OP_MUL = 5, P3_OP_EMIT = 6 };  // ADD..MUL as AirProgram::Op
 struct P3Instr {
   uint32_t op, dst /* slot; EMIT: the constraint's `when` */, a, b;
@@ -48,6 +49,7 @@ struct P3Shape {
   uint32_t k, B, L, lqd, Q, W, num_queries, pow_bits;
   uint32_t n_instr, tail_round;   // FRI rounds >= tail_round run in k_p3_fri_tail
   uint32_t G;                     // proofs of this group
+  uint32_t n_public;              // public values per proof: the tail of its flat words
   u64 w[26], w_inv[26];           // primitive 2^i-th roots of unity and their inverses
   u64 zh[8], zh_inv[8];           // x^n - 1 on the quotient coset, by chunk
   u64 s_inv[8];                   // 1 / s_c
@@ -66,6 +68,9 @@ struct P3Bufs {
   const P3Instr* prog;
   const u64* consts;
   const u64* zfirst_inv;                     // [Q][Q]: 1 / Z_{D_j}(s_c)
+  // [G][n_public]: the public values of THIS GROUP's proofs -- the batch's array advanced by the group's first proof, like
+  // every other per-proof pointer of a group (blockIdx.y counts inside the group); null when n_public = 0
+  const u64* pub;
 };
 
 // words of level l of a tree over h leaves (levels concatenated, 4 words per digest), FRI layer r, FRI tree r
@@ -104,17 +109,19 @@ class P3ProverDev {
   P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int num_queries, int pow_bits);
   ~P3ProverDev();
   const P3Config& config() const { return cfg_; }
-  size_t num_inputs() const { return cfg_.num_inputs(); }
+  // words of a flat proof: the proof's in `add_virtual_to` order, then its n_public public values
+  size_t num_inputs() const { return cfg_.num_inputs() + shape_.n_public; }
+  uint32_t n_public() const { return shape_.n_public; }
   size_t trace_words() const { return ((size_t)1 << cfg_.log_trace_height) * (size_t)cfg_.trace_width; }
   size_t scratch_words_per_proof() const;
   size_t group_size(size_t n_proofs) const;
   void set_scratch_budget(size_t bytes) { budget_bytes_ = bytes ? bytes : P3_SCRATCH_BUDGET_BYTES; }
-  // enqueue-only on `st`
-  void prove_dev(const u64* d_traces, size_t trace_stride, size_t n_proofs, const u64* d_pow_starts, u64* d_inputs,
-                 size_t input_stride, uint32_t* d_status, hipStream_t st);
+  // enqueue-only on `st`.  d_public: [n_proofs][n_public], packed (unread when n_public = 0)
+  void prove_dev(const u64* d_traces, size_t trace_stride, const u64* d_public, size_t n_proofs, const u64* d_pow_starts,
+                 u64* d_inputs, size_t input_stride, uint32_t* d_status, hipStream_t st);
   // host buffers (checked by the caller): copies, proves on the handle's own stream, waits
-  void prove_host(const u64* traces, size_t n_proofs, const u64* pow_starts, u64* inputs_out, size_t input_stride,
-                  int32_t* statuses);
+  void prove_host(const u64* traces, const u64* public_values, size_t n_proofs, const u64* pow_starts, u64* inputs_out,
+                  size_t input_stride, int32_t* statuses);
   void sync();
   // The verifying side (p3_verify_dev.hip, kernels_p3_verify.hip): src/p3/verifier.rs on flat proofs of this handle's AIR and
   // shape.  Takes none of the proving scratch; its own buffer holds verify_scratch_words_per_proof() words per proof of a
@@ -133,8 +140,8 @@ class P3ProverDev {
 
  private:
   void ensure_impl();
-  void run_group(const u64* d_traces, size_t trace_stride, uint32_t G, const u64* d_pow_starts, u64* d_inputs,
-                 size_t input_stride, uint32_t* d_status, hipStream_t st);
+  void run_group(const u64* d_traces, size_t trace_stride, const u64* d_public, uint32_t G, const u64* d_pow_starts,
+                 u64* d_inputs, size_t input_stride, uint32_t* d_status, hipStream_t st);
   P3Config cfg_;
   P3AirDevice prog_;
   P3Shape shape_;

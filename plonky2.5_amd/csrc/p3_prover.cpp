@@ -156,13 +156,17 @@ Tree commit(const std::vector<u64>& rows, size_t width, int threads) {
 
 namespace {
 struct BaseOps {
+  const std::vector<u64>& pv;
   u64 cst(u64 v) { return v; }
+  u64 pub(uint32_t i) { return pv[i]; }
   u64 add(u64 x, u64 y) { return gl::add(x, y); }
   u64 sub(u64 x, u64 y) { return gl::sub(x, y); }
   u64 mul(u64 x, u64 y) { return gl::mul(x, y); }
 };
 struct ExtOps {
+  const std::vector<u64>& pv;
   E2 cst(u64 v) { return gl::e2(v); }
+  E2 pub(uint32_t i) { return gl::e2(pv[i]); }
   E2 add(E2 x, E2 y) { return gl::add(x, y); }
   E2 sub(E2 x, E2 y) { return gl::sub(x, y); }
   E2 mul(E2 x, E2 y) { return gl::mul(x, y); }
@@ -188,6 +192,11 @@ std::vector<u64> p3_prove_fibonacci(const P3ProveParams& prm, P3Config& cfg) {
 
 std::vector<u64> p3_prove_air(const AirProgram& air, const std::vector<std::vector<u64>>& col, const P3ProveParams& prm,
                               P3Config& cfg) {
+  return p3_prove_air_pv(air, col, std::vector<u64>(), prm, cfg);
+}
+
+std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::vector<u64>>& col, const std::vector<u64>& pub,
+                                 const P3ProveParams& prm, P3Config& cfg) {
   // FriConfig.log_blowup (src/p3/mod.rs:242-246; verifier.rs uses config.log_blowup generically): the LDE domain is
   // 7*H_{n 2^B}, B = 1..4 (what p25_circuit_build_p3_verifier accepts); B = 1 is the reference's artifact, B = 2, 3 hold AIRs of
   // constraint degree up to 5 / 9 (four / eight chunks)
@@ -200,6 +209,9 @@ std::vector<u64> p3_prove_air(const AirProgram& air, const std::vector<std::vect
   const u64 w_n = gl::root_of_unity(k), w_2n = gl::root_of_unity(L);
   const int W = air.width;
   if ((int)col.size() != W) throw std::invalid_argument("p3_prove: trace width does not match the AIR");
+  if ((int)pub.size() != air.n_public) throw std::invalid_argument("p3_prove: the AIR takes n_public public values");
+  for (u64 v : pub)
+    if (v >= gl::P) throw std::invalid_argument("p3_prove: non-canonical public value");
   for (auto& c : col) {
     if (c.size() != n) throw std::invalid_argument("p3_prove: trace height does not match log_n");
     for (u64 v : c)
@@ -219,6 +231,7 @@ std::vector<u64> p3_prove_air(const AirProgram& air, const std::vector<std::vect
 
   Challenger ch;
   ch.observe_digest(trace_tree.root());
+  for (u64 v : pub) ch.observe(v);   // uni-stark's challenger.observe_slice(public_values): unpinned (include/p25.h)
   const E2 alpha = ch.sample_ext();
 
   // Quotient chunks: 2^lqd of them, lqd = log2_ceil(max constraint degree - 1) with the selector's degree counted (uni-stark's
@@ -243,7 +256,7 @@ std::vector<u64> p3_prove_air(const AirProgram& air, const std::vector<std::vect
       zh_inv[r] = gl::inv(zh[r]);
     }
     u64 x = gl::GENERATOR;
-    BaseOps ops;
+    BaseOps ops{pub};
     std::vector<u64> loc(W), nxt(W);
     for (size_t j = 0; j < nq; j++, x = gl::mul(x, w_q)) {
       const size_t i0 = lde_step * j, i1 = (lde_step * j + row_step) % N2;   // the next ROW is x w_n = 2^B LDE points on
@@ -308,7 +321,7 @@ std::vector<u64> p3_prove_air(const AirProgram& air, const std::vector<std::vect
     E2 z_h = gl::sub(gl::exp_pow2(un, k), gl::e2(1));
     E2 is_trans = gl::sub(un, gl::e2(gl::inv(w_n)));
     const E2 sel[4] = {gl::e2(0), gl::mul(z_h, gl::inv(gl::sub(un, gl::e2(1)))), gl::mul(z_h, gl::inv(is_trans)), is_trans};
-    ExtOps ops;
+    ExtOps ops{pub};
     E2 acc = gl::e2(0);
     air.fold<E2>(t_local, t_next, sel, ops, [&](E2 c) { acc = gl::add(gl::mul(acc, alpha), c); });
     E2 lhs = gl::mul(acc, gl::inv(z_h));
@@ -444,6 +457,7 @@ std::vector<u64> p3_prove_air(const AirProgram& air, const std::vector<std::vect
     for (auto& d : quot_tree.prove(ix)) push_d(d);
   }
   if (out.size() != cfg.num_inputs()) throw std::logic_error("p3 prover: flattened size mismatch");
+  out.insert(out.end(), pub.begin(), pub.end());   // plonky3's Proof holds no public values: they travel behind it
   return out;
 }
 

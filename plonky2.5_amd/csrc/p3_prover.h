@@ -37,6 +37,11 @@ std::vector<u64> p3_prove_fibonacci(const P3ProveParams& prm, P3Config& cfg_out)
 // std::logic_error("quotient identity ...") if the trace does not satisfy the AIR.
 std::vector<u64> p3_prove_air(const AirProgram& air, const std::vector<std::vector<u64>>& col, const P3ProveParams& prm,
                               P3Config& cfg_out);
+// The same with the proof's public values (air.n_public of them, each < p): observed by the challenger right after the trace
+// commitment, read by the AIR's PUBLIC nodes, and appended to the flat vector behind the proof's words (cfg_out.num_inputs()
+// + air.n_public words in all).  With no public values the words are p3_prove_air's.
+std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::vector<u64>>& col, const std::vector<u64>& pub,
+                                 const P3ProveParams& prm, P3Config& cfg_out);
 // serde-JSON text in the reference's format (proof.rs:16-19: field elements are {"value": u64})
 std::string p3_inputs_to_json(const std::vector<u64>& inputs, const P3Config& cfg);
 

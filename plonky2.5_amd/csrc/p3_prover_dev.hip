@@ -7,14 +7,14 @@
 namespace p25 {
 
 // ---------------------------------------------------------------------------------------------------------------------
-// AirProgram -> register program.  Nodes are visited in the order AirProgram::fold evaluates them; a LOCAL / NEXT / CONST
-// node becomes an operand, an arithmetic node takes a slot from its evaluation to its last use.
+// AirProgram -> register program.  Nodes are visited in the order AirProgram::fold evaluates them; a LOCAL / NEXT / CONST /
+// PUBLIC node becomes an operand, an arithmetic node takes a slot from its evaluation to its last use.
 // ---------------------------------------------------------------------------------------------------------------------
 P3AirDevice P3AirDevice::compile(const AirProgram& air) {
   typedef AirProgram A;
   const size_t N = air.nodes.size();
   P3AirDevice out;
-  auto is_leaf = [&](uint32_t i) { return air.nodes[i].op <= A::CONST; };
+  auto is_leaf = [&](uint32_t i) { return air.nodes[i].op <= A::CONST || air.nodes[i].op == A::PUBLIC; };
   // uses of every arithmetic node by the nodes and constraints that are evaluated
   std::vector<uint32_t> uses(N, 0);
   std::vector<char> seen(N, 0);
@@ -43,6 +43,7 @@ P3AirDevice P3AirDevice::compile(const AirProgram& air) {
     const A::Node& nd = air.nodes[i];
     if (nd.op == A::LOCAL) return (P3_OPND_LOCAL << 28) | nd.a;
     if (nd.op == A::NEXT) return (P3_OPND_NEXT << 28) | nd.a;
+    if (nd.op == A::PUBLIC) return (P3_OPND_PUBLIC << 28) | nd.a;
     if (nd.op == A::CONST) {
       if (!have[i]) {
         have[i] = 1;
@@ -132,6 +133,7 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
   s.k = k; s.B = B; s.L = L; s.lqd = lqd; s.Q = (uint32_t)Q; s.W = W;
   s.num_queries = num_queries; s.pow_bits = pow_bits;
   s.n_instr = (uint32_t)prog_.instr.size();
+  s.n_public = (uint32_t)air.n_public;
   // FRI layers of at most 2^P3_TAIL_LOG values fold in one workgroup per proof
   s.tail_round = L > P3_TAIL_LOG ? std::min(k, L - P3_TAIL_LOG) : 0;
   for (int i = 0; i < 26; i++) {
@@ -160,7 +162,7 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
   s.sz_a = 0;
   for (int r = 0; r < k; r++) s.sz_a += 2 + 4 * (L - r - 1);
   s.sz_b = W + 4 * L + 2 * (uint32_t)Q + 4 * L;
-  if ((size_t)s.hdr_words + (size_t)num_queries * (s.sz_a + s.sz_b) + 3 != cfg_.num_inputs())
+  if ((size_t)s.hdr_words + (size_t)num_queries * (s.sz_a + s.sz_b) + 3 != cfg_.num_inputs())   // the public values follow
     throw std::logic_error("p3 device prover: flattened size mismatch");
   budget_bytes_ = P3_SCRATCH_BUDGET_BYTES;
 }
@@ -230,8 +232,8 @@ void P3ProverDev::ensure_impl() {
   }
 }
 
-void P3ProverDev::prove_dev(const u64* d_traces, size_t trace_stride, size_t n_proofs, const u64* d_pow_starts, u64* d_inputs,
-                            size_t input_stride, uint32_t* d_status, hipStream_t st) {
+void P3ProverDev::prove_dev(const u64* d_traces, size_t trace_stride, const u64* d_public, size_t n_proofs,
+                            const u64* d_pow_starts, u64* d_inputs, size_t input_stride, uint32_t* d_status, hipStream_t st) {
   if (!n_proofs) return;
   ensure_impl();
   const size_t G = group_size(n_proofs), need = G * scratch_words_per_proof();
@@ -245,14 +247,16 @@ void P3ProverDev::prove_dev(const u64* d_traces, size_t trace_stride, size_t n_p
   P3CallRecord record{impl_, st};
   for (size_t g0 = 0; g0 < n_proofs; g0 += G) {
     const size_t cnt = std::min(G, n_proofs - g0);
-    run_group(d_traces + g0 * trace_stride, trace_stride, (uint32_t)cnt, d_pow_starts ? d_pow_starts + g0 : nullptr,
-              d_inputs + g0 * input_stride, input_stride, d_status + g0, st);
+    // every per-proof array advances by the group's first proof: the kernels index inside the group
+    run_group(d_traces + g0 * trace_stride, trace_stride, shape_.n_public ? d_public + g0 * shape_.n_public : nullptr,
+              (uint32_t)cnt, d_pow_starts ? d_pow_starts + g0 : nullptr, d_inputs + g0 * input_stride, input_stride,
+              d_status + g0, st);
   }
   P25_HIP(hipGetLastError());
 }
 
-void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, uint32_t G, const u64* d_pow_starts, u64* d_inputs,
-                            size_t input_stride, uint32_t* d_status, hipStream_t st) {
+void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, const u64* d_public, uint32_t G, const u64* d_pow_starts,
+                            u64* d_inputs, size_t input_stride, uint32_t* d_status, hipStream_t st) {
   P3Shape s = shape_;
   s.G = G;
   const int k = s.k, B = s.B;
@@ -265,6 +269,7 @@ void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, uint32_t G
   b.prog = reinterpret_cast<const P3Instr*>(impl_->prog.p);
   b.consts = impl_->consts.p;
   b.zfirst_inv = impl_->zfirst.p;
+  b.pub = d_public;
 
   // the LDE on shift * <w_{n 2^B}> in bit-reversed order; 16 cosets as two interleaved sets of 8 (coset 2 c + e of the
   // first kind is coset c of the set with shift * w^e, and lands in half e of the bit-reversed output)
@@ -304,16 +309,17 @@ void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, uint32_t G
   p3_launch_gather(s, b, d_inputs, input_stride, d_status, st);    // :423-445
 }
 
-void P3ProverDev::prove_host(const u64* traces, size_t n_proofs, const u64* pow_starts, u64* inputs_out, size_t input_stride,
-                             int32_t* statuses) {
+void P3ProverDev::prove_host(const u64* traces, const u64* public_values, size_t n_proofs, const u64* pow_starts,
+                             u64* inputs_out, size_t input_stride, int32_t* statuses) {
   if (!n_proofs) return;
-  const size_t tw = trace_words(), ni = num_inputs();
+  const size_t tw = trace_words(), ni = num_inputs(), np = shape_.n_public;
   ensure_impl();
   hipStream_t st = impl_->host_stream();
-  DevMem d_traces(n_proofs * tw), d_pow(n_proofs), d_out(n_proofs * ni), d_status((n_proofs + 1) / 2);
+  DevMem d_traces(n_proofs * tw), d_pub(n_proofs * np), d_pow(n_proofs), d_out(n_proofs * ni), d_status((n_proofs + 1) / 2);
   P25_HIP(hipMemcpyAsync(d_traces.p, traces, n_proofs * tw * 8, hipMemcpyHostToDevice, st));
+  if (np) P25_HIP(hipMemcpyAsync(d_pub.p, public_values, n_proofs * np * 8, hipMemcpyHostToDevice, st));
   if (pow_starts) P25_HIP(hipMemcpyAsync(d_pow.p, pow_starts, n_proofs * 8, hipMemcpyHostToDevice, st));
-  prove_dev(d_traces.p, tw, n_proofs, pow_starts ? d_pow.p : nullptr, d_out.p, ni, reinterpret_cast<uint32_t*>(d_status.p), st);
+  prove_dev(d_traces.p, tw, np ? d_pub.p : nullptr, n_proofs, pow_starts ? d_pow.p : nullptr, d_out.p, ni, reinterpret_cast<uint32_t*>(d_status.p), st);
   // the input_stride - num_inputs words behind a proof stay untouched
   P25_HIP(hipMemcpy2DAsync(inputs_out, input_stride * 8, d_out.p, ni * 8, ni * 8, n_proofs, hipMemcpyDeviceToHost, st));
   std::vector<uint32_t> hs(n_proofs);

@@ -28,6 +28,8 @@ P3VerifyArgs P3ProverDev::verify_args() const {
   a.k = s.k; a.B = s.B; a.L = s.L; a.Q = s.Q; a.W = s.W;
   a.num_queries = s.num_queries; a.pow_bits = s.pow_bits; a.n_instr = s.n_instr;
   a.num_inputs = (uint32_t)num_inputs();
+  a.n_public = s.n_public;
+  a.o_public = a.num_inputs - s.n_public;
   a.o_open = 8;
   a.o_roots = 8 + 4 * s.W + 4 * s.Q;
   a.o_qp = s.hdr_words;
@@ -38,7 +40,7 @@ P3VerifyArgs P3ProverDev::verify_args() const {
   a.sz_b = s.sz_b;
   a.c_idx = P3VC_BETAS + 2 * s.k;
   a.chal_stride = a.c_idx + s.num_queries;
-  if ((size_t)a.o_qo + (size_t)s.num_queries * s.sz_b != num_inputs() || a.o_roots + 4 * s.k != s.hdr_words ||
+  if ((size_t)a.o_qo + (size_t)s.num_queries * s.sz_b != a.o_public || a.o_roots + 4 * s.k != s.hdr_words ||
       p3v_round_off(a, s.k) != s.sz_a || (size_t)a.chal_stride + 2 * (size_t)s.num_queries * s.k != verify_scratch_words_per_proof())
     throw std::logic_error("p3 verifier: layout out of step with the proof's");
   a.w_L = s.w[s.L];

@@ -1,13 +1,14 @@
 // The plonky3 verifier's per-lane work, host and device: the verifier of src/p3/verifier.rs (the reference states it as a
 // circuit) as plain functions of a batch description.  The kernels of kernels_p3_verify.hip only map lanes to (tree, proof,
 // query) and merge the keys; everything here also compiles for the host (tests/native/p3_verify_lanes.cpp).
-//   transcript_lane   challenger.rs:70-169 in the order of verifier.rs:135-139, 258, 363-382, and the scan for words >= p;
+//   transcript_lane   challenger.rs:70-169 in the order of verifier.rs:135-139, 258, 363-382 (the proof's public values, if
+//                     its AIR has any, observed behind the trace root), and the scan for words >= p;
 //                     the device runs k_p3v_transcript (cooperative permutation) instead, this is its plain statement
 //   identity_lane     verifier.rs:169-239: the quotient identity at zeta
 //   fold_lane         verifier.rs:296-338 (reduced openings) and :419-518 (fold chain) of one query
 //   merkle_lane       commit.rs:62-129 for one tree of one query: trace batch, quotient batch or a FRI round
 //   verdict_lane      key -> P25_P3_REJECT_*
-// A proof is the flat input vector of include/p25.h (`add_virtual_to` order, proof.rs:357-373).
+// A proof is the flat input vector of include/p25.h (`add_virtual_to` order, proof.rs:357-373, then its public values).
 #pragma once
 #include "p3_air_run.h"
 #include "poseidon2.h"
@@ -47,6 +48,9 @@ struct P3VerifyArgs {
   // final polynomial, the PoW witness, the queries' input openings (sz_b words each)
   uint32_t o_open, o_roots, o_qp, sz_a, o_final, o_pow, o_qo, sz_b;
   uint32_t c_idx, chal_stride;
+  // the proof's public values: its last n_public words (num_inputs counts them), observed after the trace root and read
+  // by the AIR's PUBLIC operands
+  uint32_t n_public, o_public;
   u64 w_L, w_L_inv;    // primitive root of the LDE domain and its inverse
   u64 w_n, g_inv;      // generator of the trace domain and its inverse
   u64 neg2_inv;        // 1 / -2
@@ -103,6 +107,7 @@ GL_HD uint32_t transcript_lane(const P3VerifyArgs& a, uint32_t p) {
     for (uint32_t i = 0; i < n; i++) chal[slot + i] = ch.sample();
   };
   for (int i = 0; i < 4; i++) ch.observe(proof[i]);
+  for (uint32_t i = 0; i < a.n_public; i++) ch.observe(proof[a.o_public + i]);
   draw(P3VC_ALPHA, 2);
   for (int i = 0; i < 4; i++) ch.observe(proof[4 + i]);
   draw(P3VC_ZETA, 2);
@@ -121,7 +126,8 @@ GL_HD uint32_t transcript_lane(const P3VerifyArgs& a, uint32_t p) {
 
 // The quotient identity at zeta (verifier.rs:169-239): folded constraints * inv_zeroifier == sum_c zps_c * chunk_c(zeta).
 GL_HD bool identity_lane(const P3VerifyArgs& a, uint32_t p) {
-  const u64* open = a.proofs + (size_t)p * a.stride + a.o_open;
+  const u64* proof = a.proofs + (size_t)p * a.stride;
+  const u64* open = proof + a.o_open;
   const u64* chal = a.chal + (size_t)p * a.chal_stride;
   const E2 zeta = ld(chal + P3VC_ZETA), alpha = ld(chal + P3VC_ALPHA);
   // two_adic.rs:100-147: selectors at a point off the domain
@@ -130,7 +136,7 @@ GL_HD bool identity_lane(const P3VerifyArgs& a, uint32_t p) {
   const E2 sel[4] = {gl::e2(0), gl::mul(z_h, gl::inv(gl::sub(zeta, gl::e2(1)))), gl::mul(z_h, gl::inv(is_trans)), is_trans};
   const uint32_t W = a.W;
   auto load = [&](int next, uint32_t c) -> E2 { return ld(open + 2 * ((next ? W : 0) + c)); };
-  const E2 acc = run_air<ExtF>(a.prog, a.n_instr, a.consts, load, sel, alpha);
+  const E2 acc = run_air<ExtF>(a.prog, a.n_instr, a.consts, proof + a.o_public, load, sel, alpha);
   const E2 lhs = gl::mul(acc, gl::inv(z_h));
   // zps_c = prod_{j != c} Z_{D_j}(zeta) / Z_{D_j}(s_c),  Z_{D_j}(x) = (x / s_j)^n - 1
   E2 at_zeta[8];

@@ -227,8 +227,37 @@ p25_status p25_circuit_build_p3_verifier(const p25_p3_config* cfg, int32_t air, 
  *              outer proof with P25_ERR_WITNESS_CONFLICT.
  *   Proving    p25_p3_prove_air_pv, p25_p3_prove_batch_pv[_dev].  The forms without public values (p25_p3_prove_air[_ex],
  *              p25_p3_prove_batch[_dev]) return P25_ERR_INVALID_ARG for an AIR with n_public > 0; the message names the _pv
- *              form.  p25_p3_verify_batch[_dev] read the values from the proof's tail. */
+ *              form.  p25_p3_verify_batch[_dev] read the values from the proof's tail.
+ *
+ * PERIODIC COLUMNS (this library's extension, like public values: the reference's `Air` trait, src/p3/air.rs:10-27, has
+ * none; ethSTARK and Winterfell call them so).  A column of period P = 2^log_period is part of the AIR like a constant:
+ * known values v[0..P), each < p, that differ from row to row -- round constants of a hash chain, an "every 4th row"
+ * selector, a step counter modulo P, a small ROM.  It is neither committed nor opened, so the proof's words,
+ * p25_p3_config, num_inputs, the JSON forms and the transcript are what they were; like a CONST, the AIR is not observed.
+ *   Value      on trace row i the column is v[i mod P].  Over the trace domain <w_n>, n = 2^log_n, it is the polynomial
+ *              c(x) = q(x^(n/P)), q the interpolant of degree < P with q(w_P^j) = v[j], w_P = w_n^(n/P).  Its degree is
+ *              n - n/P <= n - 1: it COUNTS AS DEGREE 1, exactly like LOCAL, towards log_quotient_degree.
+ *   Node       node.op 7 PERIODIC(a): column a < n_columns at the CURRENT row.  There is no next-row form: the column
+ *              rotated by one place gives it.
+ *   Limits     at most P25_AIR_MAX_PERIODIC columns; 1 <= log_period <= P25_AIR_MAX_LOG_PERIOD and <= log_n (with
+ *              log_n <= 8 a column of period n is a full fixed column).  An index >= n_columns, a log_period of 0, above 8
+ *              or above log_n, a value >= p and more than 32 columns are P25_ERR_INVALID_ARG; the message names the limit.
+ *   Prover     on the quotient coset 7 H_{n Q}, Q = 2^log_quotient_degree, the value at x_j = 7 w_{nQ}^j is
+ *              T[j mod (P Q)], T[r] = q(7^(n/P) u^r), u = w_{nQ}^(n/P): a table of P Q words per column, made on the host
+ *              when the prover handle is created.
+ *   At zeta    the prover's self-check, the device verifier and the verifier circuit compute c(zeta) = q(zeta^(n/P)):
+ *              log_n - log_period squarings in the extension, then Horner over q's P base-field coefficients.  The circuit
+ *              does so with arithmetic gates and the coefficients as constants: columns in index order, directly before
+ *              the AIR's constraints.  A proof checked against other column values fails the identity: REJECT_CONSTRAINTS
+ *              from p25_p3_verify_batch[_dev], P25_ERR_WITNESS_CONFLICT from the outer prover.
+ *   Interface  p25_air cannot grow (old callers pass its old size), so the columns travel beside it in p25_air_periodic,
+ *              taken by p25_p3_prove_air_pc, p25_p3_prover_create_pc and p25_circuit_build_p3_verifier_air_pc: each is
+ *              the function without the suffix plus `periodic`, copies what it is given, and with periodic = NULL or
+ *              n_columns = 0 IS that function (same words, same circuit blob).  The functions without it return
+ *              P25_ERR_INVALID_ARG for an AIR that contains op 7, name the _pc form and write nothing.  The batch entry
+ *              points need no new form: the handle carries the AIR. */
 enum { P25_AIR_MAX_PUBLIC = 64 };
+enum { P25_AIR_MAX_PERIODIC = 32, P25_AIR_MAX_LOG_PERIOD = 8 };
 typedef struct {
   uint32_t op, a, b, reserved;
   uint64_t value;
@@ -241,9 +270,17 @@ typedef struct {
   const p25_air_node* nodes;
   const p25_air_constraint* constraints;
 } p25_air;
+typedef struct {
+  uint32_t n_columns;            /* 0..P25_AIR_MAX_PERIODIC */
+  const uint32_t* log_period;    /* [n_columns] */
+  const uint64_t* values;        /* the columns back to back: column c has 2^log_period[c] words */
+} p25_air_periodic;
 /* p3_verify_proof for a user AIR: `builder.p3_verify_proof::<H>(proof, &air, fri_config)` with any `impl Air`
  * (src/p3/mod.rs:66-94, 239-250).  cfg->trace_width must equal air->width. */
 p25_status p25_circuit_build_p3_verifier_air(const p25_p3_config* cfg, const p25_air* air, p25_circuit** out);
+/* The same for an AIR with periodic columns (PERIODIC COLUMNS above); log_period is checked against cfg->log_trace_height. */
+p25_status p25_circuit_build_p3_verifier_air_pc(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
+                                                p25_circuit** out);
 /* Native plonky3 prover (see p25_p3_prove_fibonacci) for a user AIR and its trace, trace[row * width + col],
  * 2^log_n rows.  P25_ERR_INVALID_ARG if the trace does not satisfy the AIR. */
 p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t num_queries,
@@ -266,6 +303,12 @@ p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_
 p25_status p25_p3_prove_air_pv(const p25_air* air, const uint64_t* trace, const uint64_t* public_values, int32_t log_n,
                                int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start, int32_t threads,
                                uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out);
+/* p25_p3_prove_air_pv for an AIR with periodic columns (PERIODIC COLUMNS above); log_period is checked against log_n.
+ * P25_ERR_INVALID_ARG if the trace does not satisfy the AIR under these columns. */
+p25_status p25_p3_prove_air_pc(const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
+                               const p25_air_periodic* periodic, int32_t log_n, int32_t log_blowup, int32_t num_queries,
+                               int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
+                               size_t* n_out, p25_p3_config* cfg_out);
 
 /* Small circuits mirroring the reference's gadget tests (src/p3/mod.rs:271-494 test_p3_and / xor / lsh /
  * rsh / reverse, src/p3/commit.rs:173-198 test_compress): kind 0 and(x,y) 1 xor(x,y) 2 lsh(x,param)
@@ -521,7 +564,7 @@ p25_status p25_verify_batch_dev(p25_circuit* c, const uint64_t* digest4, const u
  * p25_p3_prover_create   host only, works without a GPU.  Replaces the shape half of p25_p3_prove_air_ex: validates exactly
  *     what that function validates, with the same P25_ERR_INVALID_ARG cases (the AIR itself; log_n 1..22, log_blowup 1..4,
  *     log_n + log_blowup <= 24; num_queries >= 1; pow_bits 0..30; log_quotient_degree <= log_blowup), and compiles the AIR
- *     into the register program the quotient kernel interprets.  LOCAL / NEXT / CONST / PUBLIC nodes cost nothing; the device form's
+ *     into the register program the quotient kernel interprets.  LOCAL / NEXT / CONST / PUBLIC / PERIODIC nodes cost nothing; the device form's
  *     own limits are 64 arithmetic-node values alive at the same time (after a liveness pass over the DAG in constraint
  *     order), 2^20 instructions and 65535 queries: an AIR beyond them is refused HERE, with a message naming the limit,
  *     never later.  Width 64 and 512 nodes are within them.  No device memory is touched before the first compute call.
@@ -576,6 +619,11 @@ p25_status p25_verify_batch_dev(p25_circuit* c, const uint64_t* digest4, const u
 typedef struct p25_p3_prover p25_p3_prover;
 p25_status p25_p3_prover_create(const p25_air* air, int32_t log_n, int32_t log_blowup, int32_t num_queries,
                                 int32_t pow_bits, p25_p3_prover** out);
+/* The same for an AIR with periodic columns (PERIODIC COLUMNS, above); log_period is checked against log_n here.  The
+ * columns' coefficients and coset tables are made here, on the host, and go to the device with the handle's other constant
+ * tables on the first compute call.  A PERIODIC node costs the device form nothing, like LOCAL. */
+p25_status p25_p3_prover_create_pc(const p25_air* air, const p25_air_periodic* periodic, int32_t log_n, int32_t log_blowup,
+                                   int32_t num_queries, int32_t pow_bits, p25_p3_prover** out);
 void p25_p3_prover_destroy(p25_p3_prover* p);
 p25_status p25_p3_prover_config(const p25_p3_prover* p, p25_p3_config* cfg_out, size_t* num_inputs_out);
 p25_status p25_p3_prove_batch(p25_p3_prover* p, const uint64_t* traces, size_t n_proofs, const uint64_t* pow_starts,

@@ -58,6 +58,10 @@ class AirC(C.Structure):
                 ("nodes", C.POINTER(AirNode)), ("constraints", C.POINTER(AirConstraint))]
 
 
+class AirPeriodicC(C.Structure):
+    _fields_ = [("n_columns", C.c_uint32), ("log_period", C.POINTER(C.c_uint32)), ("values", C.POINTER(C.c_uint64))]
+
+
 class Air:
     """An AIR as an expression DAG (p25_air in include/p25.h): the data form of the reference's `Air` trait
     (src/p3/air.rs:10-18).  Build it like the trait's `eval` body:
@@ -67,11 +71,15 @@ class Air:
 
     n_public (0..64): the proof's public values, read with air.public(i) wherever a constant could stand
     (`builder.public_values()[i]` in a uni-stark AIR); they are the last n_public words of the proof's flat input.
+
+    periodic: a list of 1-D uint64 arrays, the AIR's periodic columns (include/p25.h, PERIODIC COLUMNS): column i has
+    2^k values, 1 <= k <= min(log_n, 8), is read with air.periodic(i) and is its values[row mod 2^k] on every trace row.
     """
     ALWAYS, FIRST_ROW, LAST_ROW, TRANSITION = 0, 1, 2, 3
 
-    def __init__(self, width, n_public=0):
+    def __init__(self, width, n_public=0, periodic=None):
         self.width, self.n_public, self.nodes, self.constraints = width, int(n_public), [], []
+        self.periodic_columns = [np.ascontiguousarray(c, dtype=np.uint64).reshape(-1) for c in (periodic or [])]
 
     def _n(self, op, a=0, b=0, value=0):
         self.nodes.append((op, a, b, value))
@@ -81,6 +89,7 @@ class Air:
     def next(self, col): return self._n(1, col)
     def const(self, v): return self._n(2, 0, 0, int(v))
     def public(self, i): return self._n(6, int(i))
+    def periodic(self, i): return self._n(7, int(i))
     def add(self, x, y): return self._n(3, x, y)
     def sub(self, x, y): return self._n(4, x, y)
     def mul(self, x, y): return self._n(5, x, y)
@@ -108,6 +117,21 @@ class Air:
         cons = (AirConstraint * len(self.constraints))(*[AirConstraint(n, w) for n, w in self.constraints])
         c = AirC(self.width, len(self.nodes), len(self.constraints), self.n_public, nodes, cons)
         c._keep = (nodes, cons)
+        return c
+
+    def periodic_to_c(self):
+        """p25_air_periodic of the columns (for the _pc entry points), or None without columns."""
+        if not self.periodic_columns:
+            return None
+        logs = []
+        for col in self.periodic_columns:
+            if col.size < 1 or col.size & (col.size - 1):
+                raise ValueError("a periodic column holds 2^k values")
+            logs.append(int(col.size).bit_length() - 1)
+        lp = (C.c_uint32 * len(logs))(*logs)
+        vals = np.ascontiguousarray(np.concatenate(self.periodic_columns), dtype=np.uint64)
+        c = AirPeriodicC(len(logs), lp, vals.ctypes.data_as(C.POINTER(C.c_uint64)))
+        c._keep = (lp, vals)
         return c
 
 
@@ -221,6 +245,11 @@ EXPORTED_SYMBOLS = {
                                   C.POINTER(P3Config)]),
     "p25_p3_prove_batch_pv": (i32, [vp, vp, vp, sz, vp, vp, sz, vp]),
     "p25_p3_prove_batch_pv_dev": (i32, [vp, vp, sz, vp, sz, vp, vp, sz, vp, vp]),
+    "p25_p3_prove_air_pc": (i32, [C.POINTER(AirC), vp, vp, vp, i32, i32, i32, i32, C.c_uint64, i32, vp, sz,
+                                  C.POINTER(sz), C.POINTER(P3Config)]),
+    "p25_p3_prover_create_pc": (i32, [C.POINTER(AirC), vp, i32, i32, i32, i32, C.POINTER(vp)]),
+    "p25_circuit_build_p3_verifier_air_pc": (i32, [C.POINTER(P3Config), C.POINTER(AirC), vp,
+                                                   C.POINTER(vp)]),
     "p25_p3_prover_sync": (i32, [vp]),
     "p25_p3_verify_batch": (i32, [vp, vp, sz, sz, vp]),
     "p25_p3_verify_batch_dev": (i32, [vp, vp, sz, sz, vp, vp]),
@@ -466,7 +495,8 @@ def _public_rows(public_values, n, n_public):
 def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=None, log_blowup=1, public_values=None):
     """Native plonky3 proof of `air` (binding.Air) on `trace` (uint64[2^log_n][width]) -> (inputs, P3Config).
     log_blowup: FriConfig.log_blowup (1 = the reference's; 2 / 3 for AIRs of constraint degree up to 5 / 9).
-    public_values: the air.n_public values of this proof; they end up as the last words of `inputs`."""
+    public_values: the air.n_public values of this proof; they end up as the last words of `inputs`.
+    An AIR with periodic columns goes through p25_p3_prove_air_pc."""
     threads = threads or min(16, os.cpu_count() or 1)
     t = np.ascontiguousarray(trace, dtype=np.uint64)
     if t.ndim != 2 or t.shape[1] != air.width or t.shape[0] & (t.shape[0] - 1) or t.shape[0] < 2:
@@ -474,6 +504,13 @@ def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=
     log_n = int(t.shape[0]).bit_length() - 1
     ac = air.to_c()
     cfg = P3Config()
+    pc = air.periodic_to_c()
+    if pc is not None:
+        pv = _public_rows(public_values, 1, air.n_public)
+        out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_pc(C.byref(ac), _ptr(t), _ptr(pv), C.byref(pc), log_n, log_blowup,
+                                                                   num_queries, pow_bits, pow_start, threads, buf, cap, n,
+                                                                   C.byref(cfg)), np.uint64)
+        return out, cfg
     if air.n_public == 0 and public_values is None:
         out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_ex(C.byref(ac), _ptr(t), log_n, log_blowup, num_queries,
                                                                    pow_bits, pow_start, threads, buf, cap, n, C.byref(cfg)),
@@ -493,7 +530,11 @@ class P3Prover:
     def __init__(self, air, log_n, log_blowup=1, num_queries=100, pow_bits=16):
         ac = air.to_c()
         h = vp()
-        _check(lib().p25_p3_prover_create(C.byref(ac), log_n, log_blowup, num_queries, pow_bits, C.byref(h)))
+        pc = air.periodic_to_c()
+        if pc is None:
+            _check(lib().p25_p3_prover_create(C.byref(ac), log_n, log_blowup, num_queries, pow_bits, C.byref(h)))
+        else:
+            _check(lib().p25_p3_prover_create_pc(C.byref(ac), C.byref(pc), log_n, log_blowup, num_queries, pow_bits, C.byref(h)))
         self._h = vp(h.value)
         self.width, self.log_n, self.n_public = air.width, log_n, air.n_public
         self.config = P3Config()
@@ -600,6 +641,9 @@ class Circuit:
     def build_p3_verifier_air(cfg, air):
         """`builder.p3_verify_proof::<H>(proof, &air, fri_config)` for a user AIR (binding.Air)."""
         ac = air.to_c()
+        pc = air.periodic_to_c()
+        if pc is not None:
+            return _new_circuit(lib().p25_circuit_build_p3_verifier_air_pc, C.byref(cfg), C.byref(ac), C.byref(pc))
         return _new_circuit(lib().p25_circuit_build_p3_verifier_air, C.byref(cfg), C.byref(ac))
 
     @staticmethod

@@ -295,10 +295,29 @@ P3Config checked_p3_config(const p25_p3_config* cfg) {
     throw std::invalid_argument("p25_p3_config out of range");
   return from_c(cfg);
 }
-AirProgram air_from_c(const p25_air* air) {
+// `periodic`: the AIR's periodic columns (null: none), copied.  `pc_form`: set by the entry points that take no columns,
+// the name of the one that does -- they refuse an AIR that reads a column (op 7) and name it.
+AirProgram air_from_c(const p25_air* air, const p25_air_periodic* periodic = nullptr, const char* pc_form = nullptr) {
   if (!air || !air->nodes || !air->constraints) throw std::invalid_argument("null AIR");
   if (air->n_nodes > (1u << 20) || air->n_constraints > (1u << 16)) throw std::invalid_argument("AIR too large");
   AirProgram p;
+  if (pc_form)
+    for (uint32_t i = 0; i < air->n_nodes; i++)
+      if (air->nodes[i].op == AirProgram::PERIODIC)
+        throw std::invalid_argument(std::string("the AIR reads periodic columns (node op 7 PERIODIC): use ") + pc_form);
+  if (periodic && periodic->n_columns) {
+    if (periodic->n_columns > (uint32_t)AirProgram::MAX_PERIODIC)
+      throw std::invalid_argument("AIR: more than 32 periodic columns (P25_AIR_MAX_PERIODIC)");
+    if (!periodic->log_period || !periodic->values) throw std::invalid_argument("null periodic columns");
+    const uint64_t* v = periodic->values;
+    for (uint32_t c = 0; c < periodic->n_columns; c++) {
+      const uint32_t lp = periodic->log_period[c];
+      if (lp < 1 || lp > (uint32_t)AirProgram::MAX_LOG_PERIOD)
+        throw std::invalid_argument("AIR: a periodic column's log_period must be 1..8 (P25_AIR_MAX_LOG_PERIOD)");
+      p.periodic.push_back(AirProgram::Periodic{lp, std::vector<u64>(v, v + ((size_t)1 << lp))});
+      v += (size_t)1 << lp;
+    }
+  }
   p.width = (int)air->width;
   if (air->n_public > (uint32_t)AirProgram::MAX_PUBLIC) throw std::invalid_argument("AIR: more than 64 public values (n_public)");
   p.n_public = (int)air->n_public;
@@ -591,10 +610,13 @@ p25_status p25_circuit_build_p3_verifier(const p25_p3_config* cfg, int32_t air, 
     return build_verifier(cfg, fib, out);
   });
 }
-p25_status p25_circuit_build_p3_verifier_air(const p25_p3_config* cfg, const p25_air* air, p25_circuit** out) {
+// p25_circuit_build_p3_verifier_air (pc_form false: refuses an AIR that reads periodic columns) and its _pc form
+static p25_status p3_build_verifier_air(bool pc_form, const p25_p3_config* cfg, const p25_air* air,
+                                        const p25_air_periodic* periodic, p25_circuit** out) {
   return host_guarded([&]() -> p25_status {
     if (!cfg || !air || !out) throw std::invalid_argument("null argument");
-    AirProgram prog = air_from_c(air);
+    AirProgram prog = air_from_c(air, periodic, pc_form ? nullptr : "p25_circuit_build_p3_verifier_air_pc");
+    prog.check_periodic(cfg->log_trace_height);
     // the chunk count follows from the AIR (uni-stark get_log_quotient_degree): the shape must say the same
     if (prog.log_quotient_degree() != cfg->log_quotient_degree)
       throw std::invalid_argument("an AIR of constraint degree " + std::to_string(prog.max_constraint_degree()) + " has 2^" +
@@ -603,19 +625,29 @@ p25_status p25_circuit_build_p3_verifier_air(const p25_p3_config* cfg, const p25
     return build_verifier(cfg, pa, out);
   });
 }
+p25_status p25_circuit_build_p3_verifier_air(const p25_p3_config* cfg, const p25_air* air, p25_circuit** out) {
+  return p3_build_verifier_air(false, cfg, air, nullptr, out);
+}
+p25_status p25_circuit_build_p3_verifier_air_pc(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
+                                                p25_circuit** out) {
+  return p3_build_verifier_air(true, cfg, air, periodic, out);
+}
 
 p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t num_queries,
                             int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
                             size_t* n_out, p25_p3_config* cfg_out) {
   return p25_p3_prove_air_ex(air, trace, log_n, 1, num_queries, pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
-// p25_p3_prove_air_ex (pv_form false: refuses an AIR with public values) and p25_p3_prove_air_pv
-static p25_status p3_prove_air_host(bool pv_form, const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
+// p25_p3_prove_air_ex (pv_form false: refuses an AIR with public values), p25_p3_prove_air_pv and p25_p3_prove_air_pc
+// (pc_form: the name of the form that takes periodic columns, for the two that do not and refuse an AIR reading one)
+static p25_status p3_prove_air_host(bool pv_form, const char* pc_form, const p25_air* air, const uint64_t* trace,
+                                    const uint64_t* public_values, const p25_air_periodic* periodic,
                                     int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start,
                                     int32_t threads, uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out) {
   return host_guarded([&]() -> p25_status {
     if (!air || !n_out) throw std::invalid_argument("null argument");
-    AirProgram prog = air_from_c(air);
+    AirProgram prog = air_from_c(air, periodic, pc_form);
+    prog.check_periodic(log_n);
     if (!pv_form && prog.n_public > 0)
       throw std::invalid_argument("the AIR has public values (n_public > 0): use p25_p3_prove_air_pv");
     if (log_blowup < 1 || log_blowup > 4) throw std::invalid_argument("log_blowup must be 1..4");
@@ -648,27 +680,42 @@ static p25_status p3_prove_air_host(bool pv_form, const p25_air* air, const uint
 p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t log_blowup, int32_t num_queries,
                                int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
                                size_t* n_out, p25_p3_config* cfg_out) {
-  return p3_prove_air_host(false, air, trace, nullptr, log_n, log_blowup, num_queries, pow_bits, pow_start, threads, inputs_out,
-                           cap, n_out, cfg_out);
+  return p3_prove_air_host(false, "p25_p3_prove_air_pc", air, trace, nullptr, nullptr, log_n, log_blowup, num_queries, pow_bits,
+                           pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
 p25_status p25_p3_prove_air_pv(const p25_air* air, const uint64_t* trace, const uint64_t* public_values, int32_t log_n,
                                int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start, int32_t threads,
                                uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out) {
-  return p3_prove_air_host(true, air, trace, public_values, log_n, log_blowup, num_queries, pow_bits, pow_start, threads,
-                           inputs_out, cap, n_out, cfg_out);
+  return p3_prove_air_host(true, "p25_p3_prove_air_pc", air, trace, public_values, nullptr, log_n, log_blowup, num_queries,
+                           pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
+}
+p25_status p25_p3_prove_air_pc(const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
+                               const p25_air_periodic* periodic, int32_t log_n, int32_t log_blowup, int32_t num_queries,
+                               int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
+                               size_t* n_out, p25_p3_config* cfg_out) {
+  return p3_prove_air_host(true, nullptr, air, trace, public_values, periodic, log_n, log_blowup, num_queries, pow_bits,
+                           pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
 
 // ---- the plonky3 prover on the device -------------------------------------------------------------------------------
-p25_status p25_p3_prover_create(const p25_air* air, int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits,
-                                p25_p3_prover** out) {
+static p25_status p3_prover_create(bool pc_form, const p25_air* air, const p25_air_periodic* periodic, int32_t log_n,
+                                   int32_t log_blowup, int32_t num_queries, int32_t pow_bits, p25_p3_prover** out) {
   return host_guarded([&]() -> p25_status {
     if (!air || !out) throw std::invalid_argument("null argument");
-    const AirProgram prog = air_from_c(air);
+    const AirProgram prog = air_from_c(air, periodic, pc_form ? nullptr : "p25_p3_prover_create_pc");
     std::unique_ptr<p25_p3_prover> h(new p25_p3_prover());
     h->dev.reset(new P3ProverDev(prog, log_n, log_blowup, num_queries, pow_bits));
     *out = h.release();
     return P25_OK;
   });
+}
+p25_status p25_p3_prover_create(const p25_air* air, int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits,
+                                p25_p3_prover** out) {
+  return p3_prover_create(false, air, nullptr, log_n, log_blowup, num_queries, pow_bits, out);
+}
+p25_status p25_p3_prover_create_pc(const p25_air* air, const p25_air_periodic* periodic, int32_t log_n, int32_t log_blowup,
+                                   int32_t num_queries, int32_t pow_bits, p25_p3_prover** out) {
+  return p3_prover_create(true, air, periodic, log_n, log_blowup, num_queries, pow_bits, out);
 }
 void p25_p3_prover_destroy(p25_p3_prover* p) { delete p; }
 p25_status p25_p3_prover_config(const p25_p3_prover* p, p25_p3_config* cfg_out, size_t* num_inputs_out) {

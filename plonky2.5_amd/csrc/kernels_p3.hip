@@ -286,8 +286,14 @@ __global__ __launch_bounds__(256) void k_p3_quotient(P3Shape sh, P3Bufs b) {
   const u64 sel[4] = {0, gl::mul(zhx, gl::inv(gl::sub(x, 1))), gl::mul(zhx, gl::inv(is_trans)), is_trans};
   const E2 alpha = ld_e2(b.state[g].alpha);
   auto load = [&](int next, uint32_t c) -> u64 { return lde[(size_t)c * N2 + (next ? pos1 : p)]; };
+  // A periodic column at x_j: its table by j mod (P Q) -- the NATURAL index j, whose low bits are the reversed top bits of
+  // p.  256 consecutive p share their top bits once n >= 256 P, so a block then reads one word: a plain load.
+  const u64* ptab = b.consts + sh.per_tab;
+  auto per = [&](uint32_t i) -> u64 {
+    return ptab[((size_t)p3_per_offset(i) << sh.lqd) + (j & ((1u << (p3_per_log_period(i) + sh.lqd)) - 1))];
+  };
   // every lane of the block reads the row of proof g: a plain load at a uniform address
-  const E2 acc = run_air<BaseF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, load, sel, alpha);
+  const E2 acc = run_air<BaseF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, load, per, sel, alpha);
   const E2 q = gl::mul(acc, sh.zh_inv[chunk]);
   u64* dst = b.qv + (((size_t)chunk * sh.G + g) * 2) * n + (p & (n - 1));
   dst[0] = q.a;
@@ -347,7 +353,9 @@ __global__ __launch_bounds__(64) void k_p3_identity(P3Shape sh, P3Bufs b) {
   const E2 is_trans = gl::sub(zeta, gl::e2(sh.g_inv));
   const E2 sel[4] = {gl::e2(0), gl::mul(z_h, gl::inv(gl::sub(zeta, gl::e2(1)))), gl::mul(z_h, gl::inv(is_trans)), is_trans};
   auto load = [&](int next, uint32_t c) -> E2 { return ld_e2(open + 2 * ((next ? sh.W : 0) + c)); };
-  const E2 acc = run_air<ExtF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, load, sel, alpha);
+  const u64* pcoef = b.consts + sh.per_coef;
+  auto per = [&](uint32_t i) -> E2 { return p3_periodic_at(pcoef + p3_per_offset(i), p3_per_log_period(i), sh.k, zeta); };
+  const E2 acc = run_air<ExtF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, load, per, sel, alpha);
   const E2 lhs = gl::mul(acc, gl::inv(z_h));
   E2 at_zeta[8];
   for (uint32_t j = 0; j < sh.Q; j++) at_zeta[j] = gl::sub(gl::exp_pow2(gl::mul(zeta, sh.s_inv[j]), sh.k), gl::e2(1));

@@ -27,11 +27,24 @@ struct ExtF {
   GL_HD static gl::E2 mul(gl::E2 x, gl::E2 y) { return gl::mul(x, y); }
   GL_HD static gl::E2 fold(gl::E2 acc, gl::E2 alpha, gl::E2 c) { return gl::add(gl::mul(acc, alpha), c); }
 };
-// Runs the register program: `load(next, column)` reads the row, `pub` is the proof's own row of public values (read only
-// by P3_OPND_PUBLIC operands: may be null without them), the constraints are folded in program order.
-template <class F, class Load>
+// A periodic column at zeta from its interpolant's P = 2^lp base-field coefficients: q(zeta^(n/P)), k - lp squarings and
+// Horner (p3_prover.cpp's self-check; the identity lanes of the prover and the verifier, one lane per proof).
+GL_HD gl::E2 p3_periodic_at(const u64* __restrict__ coef, uint32_t lp, uint32_t k, gl::E2 zeta) {
+  const gl::E2 y = gl::exp_pow2(zeta, k - lp);
+  gl::E2 acc = gl::e2(0);
+  for (uint32_t i = 1u << lp; i-- > 0;) {
+    acc = gl::mul(acc, y);
+    acc.a = gl::add(acc.a, coef[i]);
+  }
+  return acc;
+}
+// Runs the register program: `load(next, column)` reads the row, `per(index)` gives the periodic column of a
+// P3_OPND_PERIODIC operand (p3_per_log_period, p3_per_offset of its index) at the caller's point, `pub` is the proof's own
+// row of public values (read only by P3_OPND_PUBLIC operands: may be null without them), the constraints are folded in
+// program order.
+template <class F, class Load, class Per>
 GL_HD gl::E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u64* __restrict__ consts,
-                     const u64* __restrict__ pub, Load load, const typename F::T sel[4], gl::E2 alpha) {
+                     const u64* __restrict__ pub, Load load, Per per, const typename F::T sel[4], gl::E2 alpha) {
   typedef typename F::T T;
   T slot[P3_MAX_LIVE];
   auto fetch = [&](uint32_t o) -> T {
@@ -41,6 +54,7 @@ GL_HD gl::E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u
       case P3_OPND_LOCAL: return load(0, i);
       case P3_OPND_NEXT: return load(1, i);
       case P3_OPND_PUBLIC: return F::cst(pub[i]);
+      case P3_OPND_PERIODIC: return per(i);
       default: return F::cst(consts[i]);
     }
   };

@@ -381,12 +381,13 @@ void FibonacciAir::eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) co
 
 // ---------------------------------------------------------------- AIR programs
 // Nodes refer to earlier nodes only (validate), so one pass in index order has every operand's degree at hand.  CONST and
-// PUBLIC are the degree-0 leaves; a product's degree saturates, so that no chain of squarings wraps it.
+// PUBLIC are the degree-0 leaves, a PERIODIC column has degree n - n/P <= n - 1 and counts as 1 like LOCAL; a product's
+// degree saturates, so that no chain of squarings wraps it.
 std::vector<int> AirProgram::node_degrees() const {
   std::vector<int> deg(nodes.size(), 0);
   for (size_t k = 0; k < nodes.size(); k++) {
     const Node& nd = nodes[k];
-    if (nd.op == LOCAL || nd.op == NEXT) deg[k] = 1;
+    if (nd.op == LOCAL || nd.op == NEXT || nd.op == PERIODIC) deg[k] = 1;
     else if (nd.op == CONST || nd.op == PUBLIC) deg[k] = 0;
     else if (nd.op == MUL) deg[k] = std::min(deg[nd.a] + deg[nd.b], DEGREE_SAT);
     else deg[k] = std::max(deg[nd.a], deg[nd.b]);
@@ -396,12 +397,21 @@ std::vector<int> AirProgram::node_degrees() const {
 void AirProgram::validate() const {
   if (width < 1 || width > 1024) throw std::invalid_argument("AIR: width out of range");
   if (n_public < 0 || n_public > MAX_PUBLIC) throw std::invalid_argument("AIR: more than 64 public values (n_public)");
+  if (periodic.size() > (size_t)MAX_PERIODIC) throw std::invalid_argument("AIR: more than 32 periodic columns (P25_AIR_MAX_PERIODIC)");
+  for (const Periodic& pc : periodic) {
+    if (pc.log_period < 1 || pc.log_period > (uint32_t)MAX_LOG_PERIOD)
+      throw std::invalid_argument("AIR: a periodic column's log_period must be 1..8 (P25_AIR_MAX_LOG_PERIOD)");
+    if (pc.values.size() != (size_t)1 << pc.log_period) throw std::invalid_argument("AIR: a periodic column holds 2^log_period values");
+    for (u64 v : pc.values)
+      if (v >= gl::P) throw std::invalid_argument("AIR: non-canonical periodic value (>= p)");
+  }
   if (nodes.empty() || constraints.empty()) throw std::invalid_argument("AIR: empty program");
   for (size_t i = 0; i < nodes.size(); i++) {
     const Node& nd = nodes[i];
-    if (nd.op > PUBLIC) throw std::invalid_argument("AIR: unknown node op");
+    if (nd.op > PERIODIC) throw std::invalid_argument("AIR: unknown node op");
     if ((nd.op == LOCAL || nd.op == NEXT) && nd.a >= (uint32_t)width) throw std::invalid_argument("AIR: column out of range");
     if (nd.op == PUBLIC && nd.a >= (uint32_t)n_public) throw std::invalid_argument("AIR: public value index >= n_public");
+    if (nd.op == PERIODIC && nd.a >= periodic.size()) throw std::invalid_argument("AIR: periodic column index >= n_columns");
     if (nd.op >= ADD && nd.op <= MUL && (nd.a >= i || nd.b >= i)) throw std::invalid_argument("AIR: node refers to a later node");
     if (nd.op == CONST && nd.value >= gl::P) throw std::invalid_argument("AIR: non-canonical constant");
   }
@@ -415,6 +425,25 @@ void AirProgram::validate() const {
     if (deg[c.node] + (c.when == ALWAYS ? 0 : 1) > 9)
       throw std::invalid_argument("AIR: constraint degree > 9 needs more than eight quotient chunks");
   }
+}
+void AirProgram::check_periodic(int log_n) const {
+  for (const Periodic& pc : periodic)
+    if ((int)pc.log_period > log_n)
+      throw std::invalid_argument("AIR: a periodic column's log_period exceeds the trace's log height (log_n)");
+}
+// q's coefficients: the inverse transform over <w_P>, a_i = 1/P sum_j v_j w_P^(-i j).  P <= 256: the plain sum will do.
+std::vector<u64> AirProgram::periodic_coefficients(size_t c) const {
+  const Periodic& pc = periodic.at(c);
+  const size_t P = pc.values.size();
+  const u64 w_inv = gl::inv(gl::root_of_unity(pc.log_period)), p_inv = gl::inv((u64)P);
+  std::vector<u64> coef(P);
+  u64 wi = 1;   // w_P^(-i)
+  for (size_t i = 0; i < P; i++, wi = gl::mul(wi, w_inv)) {
+    u64 acc = 0;
+    for (size_t j = P; j-- > 0;) acc = gl::add(gl::mul(acc, wi), pc.values[j]);
+    coef[i] = gl::mul(acc, p_inv);
+  }
+  return coef;
 }
 int AirProgram::max_constraint_degree() const {
   const std::vector<int> deg = node_degrees();
@@ -449,15 +478,33 @@ namespace {
 struct CircuitExtOps {
   CircuitBuilder& cb;
   const std::vector<Ext>& public_values;
+  const std::vector<Ext>& periodic;
   Ext cst(u64 v) { return p3_field_to_arr(cb, p3_constant(cb, v)); }
   Ext pub(uint32_t i) { return public_values.at(i); }
+  Ext per(uint32_t c) { return periodic.at(c); }
   Ext add(const Ext& x, const Ext& y) { return p3_ext_add(cb, x, y); }
   Ext sub(const Ext& x, const Ext& y) { return p3_ext_sub(cb, x, y); }
   Ext mul(const Ext& x, const Ext& y) { return p3_ext_mul(cb, x, y); }
 };
 }  // namespace
+// The periodic columns at zeta, c(zeta) = q_c(zeta^(n/P)).  Emission order (the circuit's digest depends on it): column by
+// column in index order; for each, log_n - log_period extension squarings of zeta, then Horner from the highest
+// coefficient down -- the constant a_{P-1} embedded in the extension, then P - 1 steps of (extension product by y, the
+// constant a_i added to component 0).  Every column is emitted, whether a constraint reads it or not.
+std::vector<Ext> ProgramAir::periodic_at(CircuitBuilder& cb, const Ext& zeta, int log_n) const {
+  prog.check_periodic(log_n);
+  std::vector<Ext> out;
+  for (size_t c = 0; c < prog.periodic.size(); c++) {
+    const std::vector<u64> coef = prog.periodic_coefficients(c);
+    const Ext y = p3_ext_exp_power_of_2(cb, zeta, log_n - (int)prog.periodic[c].log_period);
+    Ext acc = p3_field_to_arr(cb, p3_constant(cb, coef.back()));
+    for (size_t i = coef.size() - 1; i-- > 0;) acc = p3_ext_add_single(cb, p3_ext_mul(cb, acc, y), p3_constant(cb, coef[i]));
+    out.push_back(acc);
+  }
+  return out;
+}
 void ProgramAir::eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const {
-  CircuitExtOps ops{cb, folder.public_values};
+  CircuitExtOps ops{cb, folder.public_values, folder.periodic};
   const Ext sel[4] = {Ext{}, folder.is_first_row, folder.is_last_row, folder.is_transition};
   prog.fold<Ext>(folder.trace_local, folder.trace_next, sel, ops, [&](const Ext& c) { folder.assert_zero(cb, c); });
 }
@@ -774,6 +821,7 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
   folder.is_transition = sels.is_transition;
   folder.alpha = alpha;
   folder.accumulator = p3_ext_zero(cb);
+  folder.periodic = air.periodic_at(cb, zeta, degree_bits);   // nothing, and no gate, for an AIR without periodic columns
   air.eval(folder, cb);
   Ext folded_constraints = folder.accumulator;
   Ext lhs = p3_ext_mul(cb, folded_constraints, sels.inv_zeroifier);

@@ -52,6 +52,7 @@ struct P3ProofTarget {
 struct VerifierConstraintFolder {
   std::vector<Ext> trace_local, trace_next;
   std::vector<Ext> public_values;   // this library's extension (AirProgram::PUBLIC): base elements embedded in the extension
+  std::vector<Ext> periodic;        // this library's extension (AirProgram::PERIODIC): the periodic columns at zeta, by column
   Ext is_first_row, is_last_row, is_transition, alpha, accumulator;
   // air.rs:69-88, 90-118
   void assert_zero(CircuitBuilder& cb, Ext x);
@@ -65,6 +66,9 @@ struct Air {
   virtual int width() const = 0;
   // public values of a proof (uni-stark's `public_values`); the reference's trait has none
   virtual int n_public() const { return 0; }
+  // the AIR's periodic columns at zeta, in column order (this library's extension; the reference's trait has none): emits
+  // the gates that compute them and throws std::invalid_argument for a period above the trace height 2^log_n
+  virtual std::vector<Ext> periodic_at(CircuitBuilder&, const Ext& /*zeta*/, int /*log_n*/) const { return {}; }
   virtual void eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const = 0;
 };
 // src/p3/mod.rs:160-221 (the test's FibonacciAir)
@@ -82,11 +86,14 @@ struct FibonacciAir : Air {
 // verifier (ProgramAir below) and the native plonky3 prover (p3_prover.h).
 struct AirProgram {
   // PUBLIC(a): public value a < n_public of the proof (uni-stark's `builder.public_values()[a]`): degree 0 like CONST
-  enum Op : uint32_t { LOCAL = 0, NEXT = 1, CONST = 2, ADD = 3, SUB = 4, MUL = 5, PUBLIC = 6 };
+  // PERIODIC(a): periodic column a at the current row (this library's extension, like PUBLIC; include/p25.h "PERIODIC
+  // COLUMNS"): degree 1 like LOCAL
+  enum Op : uint32_t { LOCAL = 0, NEXT = 1, CONST = 2, ADD = 3, SUB = 4, MUL = 5, PUBLIC = 6, PERIODIC = 7 };
   static constexpr int MAX_PUBLIC = 64;   // P25_AIR_MAX_PUBLIC
+  static constexpr int MAX_PERIODIC = 32, MAX_LOG_PERIOD = 8;   // P25_AIR_MAX_PERIODIC, P25_AIR_MAX_LOG_PERIOD
   enum When : uint32_t { ALWAYS = 0, FIRST_ROW = 1, LAST_ROW = 2, TRANSITION = 3 };
   struct Node {
-    uint32_t op, a, b;  // LOCAL/NEXT: a = column; PUBLIC: a = index; ADD/SUB/MUL: a, b = earlier node indices
+    uint32_t op, a, b;  // LOCAL/NEXT: a = column; PUBLIC: a = index; PERIODIC: a = periodic column; ADD/SUB/MUL: a, b = earlier node indices
     u64 value;          // CONST
   };
   struct Constraint {
@@ -94,12 +101,25 @@ struct AirProgram {
   };
   int width = 0;
   int n_public = 0;
+  // A periodic column is part of the AIR like a constant: on trace row i it is values[i mod P], P = 2^log_period, and as a
+  // polynomial over the trace domain q(x^(n/P)), q the interpolant of `values` over <w_P>.  Neither committed nor opened.
+  struct Periodic {
+    uint32_t log_period;       // 1..MAX_LOG_PERIOD, and at most the trace's log height (check_periodic)
+    std::vector<u64> values;   // [2^log_period], each < p
+  };
+  std::vector<Periodic> periodic;
   std::vector<Node> nodes;
   std::vector<Constraint> constraints;
-  // throws std::invalid_argument on malformed programs (a PUBLIC index >= n_public and n_public > MAX_PUBLIC among them)
+  // throws std::invalid_argument on malformed programs (a PUBLIC index >= n_public, n_public > MAX_PUBLIC, a PERIODIC index
+  // past the columns, more than MAX_PERIODIC columns, a log_period outside 1..MAX_LOG_PERIOD, a value >= p among them)
   // and on constraint degree > 9 (selector included; eight quotient chunks).  The reference's proof model carries exactly one chunk (serde/proof.rs:41-48, degree <= 2); more chunks are this
   // library's extension of it, and log_quotient_degree() of them must not exceed the FRI log_blowup (checked by the callers).
   void validate() const;
+  // the one check that needs the trace height: throws std::invalid_argument for a column with log_period > log_n
+  void check_periodic(int log_n) const;
+  // coefficients of column c's interpolant q (degree < P, q(w_P^j) = values[j]): what the evaluation at zeta and the
+  // table on the quotient coset (p3_periodic_table, p3_prover.h) start from
+  std::vector<u64> periodic_coefficients(size_t c) const;
   // the degree of every node in one pass over the DAG, saturating at DEGREE_SAT (a chain of squarings overflows any integer)
   static constexpr int DEGREE_SAT = 1 << 16;
   std::vector<int> node_degrees() const;
@@ -112,7 +132,7 @@ struct AirProgram {
   static AirProgram fibonacci();
 
   // Generic evaluation, nodes computed on demand in constraint order (so that the circuit form emits
-  // its gates in the order the reference's hand-written `eval` does).  ops: cst(u64), pub(index), add, sub, mul.
+  // its gates in the order the reference's hand-written `eval` does).  ops: cst(u64), pub(index), per(column), add, sub, mul.
   template <class T, class Ops, class Emit>
   void fold(const std::vector<T>& local, const std::vector<T>& next, const T sel[4], Ops& ops, Emit&& emit) const {
     std::vector<T> val(nodes.size());
@@ -135,6 +155,8 @@ struct AirProgram {
           val[i] = ops.cst(nd.value);
         } else if (nd.op == PUBLIC) {
           val[i] = ops.pub(nd.a);
+        } else if (nd.op == PERIODIC) {
+          val[i] = ops.per(nd.a);
         } else {
           if (!have[nd.a]) {
             stack.push_back(nd.a);
@@ -159,6 +181,8 @@ struct ProgramAir : Air {
   std::string name() const override { return "Program"; }
   int width() const override { return prog.width; }
   int n_public() const override { return prog.n_public; }
+  // emission order: p3_circuit.cpp
+  std::vector<Ext> periodic_at(CircuitBuilder& cb, const Ext& zeta, int log_n) const override;
   void eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const override;
 };
 

@@ -9,8 +9,13 @@ namespace p25 {
 
 // ---- the AIR as a register program (compiled by P3AirDevice::compile from the AirProgram DAG) ----
 // Operands: kind << 28 | index.  LOCAL / NEXT / CONST / PUBLIC nodes never take a slot: they are re-read where they are
-// used (PUBLIC: from the proof's own row of public values).
-enum : uint32_t { P3_OPND_SLOT = 0, P3_OPND_LOCAL = 1, P3_OPND_NEXT = 2, P3_OPND_CONST = 3, P3_OPND_PUBLIC = 4 };
+// used (PUBLIC: from the proof's own row of public values).  PERIODIC is as free: its index is log_period << 24 | the
+// words of the columns before it (at most 31 * 256), and its value comes from the caller of run_air -- a table word in the
+// quotient kernel, q_c(zeta^(n/P)) in the identity lanes.
+enum : uint32_t { P3_OPND_SLOT = 0, P3_OPND_LOCAL = 1, P3_OPND_NEXT = 2, P3_OPND_CONST = 3, P3_OPND_PUBLIC = 4,
+                  P3_OPND_PERIODIC = 5 };
+GL_HD uint32_t p3_per_log_period(uint32_t index) { return index >> 24; }
+GL_HD uint32_t p3_per_offset(uint32_t index) { return index & 0xffffffu; }
 enum : uint32_t { P3_OP_ADD = 3, P3_OP_SUB = 4, P3_OP_MUL = 5, P3_OP_EMIT = 6 };  // ADD..MUL as AirProgram::Op
 struct P3Instr {
   uint32_t op, dst /* slot; EMIT: the constraint's `when` */, a, b;
@@ -29,6 +34,7 @@ constexpr int P3_TAIL_LOG = 10;
 
 struct P3AirDevice {
   std::vector<P3Instr> instr;
+  // the CONST nodes' values; P3ProverDev appends the periodic columns' coefficients and tables (P3Shape::per_coef, per_tab)
   std::vector<u64> consts;
   uint32_t max_live = 0;
   // throws std::invalid_argument naming the limit the program exceeds
@@ -50,6 +56,10 @@ struct P3Shape {
   uint32_t n_instr, tail_round;   // FRI rounds >= tail_round run in k_p3_fri_tail
   uint32_t G;                     // proofs of this group
   uint32_t n_public;              // public values per proof: the tail of its flat words
+  // The periodic columns, behind the AIR's constants in P3Bufs::consts and shared by every proof of every group.  Column c
+  // with `off` words of columns before it: its P coefficients at per_coef + off, its table of P Q values on the quotient
+  // coset (p3_periodic_table) at per_tab + off * Q.
+  uint32_t per_coef, per_tab;
   u64 w[26], w_inv[26];           // primitive 2^i-th roots of unity and their inverses
   u64 zh[8], zh_inv[8];           // x^n - 1 on the quotient coset, by chunk
   u64 s_inv[8];                   // 1 / s_c

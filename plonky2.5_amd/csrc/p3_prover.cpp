@@ -154,19 +154,30 @@ Tree commit(const std::vector<u64>& rows, size_t width, int threads) {
 }
 }  // namespace
 
+std::vector<u64> p3_periodic_table(const std::vector<u64>& coef, int log_n, int lqd) {
+  unsigned lp = 0;
+  while (((size_t)1 << lp) < coef.size()) lp++;
+  // x_j^(n/P) = 7^(n/P) (w_{n Q}^(n/P))^j, and w_{n Q}^(n/P) is the primitive root of order P Q that lde() steps by
+  return lde(coef, gl::pow(gl::GENERATOR, (u64)1 << (log_n - (int)lp)), lqd);
+}
+
 namespace {
 struct BaseOps {
   const std::vector<u64>& pv;
+  const std::vector<u64>& pc;   // the periodic columns at the current point
   u64 cst(u64 v) { return v; }
   u64 pub(uint32_t i) { return pv[i]; }
+  u64 per(uint32_t c) { return pc[c]; }
   u64 add(u64 x, u64 y) { return gl::add(x, y); }
   u64 sub(u64 x, u64 y) { return gl::sub(x, y); }
   u64 mul(u64 x, u64 y) { return gl::mul(x, y); }
 };
 struct ExtOps {
   const std::vector<u64>& pv;
+  const std::vector<E2>& pc;    // the periodic columns at zeta
   E2 cst(u64 v) { return gl::e2(v); }
   E2 pub(uint32_t i) { return gl::e2(pv[i]); }
+  E2 per(uint32_t c) { return pc[c]; }
   E2 add(E2 x, E2 y) { return gl::add(x, y); }
   E2 sub(E2 x, E2 y) { return gl::sub(x, y); }
   E2 mul(E2 x, E2 y) { return gl::mul(x, y); }
@@ -204,6 +215,7 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
       prm.num_queries < 1 || prm.pow_bits < 0 || prm.pow_bits > 30)
     throw std::invalid_argument("p3_prove: unsupported parameters");
   air.validate();
+  air.check_periodic(prm.log_n);
   const int k = prm.log_n, B = prm.log_blowup, L = k + B, T = prm.threads;
   const size_t n = (size_t)1 << k, N2 = n << B;      // N2: the LDE domain's size (2 n for the reference's log_blowup 1)
   const u64 w_n = gl::root_of_unity(k), w_2n = gl::root_of_unity(L);
@@ -256,7 +268,12 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
       zh_inv[r] = gl::inv(zh[r]);
     }
     u64 x = gl::GENERATOR;
-    BaseOps ops{pub};
+    // the periodic columns on the coset: tables of P Q values, read by j mod (P Q)
+    const size_t NP = air.periodic.size();
+    std::vector<std::vector<u64>> ptab(NP);
+    for (size_t c = 0; c < NP; c++) ptab[c] = p3_periodic_table(air.periodic_coefficients(c), k, lqd);
+    std::vector<u64> per(NP);
+    BaseOps ops{pub, per};
     std::vector<u64> loc(W), nxt(W);
     for (size_t j = 0; j < nq; j++, x = gl::mul(x, w_q)) {
       const size_t i0 = lde_step * j, i1 = (lde_step * j + row_step) % N2;   // the next ROW is x w_n = 2^B LDE points on
@@ -264,6 +281,7 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
         loc[c] = lde_nat[c][i0];
         nxt[c] = lde_nat[c][i1];
       }
+      for (size_t c = 0; c < NP; c++) per[c] = ptab[c][j & (ptab[c].size() - 1)];
       // two_adic.rs:100-147: selectors at a point of the quotient coset
       const u64 zhx = zh[j & (Q - 1)];
       const u64 is_trans = gl::sub(x, g_inv);
@@ -321,7 +339,11 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
     E2 z_h = gl::sub(gl::exp_pow2(un, k), gl::e2(1));
     E2 is_trans = gl::sub(un, gl::e2(gl::inv(w_n)));
     const E2 sel[4] = {gl::e2(0), gl::mul(z_h, gl::inv(gl::sub(un, gl::e2(1)))), gl::mul(z_h, gl::inv(is_trans)), is_trans};
-    ExtOps ops{pub};
+    // c(zeta) = q_c(zeta^(n/P)): log_n - log_period squarings, then Horner over q_c's base-field coefficients
+    std::vector<E2> per;
+    for (size_t c = 0; c < air.periodic.size(); c++)
+      per.push_back(eval_ext(air.periodic_coefficients(c), gl::exp_pow2(zeta, k - (int)air.periodic[c].log_period)));
+    ExtOps ops{pub, per};
     E2 acc = gl::e2(0);
     air.fold<E2>(t_local, t_next, sel, ops, [&](E2 c) { acc = gl::add(gl::mul(acc, alpha), c); });
     E2 lhs = gl::mul(acc, gl::inv(z_h));

@@ -42,6 +42,10 @@ std::vector<u64> p3_prove_air(const AirProgram& air, const std::vector<std::vect
 // + air.n_public words in all).  With no public values the words are p3_prove_air's.
 std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::vector<u64>>& col, const std::vector<u64>& pub,
                                  const P3ProveParams& prm, P3Config& cfg_out);
+// A periodic column on the quotient coset 7 H_{n Q}, Q = 2^lqd (AirProgram::Periodic; include/p25.h "PERIODIC COLUMNS"):
+// T[r] = q(7^(n/P) u^r), u = w_{n Q}^(n/P) of order P Q, for r < P Q -- the coset LDE of the interpolant q whose P
+// coefficients are `coef`.  The column's value at the point of natural index j, x_j = 7 w_{n Q}^j, is T[j mod (P Q)].
+std::vector<u64> p3_periodic_table(const std::vector<u64>& coef, int log_n, int lqd);
 // serde-JSON text in the reference's format (proof.rs:16-19: field elements are {"value": u64})
 std::string p3_inputs_to_json(const std::vector<u64>& inputs, const P3Config& cfg);
 

@@ -2,19 +2,20 @@
 // group of proofs, which mirrors p3_prove_air (p3_prover.cpp) stage by stage.  The kernels are in kernels_p3.hip.
 #include <algorithm>
 #include <functional>
+#include "p3_prover.h"
 #include "p3_prover_impl.h"
 
 namespace p25 {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // AirProgram -> register program.  Nodes are visited in the order AirProgram::fold evaluates them; a LOCAL / NEXT / CONST /
-// PUBLIC node becomes an operand, an arithmetic node takes a slot from its evaluation to its last use.
+// PUBLIC / PERIODIC node becomes an operand, an arithmetic node takes a slot from its evaluation to its last use.
 // ---------------------------------------------------------------------------------------------------------------------
 P3AirDevice P3AirDevice::compile(const AirProgram& air) {
   typedef AirProgram A;
   const size_t N = air.nodes.size();
   P3AirDevice out;
-  auto is_leaf = [&](uint32_t i) { return air.nodes[i].op <= A::CONST || air.nodes[i].op == A::PUBLIC; };
+  auto is_leaf = [&](uint32_t i) { return air.nodes[i].op <= A::CONST || air.nodes[i].op >= A::PUBLIC; };
   // uses of every arithmetic node by the nodes and constraints that are evaluated
   std::vector<uint32_t> uses(N, 0);
   std::vector<char> seen(N, 0);
@@ -44,6 +45,11 @@ P3AirDevice P3AirDevice::compile(const AirProgram& air) {
     if (nd.op == A::LOCAL) return (P3_OPND_LOCAL << 28) | nd.a;
     if (nd.op == A::NEXT) return (P3_OPND_NEXT << 28) | nd.a;
     if (nd.op == A::PUBLIC) return (P3_OPND_PUBLIC << 28) | nd.a;
+    if (nd.op == A::PERIODIC) {
+      uint32_t off = 0;   // words of the columns before it
+      for (uint32_t c = 0; c < nd.a; c++) off += 1u << air.periodic[c].log_period;
+      return (P3_OPND_PERIODIC << 28) | (air.periodic[nd.a].log_period << 24) | off;
+    }
     if (nd.op == A::CONST) {
       if (!have[i]) {
         have[i] = 1;
@@ -110,6 +116,7 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
       pow_bits > 30)
     throw std::invalid_argument("p3_prove: unsupported parameters");
   air.validate();
+  air.check_periodic(log_n);
   const int lqd = air.log_quotient_degree();
   if (lqd > log_blowup)
     throw std::invalid_argument("p3_prove: the AIR's constraint degree needs more quotient chunks than log_blowup holds");
@@ -134,6 +141,16 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
   s.num_queries = num_queries; s.pow_bits = pow_bits;
   s.n_instr = (uint32_t)prog_.instr.size();
   s.n_public = (uint32_t)air.n_public;
+  // the periodic columns go up with the constants: every column's coefficients, then every column's table
+  s.per_coef = (uint32_t)prog_.consts.size();
+  std::vector<u64> tables;
+  for (size_t c = 0; c < air.periodic.size(); c++) {
+    const std::vector<u64> coef = air.periodic_coefficients(c), tab = p3_periodic_table(coef, k, lqd);
+    prog_.consts.insert(prog_.consts.end(), coef.begin(), coef.end());
+    tables.insert(tables.end(), tab.begin(), tab.end());
+  }
+  s.per_tab = (uint32_t)prog_.consts.size();
+  prog_.consts.insert(prog_.consts.end(), tables.begin(), tables.end());
   // FRI layers of at most 2^P3_TAIL_LOG values fold in one workgroup per proof
   s.tail_round = L > P3_TAIL_LOG ? std::min(k, L - P3_TAIL_LOG) : 0;
   for (int i = 0; i < 26; i++) {

@@ -30,6 +30,7 @@ P3VerifyArgs P3ProverDev::verify_args() const {
   a.num_inputs = (uint32_t)num_inputs();
   a.n_public = s.n_public;
   a.o_public = a.num_inputs - s.n_public;
+  a.per_coef = s.per_coef;
   a.o_open = 8;
   a.o_roots = 8 + 4 * s.W + 4 * s.Q;
   a.o_qp = s.hdr_words;

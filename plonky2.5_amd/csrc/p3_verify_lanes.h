@@ -51,6 +51,8 @@ struct P3VerifyArgs {
   // the proof's public values: its last n_public words (num_inputs counts them), observed after the trace root and read
   // by the AIR's PUBLIC operands
   uint32_t n_public, o_public;
+  // the periodic columns' coefficients: consts + per_coef (P3Shape::per_coef), read by the identity lane alone
+  uint32_t per_coef;
   u64 w_L, w_L_inv;    // primitive root of the LDE domain and its inverse
   u64 w_n, g_inv;      // generator of the trace domain and its inverse
   u64 neg2_inv;        // 1 / -2
@@ -136,7 +138,9 @@ GL_HD bool identity_lane(const P3VerifyArgs& a, uint32_t p) {
   const E2 sel[4] = {gl::e2(0), gl::mul(z_h, gl::inv(gl::sub(zeta, gl::e2(1)))), gl::mul(z_h, gl::inv(is_trans)), is_trans};
   const uint32_t W = a.W;
   auto load = [&](int next, uint32_t c) -> E2 { return ld(open + 2 * ((next ? W : 0) + c)); };
-  const E2 acc = run_air<ExtF>(a.prog, a.n_instr, a.consts, proof + a.o_public, load, sel, alpha);
+  const u64* pcoef = a.consts + a.per_coef;
+  auto per = [&](uint32_t i) -> E2 { return p3_periodic_at(pcoef + p3_per_offset(i), p3_per_log_period(i), a.k, zeta); };
+  const E2 acc = run_air<ExtF>(a.prog, a.n_instr, a.consts, proof + a.o_public, load, per, sel, alpha);
   const E2 lhs = gl::mul(acc, gl::inv(z_h));
   // zps_c = prod_{j != c} Z_{D_j}(zeta) / Z_{D_j}(s_c),  Z_{D_j}(x) = (x / s_j)^n - 1
   E2 at_zeta[8];

@@ -513,7 +513,7 @@ p25_status p25_circuit_wait_mark(p25_circuit* c, p25_circuit* producer, uint32_t
  * step k when it has enqueued it and lets the gather's side stream wait for that mark only after step k+1 has been
  * enqueued, so the wait never sits unsatisfied at the head of a hardware queue shared with a proving stream). */
 p25_status p25_circuit_stream_wait_mark(p25_circuit* c, uint32_t slot, void* stream);
-/* Proofs kept in flight by the batch entry points: one per-proof working set (~1.6 GB for the fib-64 circuit) and one
+/* Proofs kept in flight by the batch entry points: one per-proof working set (~1.1 GB for the fib-64 circuit) and one
  * stream of the process-wide pool each; 1..32.  Proof number i a circuit is asked for goes to context i mod depth, the count
  * running on across calls, so every context takes the same share of any run of proofs.  The default follows the hardware-queue
  * count the process runs with: 16 at the library's own request of up to two queues (12 .. 20 measure the same there, 24 and more

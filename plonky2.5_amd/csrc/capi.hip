@@ -329,17 +329,7 @@ AirProgram air_from_c(const p25_air* air, const p25_air_periodic* periodic = nul
   return p;
 }
 
-// The native plonky3 provers (Fibonacci, AIR): the proof's shape their parameters imply for an AIR of P3Config's default
-// width and degree (the Fibonacci AIR's)
-P3Config p3_shape(const P3ProveParams& prm) {
-  P3Config pc;
-  pc.fri_config.log_blowup = prm.log_blowup;
-  pc.fri_config.num_queries = prm.num_queries;
-  pc.log_trace_height = pc.degree_bits = prm.log_n;
-  pc.opening_matrix_log_max_height = prm.log_n + prm.log_blowup;
-  return pc;
-}
-// Their output: a size query (inputs_out NULL) is answered from the shape pc alone (and the n_public words behind the
+// The native plonky3 provers' (Fibonacci, AIR) output: a size query (inputs_out NULL) is answered from the shape pc alone (and the n_public words behind the
 // proof's), without proving; otherwise prove() completes pc and returns the inputs.
 template <class F>
 p25_status p3_prove_out(const P3ProveParams& prm, P3Config& pc, F&& prove, uint64_t* inputs_out, size_t cap, size_t* n_out,
@@ -347,7 +337,6 @@ p25_status p3_prove_out(const P3ProveParams& prm, P3Config& pc, F&& prove, uint6
   if (!inputs_out) {
     if (prm.log_n < 1 || prm.log_n > 22 || prm.num_queries < 1) throw std::invalid_argument("bad parameters");
     *n_out = pc.num_inputs() + n_public;
-    pc.fri_config.proof_of_work_bits = prm.pow_bits;
   } else {
     const std::vector<u64> v = prove();
     copy_out(v.data(), v.size(), inputs_out, cap, n_out);
@@ -655,9 +644,7 @@ static p25_status p3_prove_air_host(bool pv_form, const char* pc_form, const p25
       throw std::invalid_argument("an AIR of constraint degree " + std::to_string(prog.max_constraint_degree()) + " needs log_blowup >= " +
                                   std::to_string(prog.log_quotient_degree()));
     const P3ProveParams prm{log_n, log_blowup, num_queries, pow_bits, pow_start, threads < 1 ? 1 : threads};
-    P3Config pc = p3_shape(prm);
-    pc.trace_width = prog.width;
-    pc.log_quotient_degree = prog.log_quotient_degree();   // the number of quotient chunks follows from the AIR's degree (p3_prove_air)
+    P3Config pc = p3_config_for(prog, log_n, log_blowup, num_queries, pow_bits);
     auto prove = [&]() -> std::vector<u64> {
       if (!trace) throw std::invalid_argument("null trace");
       if (log_n < 1 || log_n > 22) throw std::invalid_argument("bad parameters");
@@ -1189,7 +1176,7 @@ p25_status p25_p3_prove_fibonacci(int32_t log_n, int32_t num_queries, int32_t po
   return host_guarded([&]() -> p25_status {
     if (!n_out) throw std::invalid_argument("null argument");
     const P3ProveParams prm{log_n, 1, num_queries, pow_bits, pow_start, threads < 1 ? 1 : threads};
-    P3Config pc = p3_shape(prm);
+    P3Config pc = p3_config_for(AirProgram::fibonacci(), log_n, 1, num_queries, pow_bits);
     return p3_prove_out(prm, pc, [&] { return p3_prove_fibonacci(prm, pc); }, inputs_out, cap, n_out, cfg_out);
   });
 }

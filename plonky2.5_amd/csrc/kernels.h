@@ -10,6 +10,7 @@
 #include <tuple>
 #include "dev_res.h"
 #include "gl.h"
+#include "prover_shape.h"   // merkle_tree_words, eval_scratch_words: the pure size functions
 
 // Wave priority (s_setprio, 0..3) in the SIMDs' issue arbitration.  The bulk hash kernels (k_hash_leaves*, and k_pow_search,
 // k_tree_level, k_fri_leaf_hash of a lone proof: 68 % of all VALU work, always enough of it resident to fill every issue slot) stay at 0;
@@ -32,7 +33,6 @@ namespace p25 {
 // ---------------- hashing (kernels_hash.hip) ----------------
 void launch_poseidon_permute(u64* d_states, size_t n, hipStream_t st);
 void launch_poseidon2_permute(u64* d_states, size_t n, hipStream_t st);
-size_t merkle_tree_words(size_t n_leaves, unsigned cap_height);
 size_t merkle_level_offset(size_t n_leaves, unsigned level);
 // ev_begin/ev_end (optional) bracket the leaf-sponge kernel -- the dominant kernel of the prover --
 // so bench.py can report its measured duration (roofline line).

@@ -48,11 +48,8 @@ static void launch_ext_pows(const ExtPowJobs& jobs, uint32_t n_jobs, hipStream_t
   hipLaunchKernelGGL(k_ext_pows, dim3((most + 1 + 255) / 256, n_jobs), dim3(256), 0, st, jobs);
 }
 
-// one block per polynomial: sum_k c_k z^k with lane t taking the coefficients k = t (mod S).  S = 1024
-// lanes: the per-lane Horner chain (n / S dependent extension multiplies) is what a lone proof waits for.
-constexpr uint32_t EVAL_LANES = 1024;
-constexpr uint32_t EVAL_CHUNK_LOG = 16;  // polynomials longer than 2^16 are split into chunks, one block each
-constexpr uint32_t EVAL_POW_WORDS = 2 * (EVAL_LANES + 2);  // one power table in the scratch
+// one block per polynomial: sum_k c_k z^k with lane t taking the coefficients k = t (mod S), S = EVAL_LANES
+// (prover_shape.h, with EVAL_CHUNK_LOG, EVAL_POW_WORDS and eval_scratch_words)
 // The job table of one launch: blocks [block_end[j - 1], block_end[j]) belong to job j, `chunks` blocks per polynomial.
 struct EvalJobs {
   EvalJob job[EVAL_MAX_JOBS];
@@ -123,10 +120,6 @@ __global__ void k_eval_combine(EvalJobs a) {
   jb.out[2 * local + 1] = acc.b;
 }
 
-size_t eval_scratch_words(uint32_t n_points, size_t total_polys, uint32_t log_n) {
-  const size_t chunks = log_n > EVAL_CHUNK_LOG ? (size_t)1 << (log_n - EVAL_CHUNK_LOG) : 1;
-  return (size_t)n_points * EVAL_POW_WORDS + 2 * total_polys * chunks;
-}
 void launch_eval_jobs(const EvalJob* jobs, uint32_t n_jobs, uint32_t log_n, const u64* d_point, const u64* scale,
                       uint32_t n_points, u64* d_scratch, hipStream_t st) {
   if (!n_jobs || n_jobs > EVAL_MAX_JOBS || !n_points || n_points > 2) throw std::invalid_argument("launch_eval_jobs: bad job table");

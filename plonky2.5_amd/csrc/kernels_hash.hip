@@ -260,15 +260,6 @@ void launch_poseidon2_permute(u64* d_states, size_t n, hipStream_t st) {
   hipLaunchKernelGGL(k_poseidon2_permute, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_states, n);
 }
 
-size_t merkle_tree_words(size_t n_leaves, unsigned cap_height) {
-  // levels 0 (leaf digests) .. log2(n) - cap_height (the cap), 4 words per node
-  size_t total = 0;
-  for (size_t m = n_leaves; m >= ((size_t)1 << cap_height); m >>= 1) {
-    total += 4 * m;
-    if (m == 1) break;
-  }
-  return total;
-}
 size_t merkle_level_offset(size_t n_leaves, unsigned level) {
   size_t off = 0;
   size_t m = n_leaves;

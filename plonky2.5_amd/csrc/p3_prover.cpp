@@ -206,16 +206,35 @@ std::vector<u64> p3_prove_air(const AirProgram& air, const std::vector<std::vect
   return p3_prove_air_pv(air, col, std::vector<u64>(), prm, cfg);
 }
 
-std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::vector<u64>>& col, const std::vector<u64>& pub,
-                                 const P3ProveParams& prm, P3Config& cfg) {
+void p3_check_params(const AirProgram& air, int log_n, int log_blowup, int num_queries, int pow_bits) {
   // FriConfig.log_blowup (src/p3/mod.rs:242-246; verifier.rs uses config.log_blowup generically): the LDE domain is
   // 7*H_{n 2^B}, B = 1..4 (what p25_circuit_build_p3_verifier accepts); B = 1 is the reference's artifact, B = 2, 3 hold AIRs of
   // constraint degree up to 5 / 9 (four / eight chunks)
-  if (prm.log_n < 1 || prm.log_n > 22 || prm.log_blowup < 1 || prm.log_blowup > 4 || prm.log_n + prm.log_blowup > 24 ||
-      prm.num_queries < 1 || prm.pow_bits < 0 || prm.pow_bits > 30)
+  if (log_n < 1 || log_n > 22 || log_blowup < 1 || log_blowup > 4 || log_n + log_blowup > 24 || num_queries < 1 || pow_bits < 0 ||
+      pow_bits > 30)
     throw std::invalid_argument("p3_prove: unsupported parameters");
   air.validate();
-  air.check_periodic(prm.log_n);
+  air.check_periodic(log_n);
+  if (air.log_quotient_degree() > log_blowup)
+    throw std::invalid_argument("p3_prove: the AIR's constraint degree needs more quotient chunks than log_blowup holds");
+}
+P3Config p3_config_for(const AirProgram& air, int log_n, int log_blowup, int num_queries, int pow_bits) {
+  P3Config cfg;
+  cfg.fri_config.log_blowup = log_blowup;
+  cfg.fri_config.num_queries = num_queries;
+  cfg.fri_config.proof_of_work_bits = pow_bits;
+  cfg.log_quotient_degree = air.log_quotient_degree();
+  cfg.log_trace_height = log_n;
+  cfg.trace_width = air.width;
+  cfg.opening_matrix_log_max_height = log_n + log_blowup;
+  cfg.opening_proof_query_openings_opened_values_length = 2;
+  cfg.degree_bits = log_n;
+  return cfg;
+}
+
+std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::vector<u64>>& col, const std::vector<u64>& pub,
+                                 const P3ProveParams& prm, P3Config& cfg) {
+  p3_check_params(air, prm.log_n, prm.log_blowup, prm.num_queries, prm.pow_bits);
   const int k = prm.log_n, B = prm.log_blowup, L = k + B, T = prm.threads;
   const size_t n = (size_t)1 << k, N2 = n << B;      // N2: the LDE domain's size (2 n for the reference's log_blowup 1)
   const u64 w_n = gl::root_of_unity(k), w_2n = gl::root_of_unity(L);
@@ -251,8 +270,7 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
   // degree 3: lqd = 1; degree 4, 5: lqd = 2 (needs log_blowup >= 2).  The quotient domain is the disjoint coset 7*H_{n 2^lqd}
   // (verifier.rs:120-124): points x_j = 7 w^j = LDE natural index j * 2^(B - lqd), so the trace's LDE already holds the trace
   // there as long as lqd <= log_blowup.
-  const int lqd = air.log_quotient_degree();
-  if (lqd > B) throw std::invalid_argument("p3_prove: the AIR's constraint degree needs more quotient chunks than log_blowup holds");
+  const int lqd = air.log_quotient_degree();   // <= B: p3_check_params
   const size_t Q = (size_t)1 << lqd, nq = n << lqd;          // chunks, quotient-domain size
   const size_t lde_step = (size_t)1 << (B - lqd);              // LDE index step between quotient-domain points
   const size_t row_step = (size_t)1 << B;                      // ... and between a row and the next (x w_n)
@@ -439,16 +457,7 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
   for (auto& ix : indices) ix = (size_t)ch.sample_bits(L);
 
   // flatten in add_virtual_to order (proof.rs:357-373)
-  cfg = P3Config();
-  cfg.fri_config.log_blowup = prm.log_blowup;
-  cfg.fri_config.num_queries = prm.num_queries;
-  cfg.fri_config.proof_of_work_bits = prm.pow_bits;
-  cfg.log_quotient_degree = lqd;
-  cfg.log_trace_height = k;
-  cfg.trace_width = W;
-  cfg.opening_matrix_log_max_height = L;
-  cfg.opening_proof_query_openings_opened_values_length = 2;
-  cfg.degree_bits = k;
+  cfg = p3_config_for(air, k, B, prm.num_queries, prm.pow_bits);
   std::vector<u64> out;
   auto push_d = [&](const Digest& d) { out.insert(out.end(), d.begin(), d.end()); };
   auto push_e = [&](E2 e) {

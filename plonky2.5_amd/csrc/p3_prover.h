@@ -30,6 +30,11 @@ struct P3ProveParams {
   u64 pow_start = 0;
   int threads = 1;
 };
+// What every plonky3 prover of the library holds of its parameters, host and device: the ranges, the AIR's own checks, and
+// a constraint degree that log_blowup's quotient chunks can hold.  Throws std::invalid_argument.
+void p3_check_params(const AirProgram& air, int log_n, int log_blowup, int num_queries, int pow_bits);
+// The shape of the proof these parameters give for `air` (no checks: a size query answers from it before any)
+P3Config p3_config_for(const AirProgram& air, int log_n, int log_blowup, int num_queries, int pow_bits);
 // Returns the proof as the flat input vector (add_virtual_to order) and its shape.
 std::vector<u64> p3_prove_fibonacci(const P3ProveParams& prm, P3Config& cfg_out);
 // Same prover for any AIR given as a program (p3_circuit.h: AirProgram) and its trace, col[c][row];

@@ -4,6 +4,7 @@
 #include <functional>
 #include "p3_prover.h"
 #include "p3_prover_impl.h"
+#include "staging.h"
 
 namespace p25 {
 
@@ -111,29 +112,12 @@ P3AirDevice P3AirDevice::compile(const AirProgram& air) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int num_queries, int pow_bits) {
-  // exactly p3_prove_air's checks (p3_prover.cpp:194-230)
-  if (log_n < 1 || log_n > 22 || log_blowup < 1 || log_blowup > 4 || log_n + log_blowup > 24 || num_queries < 1 || pow_bits < 0 ||
-      pow_bits > 30)
-    throw std::invalid_argument("p3_prove: unsupported parameters");
-  air.validate();
-  air.check_periodic(log_n);
-  const int lqd = air.log_quotient_degree();
-  if (lqd > log_blowup)
-    throw std::invalid_argument("p3_prove: the AIR's constraint degree needs more quotient chunks than log_blowup holds");
+  p3_check_params(air, log_n, log_blowup, num_queries, pow_bits);
   if (num_queries > 65535) throw std::invalid_argument("p25_p3_prover_create: more than 65535 queries (the gather's grid limit)");
   prog_ = P3AirDevice::compile(air);
-  const int k = log_n, B = log_blowup, L = k + B, W = air.width;
+  cfg_ = p3_config_for(air, log_n, log_blowup, num_queries, pow_bits);
+  const int k = log_n, B = log_blowup, L = k + B, W = air.width, lqd = cfg_.log_quotient_degree;
   const size_t n = (size_t)1 << k, Q = (size_t)1 << lqd;
-  cfg_ = P3Config();
-  cfg_.fri_config.log_blowup = B;
-  cfg_.fri_config.num_queries = num_queries;
-  cfg_.fri_config.proof_of_work_bits = pow_bits;
-  cfg_.log_quotient_degree = lqd;
-  cfg_.log_trace_height = k;
-  cfg_.trace_width = W;
-  cfg_.opening_matrix_log_max_height = L;
-  cfg_.opening_proof_query_openings_opened_values_length = 2;
-  cfg_.degree_bits = k;
 
   P3Shape& s = shape_;
   s = P3Shape{};
@@ -339,10 +323,7 @@ void P3ProverDev::prove_host(const u64* traces, const u64* public_values, size_t
   prove_dev(d_traces.p, tw, np ? d_pub.p : nullptr, n_proofs, pow_starts ? d_pow.p : nullptr, d_out.p, ni, reinterpret_cast<uint32_t*>(d_status.p), st);
   // the input_stride - num_inputs words behind a proof stay untouched
   P25_HIP(hipMemcpy2DAsync(inputs_out, input_stride * 8, d_out.p, ni * 8, ni * 8, n_proofs, hipMemcpyDeviceToHost, st));
-  std::vector<uint32_t> hs(n_proofs);
-  P25_HIP(hipMemcpyAsync(hs.data(), d_status.p, n_proofs * 4, hipMemcpyDeviceToHost, st));
-  P25_HIP(hipStreamSynchronize(st));
-  for (size_t i = 0; i < n_proofs; i++) statuses[i] = (int32_t)hs[i];
+  statuses_to_host(reinterpret_cast<const uint32_t*>(d_status.p), n_proofs, statuses, st);
 }
 
 }  // namespace p25

@@ -3,6 +3,7 @@
 // and event chain with the prover (p3_prover_dev.hip) and none of its scratch.
 #include <algorithm>
 #include "p3_prover_impl.h"
+#include "staging.h"
 #include "p3_verify_lanes.h"
 
 namespace p25 {
@@ -92,10 +93,7 @@ void P3ProverDev::verify_host(const u64* inputs, size_t n_proofs, size_t input_s
   // the input_stride - num_inputs words behind a proof stay on the host: they are not read
   P25_HIP(hipMemcpy2DAsync(d_in.p, ni * 8, inputs, input_stride * 8, ni * 8, n_proofs, hipMemcpyHostToDevice, st));
   verify_dev(d_in.p, n_proofs, ni, reinterpret_cast<uint32_t*>(d_status.p), st);
-  std::vector<uint32_t> hs(n_proofs);
-  P25_HIP(hipMemcpyAsync(hs.data(), d_status.p, n_proofs * 4, hipMemcpyDeviceToHost, st));
-  P25_HIP(hipStreamSynchronize(st));
-  for (size_t i = 0; i < n_proofs; i++) statuses[i] = (int32_t)hs[i];
+  statuses_to_host(reinterpret_cast<const uint32_t*>(d_status.p), n_proofs, statuses, st);
 }
 
 }  // namespace p25

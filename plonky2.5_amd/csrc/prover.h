@@ -9,6 +9,7 @@
 #include "builder.h"
 #include "inflight.h"
 #include "prover_kernels.h"
+#include "working_set.h"
 
 namespace p25 {
 
@@ -22,26 +23,13 @@ struct ProofLayout {
   uint32_t final_poly_len;
 };
 ProofLayout make_proof_layout(const Circuit& c);
+ProverShape make_prover_shape(const Circuit& c, const ProofLayout& layout);
 
-// FRI working set and shape: shared by the whole-proof pipeline and the standalone p25_fri_prove entry point.
-struct FriWork {
-  DevMem coeffs[9], vals[9], tree[9];
-  void alloc(int log_n, int rate_bits, unsigned cap_height, const std::vector<int>& arity_bits);
-};
-struct FriShape {
-  int log_n, rate_bits;
-  unsigned cap_height;
-  std::vector<int> arity_bits;
-  int pow_bits, num_queries;
-};
-struct FriOffsets {  // word offsets into the flat proof buffer
-  size_t caps, final_poly, pow_witness, queries, query_stride;
-};
 void fri_commit_pow_query(NttTables& tables, FriWork& w, const FriShape& sh, Transcript* tr, u64* chal, QueryArgs qy,
                           u64* d_proof, const FriOffsets& fo, uint32_t* d_status, hipStream_t st, bool single_proof);
 
 void transcript_script(const u64* obs, const uint32_t* seg_len, const uint32_t* n_chal, size_t n_seg, u64* out);
-size_t fri_prove_words(const FriShape& sh);
+inline size_t fri_prove_words(const FriShape& sh) { return fri_standalone_layout(sh).out_words; }
 void fri_prove_standalone(NttTables& tables, const u64* coeffs, const FriShape& sh, const u64* seed, size_t n_seed,
                           u64* out, int32_t* status_out);
 
@@ -73,8 +61,6 @@ class DeviceCircuit {
   // host copies of the constants/sigmas commitment (coefficients, LDE in leaf order, Merkle tree) for
   // CircuitData::to_bytes (circuit_bytes.h)
   void commitment_to_host(std::vector<u64>& coeffs, std::vector<u64>& lde, std::vector<u64>& tree);
-  size_t n() const { return c_.degree(); }
-  size_t big() const { return c_.degree() << c_.cfg.rate_bits; }
 
   // Proves n_proofs independent inputs.  inputs[n_proofs][num_inputs] (host), seeds (host, nullable),
   // proofs_out[n_proofs][proof_stride] (host), statuses[n_proofs].  Returns first non-zero HIP-level
@@ -143,13 +129,14 @@ class DeviceCircuit {
   // alpha_table: launch the alpha-power table kernel first (prove_one gets the table from its transcript launch)
   void enqueue_quotient(Ctx& cx, hipStream_t st, bool alpha_table = true);
   void set_challenges(Ctx& cx, const u64* betas, const u64* gammas, const u64* alphas);
-  size_t ctx_bytes() const;
+  size_t ctx_bytes() const { return 8 * working_set_words(shape_); }   // device bytes of one proof context
   void ensure_ctx(size_t count);
   void ensure_vals(int buf, size_t batch);   // vals_[buf] holds at least `batch` proofs
 
   MainStreamLease main_lease_;   // first member: given back also when the constructor throws further down
   Circuit c_;
   ProofLayout layout_;
+  ProverShape shape_;   // the circuit's dimensions: what every size and launch below reads
   NttTables tables_;
   DeviceWitnessProgram wp_;
   DevMem cs_vals_, cs_coeffs_, cs_lde_, cs_tree_, k_is_, preamble_, l0_inv_;

@@ -5,6 +5,7 @@
 #include <mutex>
 #include <string.h>
 #include "poseidon.h"
+#include "staging.h"
 
 namespace p25 {
 
@@ -136,22 +137,13 @@ ProofLayout make_proof_layout(const Circuit& c) {
   return L;
 }
 
-// ---------------------------------------------------------------- FRI (upstream fri/prover.rs `fri_proof`)
-void FriWork::alloc(int log_n, int rate_bits, unsigned cap_height, const std::vector<int>& arity_bits) {
-  size_t m = (size_t)1 << log_n;
-  const size_t nl = arity_bits.size();
-  if (nl > 8) throw std::invalid_argument("too many FRI layers");
-  for (size_t l = 0; l <= nl; l++) {
-    coeffs[l] = DevMem(2 * m);
-    if (l < nl) {
-      size_t nvals = m << rate_bits;
-      vals[l] = DevMem(2 * nvals);
-      tree[l] = DevMem(merkle_tree_words(nvals >> arity_bits[l], cap_height));
-      m >>= arity_bits[l];
-    }
-  }
+ProverShape make_prover_shape(const Circuit& c, const ProofLayout& L) {
+  return prover_shape(c.degree_bits, c.cfg.rate_bits, c.cfg.cap_height, c.cfg.num_wires, c.cfg.num_challenges,
+                      c.num_partial_products, c.cfg.max_quotient_degree_factor, L.oracle_width[0], c.fri_reduction_arity_bits,
+                      L.total, sizeof(Transcript) / 8 + 1, CH_WORDS, 2 * ALPHA_POWS);
 }
 
+// ---------------------------------------------------------------- FRI (upstream fri/prover.rs `fri_proof`)
 // Commit phase ("fold codewords in the commitment phase"), "find proof-of-work witness", query rounds.
 // In: the batched polynomial's coefficients in w.coeffs[0] (components a | b, n each), the transcript, and the
 // initial-oracle part of `qy` (n_oracles may be 0).  Out: caps, final polynomial, PoW witness and query openings
@@ -227,64 +219,14 @@ void fri_commit_pow_query(NttTables& tables, FriWork& w, const FriShape& sh, Tra
 }
 
 // ---------------------------------------------------------------- per-proof working set
-struct DeviceCircuit::Ctx {
-  DevMem wires_vals, wires_coeffs, tmp, wires_lde, wires_tree;
-  DevMem zs_vals, zs_coeffs, zs_lde, zs_tree, zpp_chunk, zpp_tot, zpp_btot;
-  DevMem q_vals, q_tmp, q_coeffs, q_lde, q_tree;
-  DevMem transcript, chal, alpha_pows, eval_pows;
-  DevMem preamble;  // circuit_digest[4] | public_inputs_hash[4] of the proof in flight: what the transcript absorbs first
-  DevMem fri_comp, fri_scan;
-  FriWork fri;
-  DevMem proof, status;
-  DevEvent ev[12];             // PhaseTimes marks
+// The buffers and events are the WorkingSet's (working_set.h), whole before anything here is touched.
+struct DeviceCircuit::Ctx : WorkingSet {
   hipStream_t st = nullptr;    // a stream of the process-wide pool (never destroyed)
-  // done[b]: recorded after the context's latest read of witness-value buffer b (DeviceCircuit::vals_[b])
-  DevEvent done[2];
   DevEvent join;               // DeviceCircuit::stream_join: created by its first call
-  // Everything a context owns: a constructor that throws half way gives back what it had made.
-  Ctx(const DeviceCircuit& dc, hipStream_t stream);
+  Ctx(const DeviceCircuit& dc, hipStream_t stream) : WorkingSet(dc.shape_), st(stream) {
+    P25_HIP(hipMemcpy(preamble.p, dc.preamble_.p, 64, hipMemcpyDeviceToDevice));  // digest | hash_no_pad([]) = zeros
+  }
 };
-
-DeviceCircuit::Ctx::Ctx(const DeviceCircuit& dc, hipStream_t stream) : st(stream) {
-  const Circuit& c = dc.c_;
-  const ProofLayout& L = dc.layout_;
-  for (auto& e : done) e.create(hipEventDisableTiming);
-  const size_t n = c.degree(), B = dc.big();
-  const int W = c.cfg.num_wires, NC = c.cfg.num_challenges, NP = c.num_partial_products;
-  const int nz = NC * (1 + NP), nq = NC * c.cfg.max_quotient_degree_factor;
-  const size_t tw = merkle_tree_words(B, c.cfg.cap_height);
-  wires_vals = DevMem((size_t)W * n);
-  wires_coeffs = DevMem((size_t)W * n);
-  tmp = DevMem((size_t)W * n);
-  wires_lde = DevMem((size_t)W * B);
-  wires_tree = DevMem(tw);
-  zs_vals = DevMem((size_t)nz * n);
-  zs_coeffs = DevMem((size_t)nz * n);
-  zs_lde = DevMem((size_t)nz * B);
-  zs_tree = DevMem(tw);
-  zpp_chunk = DevMem((size_t)NC * (NP + 1) * n);
-  zpp_tot = DevMem((size_t)NC * n);
-  zpp_btot = DevMem((size_t)NC * ((n + 255) / 256) + 16);
-  q_vals = DevMem((size_t)NC * B);
-  q_tmp = DevMem((size_t)NC * B);
-  q_coeffs = DevMem((size_t)NC * B);
-  q_lde = DevMem((size_t)nq * B);
-  q_tree = DevMem(tw);
-  preamble = DevMem(8);
-  P25_HIP(hipMemcpy(preamble.p, dc.preamble_.p, 64, hipMemcpyDeviceToDevice));  // digest | hash_no_pad([]) = zeros
-  transcript = DevMem(sizeof(Transcript) / 8 + 1);
-  chal = DevMem(CH_WORDS);
-  alpha_pows = DevMem(2 * ALPHA_POWS);
-  // the power tables of zeta and g zeta, followed by the per-chunk partial sums of the openings (launch_eval_jobs)
-  eval_pows = DevMem(eval_scratch_words(2, (size_t)L.oracle_width[0] + W + nz + nq + NC, (uint32_t)c.degree_bits));
-  fri_comp = DevMem(4 * n);
-  const size_t total_polys = L.oracle_width[0] + L.oracle_width[1] + L.oracle_width[2] + L.oracle_width[3];
-  fri_scan = DevMem(2 * (total_polys + 1) + 8 * (n + 1) + 4 * ((n + 255) / 256) + 64);
-  fri.alloc(c.degree_bits, c.cfg.rate_bits, c.cfg.cap_height, c.fri_reduction_arity_bits);
-  proof = DevMem(L.total);
-  status = DevMem(1);
-  for (auto& e : ev) e.create();
-}
 
 DeviceCircuit::DeviceCircuit(Circuit c) : c_(std::move(c)) {
   if (c_.cfg.num_challenges != 2 || c_.cfg.rate_bits > 3 || c_.gates.size() > 16)
@@ -296,8 +238,9 @@ DeviceCircuit::DeviceCircuit(Circuit c) : c_(std::move(c)) {
     throw std::invalid_argument("circuit exceeds the permutation-argument / quotient kernels' capacities");
   stream_ = g_stream_pool.main_acquire(main_lease_);
   layout_ = make_proof_layout(c_);
-  const size_t n = c_.degree();
-  const int ncs = (int)c_.constants_sigmas.size();
+  shape_ = make_prover_shape(c_, layout_);
+  const size_t n = shape_.n, B = shape_.B, tw = shape_.tw, capw = shape_.capw;
+  const int ncs = (int)shape_.oracle_width[0], db = shape_.degree_bits, rb = shape_.rate_bits;
   // witness program
   WitnessProgram wp = build_witness_program(c_);
   auto up32 = [&](const std::vector<uint32_t>& v) {
@@ -352,17 +295,14 @@ DeviceCircuit::DeviceCircuit(Circuit c) : c_(std::move(c)) {
   for (int p = 0; p < ncs; p++)
     P25_HIP(hipMemcpy(cs_vals_.p + (size_t)p * n, c_.constants_sigmas[p].data(), n * 8, hipMemcpyHostToDevice));
   cs_coeffs_ = DevMem((size_t)ncs * n);
-  cs_lde_ = DevMem((size_t)ncs * big());
-  const size_t tw = merkle_tree_words(big(), c_.cfg.cap_height);
+  cs_lde_ = DevMem((size_t)ncs * B);
   cs_tree_ = DevMem(tw);
   {
     DevMem tmp((size_t)ncs * n);
-    ntt_inverse_then_lde(tables_, cs_vals_.p, n, tmp.p, n, cs_coeffs_.p, n, cs_lde_.p, big(), c_.degree_bits, c_.cfg.rate_bits, ncs,
-                         gl::GENERATOR, stream_);
-    launch_merkle_tree(cs_lde_.p, big(), ncs, big(), c_.cfg.cap_height, cs_tree_.p, stream_);
+    ntt_inverse_then_lde(tables_, cs_vals_.p, n, tmp.p, n, cs_coeffs_.p, n, cs_lde_.p, B, db, rb, ncs, gl::GENERATOR, stream_);
+    launch_merkle_tree(cs_lde_.p, B, ncs, B, shape_.cap_height, cs_tree_.p, stream_);
     P25_HIP(hipStreamSynchronize(stream_));
   }
-  const size_t capw = (size_t)4 << c_.cfg.cap_height;
   cs_cap_.resize(capw);
   P25_HIP(hipMemcpy(cs_cap_.data(), cs_tree_.p + tw - capw, capw * 8, hipMemcpyDeviceToHost));
   // circuit_digest = H(cap || H_pad([]) || [degree_bits])  (host; once per circuit)
@@ -386,7 +326,7 @@ DeviceCircuit::DeviceCircuit(Circuit c) : c_(std::move(c)) {
   // quotient argument prototype
   memset(&qa_proto_, 0, sizeof(qa_proto_));
   qa_proto_.cs_lde = cs_lde_.p;
-  qa_proto_.pow_big = tables_.pow_table(c_.degree_bits + c_.cfg.rate_bits, false);
+  qa_proto_.pow_big = tables_.pow_table(db + rb, false);
   qa_proto_.k_is = k_is_.p;
   qa_proto_.n_gates = (uint32_t)c_.gates.size();
   for (size_t i = 0; i < c_.gates.size(); i++) {
@@ -394,22 +334,22 @@ DeviceCircuit::DeviceCircuit(Circuit c) : c_(std::move(c)) {
     qa_proto_.gates[i] = GateEntry{(uint32_t)c_.gates[i], (uint32_t)s, (uint32_t)c_.groups[s].first, (uint32_t)c_.groups[s].second};
   }
   qa_proto_.num_selectors = c_.num_selectors;
-  qa_proto_.num_wires = c_.cfg.num_wires;
+  qa_proto_.num_wires = shape_.W;
   qa_proto_.num_routed = c_.cfg.num_routed_wires;
-  qa_proto_.num_partial_products = c_.num_partial_products;
+  qa_proto_.num_partial_products = shape_.NP;
   qa_proto_.quotient_degree_factor = c_.cfg.max_quotient_degree_factor;
-  qa_proto_.degree_bits = c_.degree_bits;
-  qa_proto_.rate_bits = c_.cfg.rate_bits;
+  qa_proto_.degree_bits = db;
+  qa_proto_.rate_bits = rb;
   {
-    u64 g_pow_n = gl::exp_pow2(gl::GENERATOR, c_.degree_bits);
-    u64 wr = gl::root_of_unity(c_.cfg.rate_bits);
-    for (int k = 0; k < (1 << c_.cfg.rate_bits); k++) {
+    u64 g_pow_n = gl::exp_pow2(gl::GENERATOR, db);
+    u64 wr = gl::root_of_unity(rb);
+    for (int k = 0; k < (1 << rb); k++) {
       qa_proto_.zh[k] = gl::sub(gl::mul(g_pow_n, gl::pow(wr, k)), 1);
       qa_proto_.zh_inv[k] = gl::inv(qa_proto_.zh[k]);
     }
   }
-  l0_inv_ = DevMem(big());
-  launch_l0_inv(qa_proto_.pow_big, c_.degree_bits, c_.cfg.rate_bits, l0_inv_.p, stream_);
+  l0_inv_ = DevMem(B);
+  launch_l0_inv(qa_proto_.pow_big, db, rb, l0_inv_.p, stream_);
   P25_HIP(hipStreamSynchronize(stream_));
   qa_proto_.l0_inv = l0_inv_.p;
 }
@@ -524,13 +464,10 @@ void DeviceCircuit::prove_one(Ctx& x, const Pass& pass, uint32_t p, u64* d_proof
   const bool single_proof = pass.single_proof;
   const u64* d_vals = vals_[buf].p;
   hipStream_t st = x.st;
-  const size_t n = c_.degree(), B = big();
-  const int W = c_.cfg.num_wires, NC = c_.cfg.num_challenges, NP = c_.num_partial_products;
-  const int nz = NC * (1 + NP), nq = NC * c_.cfg.max_quotient_degree_factor;
-  const int db = c_.degree_bits, rb = c_.cfg.rate_bits;
-  const unsigned cap_h = c_.cfg.cap_height;
-  const size_t capw = (size_t)4 << cap_h;
-  const size_t tw = merkle_tree_words(B, cap_h);
+  const ProverShape& s = shape_;
+  const size_t n = s.n, B = s.B, capw = s.capw, tw = s.tw;
+  const int W = s.W, NC = s.NC, NP = s.NP, nz = s.nz, nq = s.nq, db = s.degree_bits, rb = s.rate_bits;
+  const unsigned cap_h = s.cap_height;
   const ProofLayout& L = layout_;
   Transcript* tr = (Transcript*)x.transcript.p;
   u64* chal = x.chal.p;
@@ -654,7 +591,7 @@ void DeviceCircuit::prove_one(Ctx& x, const Pass& pass, uint32_t p, u64* d_proof
       qy.oracle_tree[k] = trees[k];
       qy.oracle_width[k] = L.oracle_width[k];
     }
-    FriShape sh{db, rb, cap_h, c_.fri_reduction_arity_bits, c_.cfg.proof_of_work_bits, c_.cfg.num_query_rounds};
+    FriShape sh{db, rb, cap_h, s.arity_bits, c_.cfg.proof_of_work_bits, c_.cfg.num_query_rounds};
     FriOffsets fo{L.fri_caps, L.final_poly, L.pow_witness, L.queries, L.query_stride};
     fri_commit_pow_query(tables_, x.fri, sh, tr, chal, qy, d_proof, fo, d_status, st, single_proof);
   }
@@ -681,34 +618,28 @@ void DeviceCircuit::prove_one(Ctx& x, const Pass& pass, uint32_t p, u64* d_proof
 // "compute partial products": Z and partial products (values, natural row order) from the witness values and
 // betas / gammas of the context's challenge block.
 void DeviceCircuit::enqueue_partial_products(Ctx& x, hipStream_t st) {
-  const size_t n = c_.degree();
-  const int NC = c_.cfg.num_challenges, NP = c_.num_partial_products, db = c_.degree_bits;
-  u64* chal = x.chal.p;
-  {
-    ZppArgs za;
-    za.wires = x.wires_vals.p;
-    za.sigmas = cs_vals_.p + (size_t)(c_.num_selectors + c_.cfg.num_constants) * n;
-    za.pow_n = tables_.pow_table(db, false);
-    za.k_is = k_is_.p;
-    za.chal = chal;
-    za.chunk = x.zpp_chunk.p;
-    za.tot = x.zpp_tot.p;
-    za.block_tot = x.zpp_btot.p;
-    za.out = x.zs_vals.p;
-    za.n = (uint32_t)n;
-    za.num_routed = c_.cfg.num_routed_wires;
-    za.num_partial_products = NP;
-    za.num_challenges = NC;
-    za.quotient_degree_factor = c_.cfg.max_quotient_degree_factor;
-    launch_zpp(za, st);
-  }
+  ZppArgs za;
+  za.wires = x.wires_vals.p;
+  za.sigmas = cs_vals_.p + (size_t)(c_.num_selectors + c_.cfg.num_constants) * shape_.n;
+  za.pow_n = tables_.pow_table(shape_.degree_bits, false);
+  za.k_is = k_is_.p;
+  za.chal = x.chal.p;
+  za.chunk = x.zpp_chunk.p;
+  za.tot = x.zpp_tot.p;
+  za.block_tot = x.zpp_btot.p;
+  za.out = x.zs_vals.p;
+  za.n = (uint32_t)shape_.n;
+  za.num_routed = c_.cfg.num_routed_wires;
+  za.num_partial_products = shape_.NP;
+  za.num_challenges = shape_.NC;
+  za.quotient_degree_factor = c_.cfg.max_quotient_degree_factor;
+  launch_zpp(za, st);
 }
 
 // "compute quotient polys": quotient values on the coset from the wires / Z LDEs and the challenge block, then the
 // coset iNTT to 8n coefficients per challenge (= the NC x 8 chunks of n, contiguous).
 void DeviceCircuit::enqueue_quotient(Ctx& x, hipStream_t st, bool alpha_table) {
-  const size_t B = big();
-  const int NC = c_.cfg.num_challenges, lde_bits = c_.degree_bits + c_.cfg.rate_bits;
+  const size_t B = shape_.B;
   u64* chal = x.chal.p;
   if (alpha_table) launch_alpha_pows(chal, x.alpha_pows.p, st);  // prove_one: the transcript launch that drew the alphas wrote it
   {
@@ -722,13 +653,14 @@ void DeviceCircuit::enqueue_quotient(Ctx& x, hipStream_t st, bool alpha_table) {
     launch_quotient(qa, st);
   }
   // coset iNTT of the 2 value vectors (stored at bit-reversed positions) -> 8n coefficients each
-  ntt_inverse(tables_, x.q_vals.p, B, true, x.q_tmp.p, B, x.q_coeffs.p, B, lde_bits, NC, gl::GENERATOR, st);
+  ntt_inverse(tables_, x.q_vals.p, B, true, x.q_tmp.p, B, x.q_coeffs.p, B, shape_.degree_bits + shape_.rate_bits, shape_.NC,
+              gl::GENERATOR, st);
 }
 
 // ---------------------------------------------------------------- isolated stages (parity tests; include/p25.h)
 void DeviceCircuit::set_challenges(Ctx& x, const u64* betas, const u64* gammas, const u64* alphas) {
   u64 ch[CH_WORDS] = {0};
-  for (int i = 0; i < c_.cfg.num_challenges; i++) {
+  for (int i = 0; i < shape_.NC; i++) {
     if (betas) ch[CH_BETAS + i] = betas[i];
     if (gammas) ch[CH_GAMMAS + i] = gammas[i];
     if (alphas) ch[CH_ALPHAS + i] = alphas[i];
@@ -746,8 +678,7 @@ void DeviceCircuit::partial_products(const u64* wires, const u64* betas, const u
   ensure_ctx(1);
   sync();
   Ctx& x = *ctxs_[0];
-  const size_t n = c_.degree();
-  const size_t W = c_.cfg.num_wires, nz = (size_t)c_.cfg.num_challenges * (1 + c_.num_partial_products);
+  const size_t n = shape_.n, W = shape_.W, nz = shape_.nz;
   check_canonical(wires, W * n, "wires");
   set_challenges(x, betas, gammas, nullptr);
   P25_HIP(hipMemcpyAsync(x.wires_vals.p, wires, W * n * 8, hipMemcpyHostToDevice, x.st));
@@ -761,9 +692,8 @@ void DeviceCircuit::quotient(const u64* wires, const u64* zs_pp, const u64* beta
   ensure_ctx(1);
   sync();
   Ctx& x = *ctxs_[0];
-  const size_t n = c_.degree(), B = big();
-  const int W = c_.cfg.num_wires, NC = c_.cfg.num_challenges, nz = NC * (1 + c_.num_partial_products);
-  const int db = c_.degree_bits, rb = c_.cfg.rate_bits;
+  const size_t n = shape_.n, B = shape_.B;
+  const int W = shape_.W, NC = shape_.NC, nz = shape_.nz, db = shape_.degree_bits, rb = shape_.rate_bits;
   check_canonical(wires, (size_t)W * n, "wires");
   check_canonical(zs_pp, (size_t)nz * n, "zs_partial_products");
   set_challenges(x, betas, gammas, alphas);
@@ -821,17 +751,6 @@ void transcript_script(const u64* obs, const uint32_t* seg_len, const uint32_t* 
   P25_HIP(hipGetLastError());
 }
 
-size_t fri_prove_words(const FriShape& sh) {
-  const size_t capw = (size_t)4 << sh.cap_height, nl = sh.arity_bits.size();
-  int deg = sh.log_n, bits = sh.log_n + sh.rate_bits;
-  size_t per_q = 0;
-  for (int a : sh.arity_bits) {
-    deg -= a;
-    bits -= a;
-    per_q += 2 * ((size_t)1 << a) + 4 * (size_t)(bits - (int)sh.cap_height);
-  }
-  return nl * capw + 2 * nl + 2 * ((size_t)1 << deg) + 1 + sh.num_queries + per_q * sh.num_queries;
-}
 // out: CAP[n_layers] | betas E[n_layers] | final_poly E[..] | pow_witness | indices[num_queries] | query openings
 void fri_prove_standalone(NttTables& tables, const u64* coeffs, const FriShape& sh, const u64* seed, size_t n_seed,
                           u64* out, int32_t* status_out) {
@@ -839,25 +758,19 @@ void fri_prove_standalone(NttTables& tables, const u64* coeffs, const FriShape& 
   check_canonical(coeffs, 2 * n, "polynomial coefficients");
   check_canonical(seed, n_seed, "transcript seed");
   int deg = sh.log_n, bits = sh.log_n + sh.rate_bits;
-  size_t per_q = 0;
   for (int a : sh.arity_bits) {
     if (a < 1 || a > 8) throw std::invalid_argument("FRI arity bits must be in 1..8");
     deg -= a;
     bits -= a;
     if (deg < 0 || bits < (int)sh.cap_height) throw std::invalid_argument("FRI layer smaller than the Merkle cap");
-    per_q += 2 * ((size_t)1 << a) + 4 * (size_t)(bits - (int)sh.cap_height);
   }
   if (sh.num_queries < 1 || sh.num_queries > 64 || sh.pow_bits < 0 || sh.pow_bits > 32 || sh.rate_bits < 0 || sh.rate_bits > 3)
     throw std::invalid_argument("FRI parameters out of range");
   FriWork w;
   w.alloc(sh.log_n, sh.rate_bits, sh.cap_height, sh.arity_bits);
-  FriOffsets fo;
-  fo.caps = 0;
-  fo.final_poly = nl * capw;
-  fo.pow_witness = fo.final_poly + 2 * ((size_t)1 << deg);
-  fo.queries = fo.pow_witness + 1;
-  fo.query_stride = per_q;
-  const size_t proof_words = fo.queries + per_q * sh.num_queries;
+  const FriStandaloneLayout lay = fri_standalone_layout(sh);
+  const FriOffsets& fo = lay.fo;
+  const size_t proof_words = lay.proof_words, per_q = fo.query_stride;
   DevMem d_tr(sizeof(Transcript) / 8 + 1), d_chal(CH_WORDS), d_proof(proof_words), d_status(1), d_seed(n_seed + 1);
   hipStream_t st = 0;
   P25_HIP(hipMemcpy(w.coeffs[0].p, coeffs, 2 * n * 8, hipMemcpyHostToDevice));
@@ -889,15 +802,6 @@ void fri_prove_standalone(NttTables& tables, const u64* coeffs, const FriShape& 
 // parallel ACROSS proofs), then each proof's commit/quotient/FRI pipeline on one of K streams so that
 // the latency-bound stretches of one proof (transcript, Merkle-cap levels, FRI tail) overlap with the
 // throughput-bound kernels of the others.
-// Approximate device bytes of one proof context (see Ctx::Ctx): the LDE matrices dominate.
-size_t DeviceCircuit::ctx_bytes() const {
-  const size_t n = c_.degree(), B = (size_t)1 << (c_.degree_bits + c_.cfg.rate_bits);
-  const size_t W = c_.cfg.num_wires, NC = c_.cfg.num_challenges, NP = c_.num_partial_products;
-  const size_t nz = NC * (1 + NP), nq = NC * c_.cfg.max_quotient_degree_factor;
-  const size_t tw = merkle_tree_words(B, c_.cfg.cap_height);
-  return 8 * (3 * W * n + W * B + 2 * nz * n + nz * B + 3 * NC * B + nq * B + 3 * tw + 16 * n + 6 * B);
-}
-
 void DeviceCircuit::prove_batch_dev(const u64* d_inputs, size_t n_proofs, const u64* d_seeds, u64* d_proofs,
                                     size_t proof_stride, uint32_t* d_status, PhaseTimes* times, const u64* d_filler,
                                     size_t in_stride, size_t in_max_off) {
@@ -906,7 +810,7 @@ void DeviceCircuit::prove_batch_dev(const u64* d_inputs, size_t n_proofs, const 
   if (K > ctxs_.size()) {
     // New contexts must fit in what is actually FREE on the device (other circuits, the caller's tensors and
     // this circuit's tables are already allocated), after the witness-value array of this call and a 5%
-    // reserve -- matters for 2^19-row circuits (13 GB per context).
+    // reserve -- matters for 2^19-row circuits (8.9 GB per context; ctx_bytes is the working set's own sum).
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) {
       const size_t pass = n_proofs < 64 ? n_proofs : 64;
@@ -984,13 +888,10 @@ void DeviceCircuit::prove_batch(const u64* inputs, size_t n_proofs, const u64* s
   }
   prove_batch_dev(d_in.p, n_proofs, d_seeds.p, d_proofs.p, layout_.total, (uint32_t*)d_status.p, times, filler ? d_filler.p : nullptr);
   sync();
-  std::vector<uint32_t> hs(n_proofs);
-  P25_HIP(hipMemcpyAsync(hs.data(), d_status.p, n_proofs * 4, hipMemcpyDeviceToHost, stream_));
   for (size_t i = 0; i < n_proofs; i++)
     P25_HIP(hipMemcpyAsync(proofs_out + i * proof_stride, d_proofs.p + i * layout_.total, layout_.total * 8,
                            hipMemcpyDeviceToHost, stream_));
-  P25_HIP(hipStreamSynchronize(stream_));
-  for (size_t i = 0; i < n_proofs; i++) statuses[i] = (int32_t)hs[i];
+  statuses_to_host((const uint32_t*)d_status.p, n_proofs, statuses, stream_);
 }
 
 int32_t DeviceCircuit::witness(const u64* inputs, u64 seed, u64* wires_out) {

@@ -135,7 +135,7 @@ struct EvalJob {
   u64* out;
   uint32_t n_polys, point;
 };
-size_t eval_scratch_words(uint32_t n_points, size_t total_polys, uint32_t log_n);
+// d_scratch: [eval_scratch_words(n_points, polynomials of all jobs, log_n)] (prover_shape.h)
 void launch_eval_jobs(const EvalJob* jobs, uint32_t n_jobs, uint32_t log_n, const u64* d_point, const u64* scale,
                       uint32_t n_points /* <= 2 */, u64* d_scratch, hipStream_t st);
 

@@ -3,6 +3,7 @@
 // the four launches of kernels_verify.hip on the circuit's main stream; nothing of a proving context is touched.
 #include <string.h>
 #include "prover.h"
+#include "staging.h"
 #include "verify_kernels.h"
 
 namespace p25 {
@@ -11,12 +12,13 @@ namespace p25 {
 // a query round.  The caller adds the batch's pointers.  Refuses shapes the kernels do not hold.
 VerifyArgs make_verify_args(const Circuit& c, const ProofLayout& L) {
   if (L.total >= ((size_t)1 << 32)) throw std::invalid_argument("proof too long for the verifier's 32-bit offsets");
-  const std::vector<int>& ab = c.fri_reduction_arity_bits;
+  const ProverShape s = make_prover_shape(c, L);   // a DeviceCircuit's shape_; made here for a caller that has the circuit alone
+  const std::vector<int>& ab = s.arity_bits;
   if (ab.size() > 8) throw std::invalid_argument("too many FRI layers");
   for (int b : ab)
     if (b < 1 || b > (int)VERIFY_MAX_ARITY_BITS) throw std::invalid_argument("FRI arity bits outside 1..5");
   if (c.cfg.num_query_rounds < 1 || c.cfg.num_query_rounds > 64) throw std::invalid_argument("1..64 query rounds are supported");
-  if (c.cfg.num_challenges != 2 || c.gates.size() > 16) throw std::invalid_argument("unsupported circuit configuration");
+  if (s.NC != 2 || c.gates.size() > 16) throw std::invalid_argument("unsupported circuit configuration");
   VerifyArgs a;
   memset(&a, 0, sizeof(a));
   a.proof_words = (uint32_t)L.total;
@@ -38,28 +40,28 @@ VerifyArgs make_verify_args(const Circuit& c, const ProofLayout& L) {
   a.pow_witness = (uint32_t)L.pow_witness;
   a.public_inputs = (uint32_t)L.public_inputs;
   a.num_public_inputs = L.num_public_inputs;
-  a.cap_words = 4u << c.cfg.cap_height;
-  a.degree_bits = (uint32_t)c.degree_bits;
-  a.rate_bits = (uint32_t)c.cfg.rate_bits;
+  a.cap_words = (uint32_t)s.capw;
+  a.degree_bits = (uint32_t)s.degree_bits;
+  a.rate_bits = (uint32_t)s.rate_bits;
   a.pow_bits = (uint32_t)c.cfg.proof_of_work_bits;
   a.num_queries = (uint32_t)c.cfg.num_query_rounds;
   a.n_layers = (uint32_t)ab.size();
   a.num_selectors = (uint32_t)c.num_selectors;
   a.num_routed = (uint32_t)c.cfg.num_routed_wires;
-  a.num_partial_products = (uint32_t)c.num_partial_products;
+  a.num_partial_products = (uint32_t)s.NP;
   a.quotient_degree_factor = (uint32_t)c.cfg.max_quotient_degree_factor;
   a.n_gates = (uint32_t)c.gates.size();
   for (uint32_t i = 0; i < a.n_gates; i++) {
-    const int s = c.selector_index[i];
-    a.gates[i] = GateEntry{(uint32_t)c.gates[i], (uint32_t)s, (uint32_t)c.groups[s].first, (uint32_t)c.groups[s].second};
+    const int g = c.selector_index[i];
+    a.gates[i] = GateEntry{(uint32_t)c.gates[i], (uint32_t)g, (uint32_t)c.groups[g].first, (uint32_t)c.groups[g].second};
   }
   // the Merkle trees of a query round, in the order the flat proof stores them
-  const uint32_t lde_bits = a.degree_bits + a.rate_bits, cap_h = (uint32_t)c.cfg.cap_height;
+  const uint32_t lde_bits = a.degree_bits + a.rate_bits, cap_h = s.cap_height;
   const uint32_t caps[4] = {0, a.wires_cap, a.zs_cap, a.quotient_cap};
   uint32_t off = 0;
   for (int t = 0; t < 4; t++) {
     a.tree_off[t] = off;
-    a.tree_width[t] = L.oracle_width[t];
+    a.tree_width[t] = s.oracle_width[t];
     a.tree_depth[t] = lde_bits - cap_h;
     a.tree_shift[t] = 0;
     a.tree_cap[t] = caps[t];
@@ -133,10 +135,7 @@ void DeviceCircuit::verify_batch(const u64* digest4, const u64* cs_cap, const u6
   // the proof_stride - proof_words words behind a proof stay on the host: they are not read
   P25_HIP(hipMemcpy2DAsync(d_proofs.p, pw * 8, proofs, proof_stride * 8, pw * 8, n_proofs, hipMemcpyHostToDevice, stream_));
   verify_batch_dev(digest4, cs_cap, d_proofs.p, n_proofs, pw, (uint32_t*)d_status.p);
-  std::vector<uint32_t> hs(n_proofs);
-  P25_HIP(hipMemcpyAsync(hs.data(), d_status.p, n_proofs * 4, hipMemcpyDeviceToHost, stream_));
-  P25_HIP(hipStreamSynchronize(stream_));
-  for (size_t i = 0; i < n_proofs; i++) statuses[i] = (int32_t)hs[i];
+  statuses_to_host((const uint32_t*)d_status.p, n_proofs, statuses, stream_);
 }
 
 }  // namespace p25

@@ -4,6 +4,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdlib.h>
+#include <map>
 #include <set>
 #include <string>
 
@@ -18,6 +19,8 @@ struct FakeHip {
   std::string calls;                      // M malloc, F free, E / e event create / destroy, S / s stream create / destroy
   size_t last_malloc_bytes = 0, creations = 0, fail_at = 0, bad_releases = 0;
   unsigned last_flags = 0;
+  size_t bytes_requested = 0, bytes_live = 0;   // running totals over the hipMallocs that succeeded / that are not freed yet
+  std::map<void*, size_t> bytes_of;             // ... per live block
   void arm(size_t nth) {   // the nth creation from now fails (0: none does)
     creations = 0;
     fail_at = nth;
@@ -44,9 +47,17 @@ inline hipError_t hipMalloc(T** p, size_t bytes) {
   g_fake_hip.last_malloc_bytes = bytes;
   *p = (T*)malloc(bytes ? bytes : 1);
   g_fake_hip.mem.insert(*p);
+  g_fake_hip.bytes_requested += bytes;
+  g_fake_hip.bytes_live += bytes;
+  g_fake_hip.bytes_of[*p] = bytes;
   return hipSuccess;
 }
 inline hipError_t hipFree(void* p) {
+  auto it = g_fake_hip.bytes_of.find(p);
+  if (it != g_fake_hip.bytes_of.end()) {
+    g_fake_hip.bytes_live -= it->second;
+    g_fake_hip.bytes_of.erase(it);
+  }
   g_fake_hip.release(g_fake_hip.mem, p, 'F');
   return hipSuccess;
 }

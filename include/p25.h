@@ -335,6 +335,26 @@ p25_status p25_p3_prove_air_pc(const p25_air* air, const uint64_t* trace, const 
  * P25_ERR_WITNESS_CONFLICT, as the failing `connect` panics upstream. */
 p25_status p25_circuit_build_gadget(int32_t kind, int32_t param, p25_circuit** out);
 /* ------------------------------------------------------------------------------------------
+ * Circuit config: the FRI rate, query count and grinding a circuit is built under.
+ * ------------------------------------------------------------------------------------------
+ * The builders above use upstream's CircuitConfig::standard_recursion_config(): rate_bits 3, 28 query rounds, 16
+ * proof-of-work bits.  The _cfg builders and p25_circuit_build_shrink take these three numbers from the caller; wires
+ * (135 / 80 routed), constants (2), cap_height 4, max_quotient_degree_factor 8 and the FRI reduction strategy
+ * ConstantArityBits(4, 5) stay the standard config's (the arity list follows the rate, as upstream's does).
+ *   cfg = NULL, or {3, 28, 16, 0}: the standard config -- the _cfg builder's blob is the plain builder's, byte for byte.
+ *   rate_bits 3..8, num_query_rounds 1..64, proof_of_work_bits 0..32, reserved 0; anything else is P25_ERR_INVALID_ARG
+ *   and p25_last_error() names the field.
+ * Conjectured security of the FRI protocol, in bits: rate_bits * num_query_rounds + proof_of_work_bits (100 for the
+ * standard config; upstream's high-rate recursion configs keep it: 7 * 12 + 16, 8 * 10 + 16 ...).  It is the CALLER'S
+ * choice: the library builds and proves whatever is in range and does not enforce a security level.
+ * A higher rate costs the prover a 2^rate_bits-fold LDE and buys a smaller proof and a smaller next recursive verifier
+ * circuit.  The device prover takes rate_bits up to 8 while degree_bits + rate_bits <= 24. */
+typedef struct { int32_t rate_bits, num_query_rounds, proof_of_work_bits, reserved; } p25_circuit_config;
+/* The three numbers of any circuit (built here or imported).  Host only. */
+p25_status p25_circuit_config_of(const p25_circuit* c, p25_circuit_config* out);
+/* p25_circuit_build_gadget under `cfg`.  Host only. */
+p25_status p25_circuit_build_gadget_cfg(int32_t kind, int32_t param, const p25_circuit_config* cfg, p25_circuit** out);
+/* ------------------------------------------------------------------------------------------
  * Recursion: verifying this library's proofs inside another plonky2 circuit.
  * ------------------------------------------------------------------------------------------ */
 /* A circuit that verifies `n_proofs` (1..16) proofs of `inner` -- upstream `builder.verify_proof::<C>(proof, vd, cd)`
@@ -366,11 +386,22 @@ p25_status p25_circuit_build_gate_eval(int32_t kind, p25_circuit** out);
  * 14 need 2^17), which is what plonky25_amd.aggregate.widest_arity finds and bench.py uses. */
 p25_status p25_circuit_build_aggregator(p25_circuit* inner, const uint64_t* digest4, const uint64_t* cs_cap,
                                         int32_t n_proofs, p25_circuit** out);
+/* The shrink step: a circuit built under `cfg` (p25_circuit_config above; NULL = the standard config) that verifies ONE
+ * proof of `inner`, exactly as p25_circuit_build_recursive_verifier(inner, .., 1, ..) does, and registers the inner
+ * proof's public inputs as its own -- the same words in the same order (upstream
+ * `builder.register_public_inputs(&proof.public_inputs)`); none if `inner` has none.  An aggregate's commitment
+ * therefore survives any number of shrink steps unchanged.  A short chain under high-rate configs -- upstream's
+ * size-optimised recursion goes (7, 12, 16) then (8, 10, 16) -- turns the last proof of an aggregation into one with
+ * fewer queries: smaller to publish, and cheaper for the next verifier.  digest4 / cs_cap as for the recursive verifier. */
+p25_status p25_circuit_build_shrink(p25_circuit* inner, const uint64_t* digest4, const uint64_t* cs_cap,
+                                    const p25_circuit_config* cfg, p25_circuit** out);
 
 /* Circuit blob (format: plonky2.5_amd/csrc/circuit_io.h): persist a built circuit / hand it to
  * another process.  export: pass buf = NULL to query the size. */
 p25_status p25_circuit_export(const p25_circuit* c, uint8_t* buf, size_t cap, size_t* len_out);
 p25_status p25_circuit_import(const uint8_t* blob, size_t len, p25_circuit** out);
+/* Import (and p25_circuit_from_bytes) accepts rate_bits 0..8 with max_quotient_degree_factor == 2^min(rate_bits, 3) and
+ * refuses, by name, a circuit with degree_bits + rate_bits > 24 (32-bit point indices and the tree sizes of the prover). */
 /* Upstream's own binary form of a built circuit: `CircuitData::to_bytes(&gate_serializer, &generator_serializer)` /
  * `CircuitData::from_bytes` (plonky2 util/serialization, restated -- the crate is absent, unpinned like the proof
  * formats; the reference's gate / generator payloads are its own `serialize` bodies: poseidon2_gate.rs:399-405,

@@ -14,7 +14,8 @@ import time
 
 import numpy as np
 
-__all__ = ["fold", "fold_roots", "fold_sharded", "release_fold", "DeviceTree", "circuit_throughput", "expected_commitment", "leaf_identifier_words", "level_plan", "group_bounds", "widest_arity"]
+__all__ = ["fold", "fold_roots", "fold_sharded", "release_fold", "DeviceTree", "circuit_throughput", "expected_commitment", "leaf_identifier_words", "level_plan", "group_bounds", "widest_arity", "shrink",
+           "SHRINK_CONFIGS"]
 
 MAX_MARKS = 16                    # include/p25.h P25_MAX_MARKS
 TREE_MARK_SLOTS = MAX_MARKS - 2   # DeviceTree uses slots 0 .. 13 (levels + 2 of them): 256 leaves two at a time (8 levels) fit
@@ -125,6 +126,34 @@ def fold(circuit, leaves, arity=8, warm=True, in_flight=16, streams=None, circui
                        "ms_per_proof": round(dt / len(level) * 1e3, 3), "circuit_build_s": round(bs, 2)})
         circ = nxt
     return {"root": level[0], "top": circ, "owned": owned, "levels": levels, "tree_s": tree_s, "build_s": build_s}
+
+
+# upstream's size-optimised recursion: two single-proof steps, 7 * 12 + 16 and 8 * 10 + 16 conjectured bits
+SHRINK_CONFIGS = ((7, 12, 16), (8, 10, 16))
+
+
+def shrink(circuit, proof, configs=SHRINK_CONFIGS):
+    """The chain of shrink steps over one `proof` of `circuit`: step i is `build_shrink(configs[i])` over the circuit of
+    step i - 1 and proves the proof of step i - 1, so the last proof carries `proof`'s public inputs unchanged under the
+    last config -- fewer queries, fewer words.  configs: CircuitConfig or (rate_bits, num_query_rounds,
+    proof_of_work_bits) each.  Returns (circuits, proofs), one of each per step; the caller closes the circuits."""
+    circuits, proofs = [], []
+    circ, cur = circuit, np.ascontiguousarray(proof, dtype=np.uint64)
+    try:
+        for cfg in configs:
+            nxt = circ.build_shrink(cfg)
+            circuits.append(nxt)
+            out, st = nxt.prove(cur[None, :], seeds=[0])
+            if int(st[0]) != 0:
+                raise RuntimeError(f"shrink step {len(circuits)}: status {int(st[0])}")
+            cur = out[0].copy()
+            proofs.append(cur)
+            circ = nxt
+    except Exception:
+        for c in circuits:
+            c.close()
+        raise
+    return circuits, proofs
 
 
 def fold_roots(top, roots, warm=True):

@@ -6,7 +6,7 @@ import numpy as np
 
 __all__ = ["P25Error", "lib", "lib_path", "device_init", "shader_clock_hz", "poseidon_permute", "poseidon2_permute",
            "merkle_commit", "merkle_tree_words", "lde_commit", "EXPORTED_SYMBOLS", "P",
-           "P3Config", "Circuit", "p3_proof_from_json", "Timings", "p3_prove_fibonacci", "p3_inputs_to_json",
+           "P3Config", "Circuit", "CircuitConfig", "p3_proof_from_json", "Timings", "p3_prove_fibonacci", "p3_inputs_to_json",
            "Air", "p3_prove_air", "P3Prover", "transcript", "fri_prove", "eval_polys", "RuntimeInfo", "runtime_info", "Comm",
            "comm_unique_id", "WARN_HW_QUEUES_LATE", "REJECT_VANISHING", "REJECT_POW", "REJECT_MALFORMED",
            "REJECT_INITIAL_MERKLE", "REJECT_FRI_EVAL", "REJECT_FRI_MERKLE", "REJECT_FINAL_POLY"]
@@ -144,6 +144,30 @@ class CircuitInfo(C.Structure):
                                           "num_public_inputs")]
 
 
+class CircuitConfig(C.Structure):
+    """p25_circuit_config: the FRI rate, query count and grinding a circuit is built under; everything else is upstream's
+    standard recursion config.  Conjectured security: rate_bits * num_query_rounds + proof_of_work_bits (the caller's choice)."""
+    _fields_ = [(n, C.c_int32) for n in ("rate_bits", "num_query_rounds", "proof_of_work_bits", "reserved")]
+
+    def __init__(self, rate_bits=3, num_query_rounds=28, proof_of_work_bits=16, reserved=0):
+        super().__init__(rate_bits, num_query_rounds, proof_of_work_bits, reserved)
+
+    def as_tuple(self):
+        return (int(self.rate_bits), int(self.num_query_rounds), int(self.proof_of_work_bits))
+
+    @property
+    def conjectured_security_bits(self):
+        return int(self.rate_bits) * int(self.num_query_rounds) + int(self.proof_of_work_bits)
+
+
+def _config_arg(config):
+    """None (the standard config), a CircuitConfig, or a (rate_bits, num_query_rounds, proof_of_work_bits) tuple -> pointer or None."""
+    if config is None:
+        return None, None
+    cc = config if isinstance(config, CircuitConfig) else CircuitConfig(*config)
+    return cc, C.byref(cc)
+
+
 class Timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("witness_ms", "wires_commit_ms", "partial_products_ms", "zs_commit_ms",
                                          "quotient_ms", "quotient_commit_ms", "openings_ms", "fri_ms", "total_ms")]
@@ -188,6 +212,9 @@ EXPORTED_SYMBOLS = {
     "p25_circuit_build_p3_verifier": (i32, [C.POINTER(P3Config), i32, C.POINTER(vp)]),
     "p25_circuit_build_gadget": (i32, [i32, i32, C.POINTER(vp)]),
     "p25_circuit_build_gate_eval": (i32, [i32, C.POINTER(vp)]),
+    "p25_circuit_config_of": (i32, [vp, C.POINTER(CircuitConfig)]),
+    "p25_circuit_build_gadget_cfg": (i32, [i32, i32, C.POINTER(CircuitConfig), C.POINTER(vp)]),
+    "p25_circuit_build_shrink": (i32, [vp, vp, vp, C.POINTER(CircuitConfig), C.POINTER(vp)]),
     "p25_circuit_build_recursive_verifier": (i32, [vp, vp, vp, i32, C.POINTER(vp)]),
     "p25_circuit_export": (i32, [vp, vp, sz, C.POINTER(sz)]),
     "p25_circuit_import": (i32, [vp, sz, C.POINTER(vp)]),
@@ -647,10 +674,14 @@ class Circuit:
         return _new_circuit(lib().p25_circuit_build_p3_verifier_air, C.byref(cfg), C.byref(ac))
 
     @staticmethod
-    def build_gadget(kind, param=0):
+    def build_gadget(kind, param=0, config=None):
         """kind: 0 and, 1 xor, 2 lsh, 3 rsh, 4 reverse_bits_len, 5 compress, 6 exp, 7 hash_iter_slices,
-        8 two connected inputs (include/p25.h)."""
-        return _new_circuit(lib().p25_circuit_build_gadget, kind, param)
+        8 two connected inputs (include/p25.h).  config: a CircuitConfig or (rate_bits, num_query_rounds,
+        proof_of_work_bits); None = the standard recursion config (3, 28, 16)."""
+        if config is None:
+            return _new_circuit(lib().p25_circuit_build_gadget, kind, param)
+        _cc, ref = _config_arg(config)
+        return _new_circuit(lib().p25_circuit_build_gadget_cfg, kind, param, ref)
 
     @staticmethod
     def build_gate_eval(kind):
@@ -665,6 +696,20 @@ class Circuit:
     def build_aggregator(self, n_proofs=2, digest=None, cs_cap=None):
         """build_recursive_verifier whose circuit registers 4 public inputs committing to the proofs it verifies."""
         return self._build_recursive(lib().p25_circuit_build_aggregator, n_proofs, digest, cs_cap)
+
+    def build_shrink(self, config=None, digest=None, cs_cap=None):
+        """The shrink step: a circuit under `config` (as for build_gadget) that verifies ONE proof of this circuit and
+        registers that proof's public inputs as its own, unchanged.  digest / cs_cap as for build_recursive_verifier."""
+        d, cap = (_u64(a) if a is not None else None for a in (digest, cs_cap))
+        _cc, ref = _config_arg(config)
+        return _new_circuit(lib().p25_circuit_build_shrink, self._h, _ptr(d), _ptr(cap), ref)
+
+    @property
+    def config(self):
+        """The circuit's CircuitConfig (rate_bits, num_query_rounds, proof_of_work_bits)."""
+        cc = CircuitConfig()
+        _check(lib().p25_circuit_config_of(self._h, C.byref(cc)))
+        return cc
 
     def _build_recursive(self, fn, n_proofs, digest, cs_cap):
         d, cap = (_u64(a) if a is not None else None for a in (digest, cs_cap))

@@ -515,6 +515,19 @@ std::array<Ext, 12> CircuitBuilder::poseidon_mds_layer(const std::array<Ext, 12>
 }
 
 // ---------------------------------------------------------------- build
+CircuitConfig circuit_config_with(int rate_bits, int num_query_rounds, int proof_of_work_bits, int reserved) {
+  if (rate_bits < 3 || rate_bits > MAX_RATE_BITS) throw std::invalid_argument("circuit config: rate_bits must be in 3..8");
+  if (num_query_rounds < 1 || num_query_rounds > 64) throw std::invalid_argument("circuit config: num_query_rounds must be in 1..64");
+  if (proof_of_work_bits < 0 || proof_of_work_bits > 32)
+    throw std::invalid_argument("circuit config: proof_of_work_bits must be in 0..32");
+  if (reserved != 0) throw std::invalid_argument("circuit config: reserved must be 0");
+  CircuitConfig cfg;
+  cfg.rate_bits = rate_bits;
+  cfg.num_query_rounds = num_query_rounds;
+  cfg.proof_of_work_bits = proof_of_work_bits;
+  return cfg;
+}
+
 std::vector<int> fri_reduction_arity_bits(const CircuitConfig& cfg, int degree_bits) {
   std::vector<int> r;
   int db = degree_bits;

@@ -49,6 +49,14 @@ struct CircuitConfig {
   int fri_final_poly_bits = 5;
 };
 
+// FRI rates the library proves: rate_bits up to 8 over an LDE of at most 2^24 points; the quotient has degree below
+// 8n whatever the rate, so it lives on the coset of 2^min(rate_bits, 3) * n points
+constexpr int MAX_RATE_BITS = 8, MAX_LDE_BITS = 24;
+inline int quotient_rate_bits(int rate_bits) { return rate_bits < 3 ? rate_bits : 3; }
+// The standard recursion config with another FRI rate / query count / grinding (p25_circuit_config, include/p25.h):
+// rate_bits 3..8, num_query_rounds 1..64, proof_of_work_bits 0..32, reserved 0; throws std::invalid_argument naming the field.
+CircuitConfig circuit_config_with(int rate_bits, int num_query_rounds, int proof_of_work_bits, int reserved);
+
 enum GateKind : uint8_t {
   G_NOOP = 0,
   G_CONSTANT,

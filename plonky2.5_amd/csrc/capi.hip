@@ -367,8 +367,13 @@ p25_status build_verifier(const p25_p3_config* cfg, const Air& air, p25_circuit*
     return cb.build();
   });
 }
+// NULL: the standard config
+CircuitConfig config_from_c(const p25_circuit_config* cfg) {
+  return cfg ? circuit_config_with(cfg->rate_bits, cfg->num_query_rounds, cfg->proof_of_work_bits, cfg->reserved) : CircuitConfig();
+}
+// shrink_cfg set: the shrink step under that config (n_proofs and expose_commitment unused)
 p25_status build_recursive(p25_circuit* inner, const uint64_t* digest4, const uint64_t* cs_cap, int32_t n_proofs,
-                           bool expose_commitment, p25_circuit** out) {
+                           bool expose_commitment, p25_circuit** out, const CircuitConfig* shrink_cfg = nullptr) {
   auto body = [&]() -> p25_status {
     if (!inner || !out) throw std::invalid_argument("null argument");
     if ((digest4 == nullptr) != (cs_cap == nullptr)) throw std::invalid_argument("pass both digest4 and cs_cap, or neither");
@@ -388,7 +393,10 @@ p25_status build_recursive(p25_circuit* inner, const uint64_t* digest4, const ui
       memcpy(dg, d.digest(), 32);
       cap = d.cs_cap();
     }
-    return new_circuit(out, [&] { return build_recursive_verifier(inner->c(), dg, cap, n_proofs, expose_commitment); });
+    return new_circuit(out, [&] {
+      return shrink_cfg ? build_shrink_circuit(inner->c(), dg, cap, *shrink_cfg)
+                        : build_recursive_verifier(inner->c(), dg, cap, n_proofs, expose_commitment);
+    });
   };
   return digest4 ? host_guarded(body) : guarded(body);
 }
@@ -400,9 +408,14 @@ void fill_timings(p25_timings* t, const PhaseTimes& pt) {
   t->openings_ms = pt.openings; t->fri_ms = pt.fri; t->total_ms = pt.total;
 }
 
+// rates of the LDE entry points: up to 3 at any size they take, up to MAX_RATE_BITS while the LDE stays within 2^MAX_LDE_BITS points
+bool lde_rate_ok(unsigned log_n, unsigned rate_bits) {
+  return rate_bits <= 3 || (rate_bits <= (unsigned)MAX_RATE_BITS && log_n + rate_bits <= (unsigned)MAX_LDE_BITS);
+}
 bool fri_shape_from_c(unsigned log_n, unsigned rate_bits, unsigned cap_height, const int32_t* arity_bits, size_t n_layers,
                       unsigned pow_bits, unsigned num_queries, FriShape& sh) {
-  if (log_n < 1 || log_n > 22 || rate_bits > 3 || cap_height > 16 || n_layers > 8 || (n_layers && !arity_bits) ||
+  if (log_n < 1 || log_n > 22 || rate_bits > (unsigned)MAX_RATE_BITS || (rate_bits > 3 && log_n + rate_bits > (unsigned)MAX_LDE_BITS) ||
+      cap_height > 16 || n_layers > 8 || (n_layers && !arity_bits) ||
       num_queries < 1 || num_queries > 64 || pow_bits > 32)
     return false;
   sh.log_n = (int)log_n;
@@ -526,7 +539,7 @@ p25_status p25_lde_commit(const uint64_t* polys, unsigned log_n, size_t n_polys,
                           unsigned rate_bits, unsigned cap_height, uint64_t* coeffs_out,
                           uint64_t* lde_out, uint64_t* cap_out) {
   return guarded([&]() -> p25_status {
-    if (!polys || !n_polys || log_n > 20 || rate_bits > 3 || log_n + rate_bits < cap_height)
+    if (!polys || !n_polys || log_n > 20 || !lde_rate_ok(log_n, rate_bits) || log_n + rate_bits < cap_height)
       throw std::invalid_argument("p25_lde_commit: bad shape");
     const size_t n = (size_t)1 << log_n, big = n << rate_bits;
     // refused, not reduced: with from_coeffs the input words ARE coeffs_out, and the commitment is of what was handed in
@@ -570,9 +583,9 @@ p25_status p25_lde_commit_dev(const uint64_t* d_polys, unsigned log_n, size_t n_
   return guarded([&]() -> p25_status {
     // as the host form: a cap above the leaves has no tree (p25_merkle_tree_words answers 0 words for it), yet the leaf
     // kernel would still write 4 << (log_n + rate_bits) words into d_tree.  Refused whether or not d_tree is given.
-    if (log_n <= 20 && rate_bits <= 3 && cap_height > log_n + rate_bits)
+    if (log_n <= 20 && lde_rate_ok(log_n, rate_bits) && cap_height > log_n + rate_bits)
       throw std::invalid_argument("p25_lde_commit_dev: cap_height above log_n + rate_bits");
-    if (!d_polys || !n_polys || log_n > 20 || rate_bits > 3 || !d_lde ||
+    if (!d_polys || !n_polys || log_n > 20 || !lde_rate_ok(log_n, rate_bits) || !d_lde ||
         (!from_coeffs && (!d_coeffs || !d_tmp)))
       throw std::invalid_argument("p25_lde_commit_dev: bad shape");
     std::lock_guard<std::mutex> lk(g_primitives_mutex);
@@ -848,11 +861,33 @@ p25_status p25_circuit_build_gadget(int32_t kind, int32_t param, p25_circuit** o
     return new_circuit(out, [&] { return build_gadget_circuit(kind, param); });
   });
 }
+p25_status p25_circuit_build_gadget_cfg(int32_t kind, int32_t param, const p25_circuit_config* cfg, p25_circuit** out) {
+  return host_guarded([&]() -> p25_status {
+    if (!out) throw std::invalid_argument("null argument");
+    const CircuitConfig cc = config_from_c(cfg);
+    return new_circuit(out, [&] { return build_gadget_circuit(kind, param, cc); });
+  });
+}
+p25_status p25_circuit_config_of(const p25_circuit* c, p25_circuit_config* out) {
+  return with_circuit(c, out, [&](const Circuit& k) {
+    *out = p25_circuit_config{k.cfg.rate_bits, k.cfg.num_query_rounds, k.cfg.proof_of_work_bits, 0};
+    return P25_OK;
+  });
+}
 
 // ---- recursion; circuit data: export / import, info, digest ---------------------------------------------------------
 p25_status p25_circuit_build_recursive_verifier(p25_circuit* inner, const uint64_t* digest4, const uint64_t* cs_cap,
                                                 int32_t n_proofs, p25_circuit** out) {
   return build_recursive(inner, digest4, cs_cap, n_proofs, false, out);
+}
+p25_status p25_circuit_build_shrink(p25_circuit* inner, const uint64_t* digest4, const uint64_t* cs_cap,
+                                    const p25_circuit_config* cfg, p25_circuit** out) {
+  CircuitConfig cc;
+  const p25_status s = host_guarded([&]() -> p25_status {
+    cc = config_from_c(cfg);
+    return P25_OK;
+  });
+  return s != P25_OK ? s : build_recursive(inner, digest4, cs_cap, 1, false, out, &cc);
 }
 p25_status p25_circuit_build_gate_eval(int32_t kind, p25_circuit** out) {
   return host_guarded([&]() -> p25_status {

@@ -190,7 +190,7 @@ void write_fri_config(W& w, const Circuit& c) {
   w.usize(c.cfg.fri_final_poly_bits);
 }
 void read_fri_config(R& r, Circuit& c) {
-  c.cfg.rate_bits = (int)r.usize_max(3, "rate_bits");
+  c.cfg.rate_bits = (int)r.usize_max(MAX_RATE_BITS, "rate_bits");
   c.cfg.cap_height = (int)r.usize_max(16, "cap_height");
   c.cfg.num_query_rounds = (int)r.usize_max(64, "num_query_rounds");
   c.cfg.proof_of_work_bits = (int)r.u32();

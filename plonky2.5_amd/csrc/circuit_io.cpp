@@ -96,6 +96,15 @@ std::vector<uint8_t> circuit_to_blob(const Circuit& c) {
   return std::move(w.b);
 }
 
+void check_rate(int degree_bits, int rate_bits, int max_quotient_degree_factor, const char* prefix) {
+  auto bad = [&](const std::string& what) { throw std::invalid_argument(std::string(prefix) + what); };
+  if (rate_bits < 0 || rate_bits > MAX_RATE_BITS) bad("rate_bits must be in 0.." + std::to_string(MAX_RATE_BITS));
+  if (max_quotient_degree_factor != (1 << quotient_rate_bits(rate_bits)))
+    bad("max_quotient_degree_factor must be 2^min(rate_bits, 3)");
+  if (degree_bits + rate_bits > MAX_LDE_BITS)
+    bad("degree_bits + rate_bits must not exceed " + std::to_string(MAX_LDE_BITS));
+}
+
 Circuit circuit_from_blob(const uint8_t* data, size_t len) {
   Reader r{data, len};
   if (r.u64r() != MAGIC) throw std::invalid_argument("not a circuit blob");
@@ -122,8 +131,7 @@ Circuit circuit_from_blob(const uint8_t* data, size_t len) {
       c.cfg.num_routed_wires > c.cfg.num_wires || c.cfg.num_routed_wires > MAX_ROUTED)
     bad("bad wire counts");
   if (c.cfg.num_challenges != 2) bad("num_challenges must be 2");
-  if (c.cfg.rate_bits < 0 || c.cfg.rate_bits > 3 || c.cfg.max_quotient_degree_factor != (1 << c.cfg.rate_bits))
-    bad("rate_bits must be in 0..3 with max_quotient_degree_factor = 2^rate_bits");
+  check_rate(c.degree_bits, c.cfg.rate_bits, c.cfg.max_quotient_degree_factor, "circuit blob: ");
   if (c.cfg.cap_height < 0 || c.cfg.cap_height > 16 || c.cfg.cap_height > c.degree_bits + c.cfg.rate_bits)
     bad("cap_height exceeds the LDE size");
   if (c.cfg.num_query_rounds < 1 || c.cfg.num_query_rounds > 64) bad("num_query_rounds must be in 1..64");

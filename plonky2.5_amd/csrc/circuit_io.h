@@ -12,4 +12,8 @@
 namespace p25 {
 std::vector<uint8_t> circuit_to_blob(const Circuit& c);
 Circuit circuit_from_blob(const uint8_t* data, size_t len);
+// The FRI rates a circuit may enter the library with: rate_bits in 0..MAX_RATE_BITS, a quotient of degree factor
+// 2^min(rate_bits, 3) (above rate 3 the quotient stays below 8n and is evaluated on a sub-coset of the LDE), and an LDE of
+// at most 2^MAX_LDE_BITS points (32-bit point indices, tree sizes).  Throws std::invalid_argument(prefix + what).
+void check_rate(int degree_bits, int rate_bits, int max_quotient_degree_factor, const char* prefix);
 }

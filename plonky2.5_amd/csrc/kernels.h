@@ -49,7 +49,7 @@ struct NttPass {
   const u64* in;
   u64* out;
   size_t in_poly_stride, out_poly_stride;
-  size_t coset_out_off[8];
+  size_t coset_out_off[8];   // an LDE pass over up to 8 cosets: where coset c's output starts (bitrev(c, log_cosets) * N)
   int log_r, log_nt, log_t;
   int in_kind, in_br_t, in_br_i;
   int out_kind, out_br_t, out_br_i;
@@ -65,6 +65,7 @@ struct NttPass {
   int lazy_out;          // the output is read by another pass of k_ntt_tile only: store any u64 congruent to the value
                          // (the kernel computes in lazy arithmetic, gl_lazy.h); 0 = canonical, as everything else expects
   uint32_t n_tiles, n_cosets, log_g, full_table;  // set by launch_ntt_pass (log_g: block decode of k_ntt_tile)
+  int log_cosets;        // an LDE pass over 2^log_cosets cosets; above 8 of them the kernel computes coset_out_off itself
 };
 void launch_ntt_pass(const NttPass& p, int n_polys, int n_cosets, hipStream_t st);
 // Shader clock (Hz) under a full-chip Poseidon load, from in-kernel cycle and wall-clock counters (kernels_hash.hip).

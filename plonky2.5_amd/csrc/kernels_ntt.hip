@@ -13,9 +13,9 @@
 // The DIF network leaves its result in bit-reversed LDS order, which is exactly what the prover
 // wants: the LDE is stored at bit-reversed index (Merkle-leaf order) with NO separate
 // transpose / bit-reversal pass -- pass 1 scatters rows to rev(j2) and pass 2 then runs in place.
-// The rate-8 LDE is computed as 8 coset transforms of length n (shift*w_8n^c, c < 8) rather than
-// one zero-padded length-8n transform: the same values, 3 fewer butterfly stages, and coset c
-// lands in the contiguous leaf block rev3(c).
+// The rate-2^rb LDE (rb <= 8) is computed as 2^rb coset transforms of length n (shift*w_{2^rb n}^c) rather than
+// one zero-padded length-2^rb n transform: the same values, rb fewer butterfly stages, and coset c
+// lands in the contiguous leaf block rev_rb(c).
 //
 // Addressing kinds (element (t, i): sub-transform t of the launch, element i of it; NT = number
 // of sub-transforms per polynomial, R = their length):
@@ -145,8 +145,14 @@ __device__ __forceinline__ void st_w(u64* base, u32 woff, u64 v) {
 // reason: with both kinds evaluated and selected per element, and every position re-derived from the element number,
 // index work was 40 % of the kernel's instructions (profiles/r11_ntt_addressing.txt).  LR, LT >= 0: the tile shape
 // (log_r, log_t) as constants -- the 2^16-point shapes, R = 256, T = 16 in both passes -- or -1: read from the pass.
-template <bool INV, int NTH, int PRE, int IN, int OUT, int MUL, bool LAZY, int LR, int LT>
+// PREM = PRE, or PRE | PRE_MANY: an LDE pass over more than 8 cosets (rates above 3), which computes a coset's output block
+// where the others read it from the pass's table -- instantiations of their own, so that the ones the rates up to 3 run
+// are, instruction for instruction, what they were.
+constexpr int PRE_MANY = 4;
+template <bool INV, int NTH, int PREM, int IN, int OUT, int MUL, bool LAZY, int LR, int LT>
 __global__ __launch_bounds__(NTH) void k_ntt_tile(NttPass a) {
+  constexpr int PRE = PREM & 3;
+  constexpr bool MANY = (PREM & PRE_MANY) != 0;
   P25_WAVE_PRIO(P25_PRIO_BULK);
   extern __shared__ u64 lds[];
   const int log_r = LR >= 0 ? LR : a.log_r, log_t = LT >= 0 ? LT : a.log_t;
@@ -168,7 +174,8 @@ __global__ __launch_bounds__(NTH) void k_ntt_tile(NttPass a) {
   const nttix::Tile tile{log_r, log_t, a.log_nt, blk.tile << log_t};
   // wave-uniform bases; a lane's part of every address is a 32-bit offset inside the polynomial (ntt_index.h)
   const u64* in = a.in + (size_t)blk.poly * a.in_poly_stride;
-  u64* out = a.out + (size_t)blk.poly * a.out_poly_stride + a.coset_out_off[blk.coset];
+  u64* out = a.out + (size_t)blk.poly * a.out_poly_stride +
+             (MANY ? (size_t)nttix::coset_block(blk.coset, a.log_cosets) << (log_r + a.log_nt) : a.coset_out_off[blk.coset]);
   // coset pre-scale: one table entry per input coefficient (shift_c^k at the coefficient's address k) ...
   const u64* pre = PRE == 1 ? a.pre + ((size_t)blk.coset << (log_r + a.log_nt)) : nullptr;
   // ... or its two factors shift_c^t * (shift_c^NT)^i when N is too large for the table to live in L2 (2^19-row circuits:
@@ -331,6 +338,22 @@ void launch_ntt_pass(const NttPass& p, int n_polys, int n_cosets, hipStream_t st
     }                                                                                                                 \
     return;                                                                                                           \
   }
+  // the LDE over more than 8 cosets: generic tile shapes only
+#define P25_NTT_FORM_MANY(PRE, IN, OUT, MUL, LAZY, WIDE)                                                              \
+  if (n_cosets > 8 && !both && !q.inverse && pre_mode == PRE && in == IN && out == OUT && mul == MUL &&               \
+      (bool)q.lazy_out == LAZY && (WIDE || !wide)) {                                                                  \
+    if (wide) {                                                                                                       \
+      if constexpr (WIDE) launch(k_ntt_tile<false, 512, PRE | PRE_MANY, IN, OUT, MUL, LAZY, -1, -1>, 512);            \
+    } else {                                                                                                          \
+      launch(k_ntt_tile<false, 256, PRE | PRE_MANY, IN, OUT, MUL, LAZY, -1, -1>, 256);                                \
+    }                                                                                                                 \
+    return;                                                                                                           \
+  }
+  P25_NTT_FORM_MANY(1, IN_T, OUT_T_BR, MUL_TWIDDLE, true, true)             // LDE pass 1
+  P25_NTT_FORM_MANY(2, IN_T, OUT_T_BR, MUL_TWIDDLE, true, true)             //   with the factored pre-scale
+  P25_NTT_FORM_MANY(1, IN_I, OUT_I_BR, MUL_NONE, false, false)              // single-pass LDE
+#undef P25_NTT_FORM_MANY
+  if (n_cosets > 8) throw std::runtime_error("NTT pass over more than 8 cosets of a form the library has no kernel for");
   P25_NTT_FORM(true, 0, IN_T, OUT_T, MUL_TWIDDLE, true, true, true)         // inverse pass 1
   P25_NTT_FORM(true, 0, IN_I_BR, OUT_T, MUL_TWIDDLE, true, true, false)     // inverse pass 1 of the quotient (bit-reversed input)
   P25_NTT_FORM(true, 0, IN_I, OUT_T, MUL_POST, false, true, true)           // inverse pass 2
@@ -476,22 +499,29 @@ void ntt_inverse(NttTables& tb, const u64* d_in, size_t in_stride, bool in_bitre
   launch_ntt_pass(q, n_polys, 1, st);
 }
 
+// a two-pass LDE whose unfactored pre-scale table (2^rate_bits cosets of n words) would exceed 2^NTT_PRE_TABLE_LOG words --
+// what the table is at the hot shape, n = 2^16 and 8 cosets -- takes the two factor tables, like one above 2^NTT_FACTOR_LOG points
+constexpr int NTT_PRE_TABLE_LOG = 19;
+
 void ntt_lde_bitrev(NttTables& tb, const u64* d_coeffs, size_t coeff_stride, u64* d_lde,
                     size_t lde_stride, int log_n, int rate_bits, int n_polys, u64 shift,
                     hipStream_t st) {
   int l1, l2;
   split(log_n, l1, l2);
+  if (rate_bits < 0 || rate_bits > 8 || log_n + rate_bits > 25) throw std::runtime_error("LDE rate or size not supported");
   const int nc = 1 << rate_bits;
-  if (nc > 8) throw std::runtime_error("rate_bits > 3 not supported");
   const size_t n = (size_t)1 << log_n;
   const u64* pw = tb.pow_table(log_n, false);
   const u64 w_big = gl::root_of_unity(log_n + rate_bits);
+  // (Rates above 3 multiply the unfactored table described next by up to 32 -- 128 MB at n = 2^16, rate_bits 8 -- so a
+  // two-pass LDE whose table would exceed the hot shape's 2^19 words is factored too, whatever n is.  Where that switch
+  // belongs has not been measured.)
   // per-coset pre-scale table: coefficient k gets shift_c^k, shift_c = shift * w_{8n}^c  (n words per coset;
   // one load + one multiply per element instead of two factor tables and two multiplies) -- while the table (8n words)
   // fits the L2s next to the data (n <= 2^16: 4 MB, 1/8 of it per XCD).  Above that the two-pass transform takes the
   // factors shift_c^k1 (k1 < R1) and (shift_c^R1)^k2 (k2 < R2) instead: 12 K words for n = 2^19 instead of 4 M.
   auto& cache = tb.coset_cache();
-  const bool factored = l1 != 0 && log_n > NTT_FACTOR_LOG;
+  const bool factored = l1 != 0 && (log_n > NTT_FACTOR_LOG || log_n + rate_bits > NTT_PRE_TABLE_LOG);
   auto key = std::make_tuple(factored ? -log_n : log_n, rate_bits, shift);
   auto it = cache.find(key);
   if (it == cache.end()) {
@@ -530,7 +560,8 @@ void ntt_lde_bitrev(NttTables& tb, const u64* d_coeffs, size_t coeff_stride, u64
   p.pow_table = pw; p.log_n_table = log_n;
   p.in = d_coeffs; p.out = d_lde;
   p.in_poly_stride = coeff_stride; p.out_poly_stride = lde_stride;
-  for (int c = 0; c < nc; c++) p.coset_out_off[c] = (size_t)gl::bitrev(c, rate_bits) * n;
+  p.log_cosets = rate_bits;
+  for (int c = 0; c < nc && c < 8; c++) p.coset_out_off[c] = (size_t)gl::bitrev(c, rate_bits) * n;
   if (factored) {
     p.pre_t = it->second;
     p.pre_i = it->second + ((size_t)nc << l1);

@@ -637,7 +637,9 @@ constexpr int QREC_WAVES = 3;
 constexpr int Q_PF = 1;
 // REC: the gate set of recursive-verifier circuits (adds ArithmeticExtensionGate and PoseidonGate).  The fib-64 hot
 // path runs the REC = false instantiation, whose code is what it was before those gates existed.
-template <bool REC>
+// SUB: the circuit's rate is above 3, the points are a sub-coset of the LDE (below) -- instantiations of their own: with
+// SUB = false the column stride IS the number of points, one value as before.
+template <bool REC, bool SUB>
 __device__ __forceinline__ void quotient_body(const QuotientArgs& a) {
   __shared__ u64 ap[2 * ALPHA_POWS];
   __shared__ AlphaLimbs apl[ALPHA_POWS];
@@ -655,6 +657,9 @@ __device__ __forceinline__ void quotient_body(const QuotientArgs& a) {
     const int c = i / (int)a.num_routed, j = i - c * (int)a.num_routed;
     kb[i] = gl::mul(a.k_is[j], a.chal[CH_BETAS + c]);
   }
+  // The quotient has degree below 2^rate_bits n (rate_bits = min(the circuit's, 3), QuotientArgs), so it is evaluated on the
+  // coset of `big` = 2^(degree_bits + rate_bits) points; in the bit-reversed LDE of a higher rate those points are the first
+  // `big` words of every column (lde[rev(2^(rb-3) i)] = the rate-3 lde[rev(i)]), and the columns are cstride words apart.
   __syncthreads();
   const uint32_t lde_bits = a.degree_bits + a.rate_bits;
   const size_t big = (size_t)1 << lde_bits;
@@ -667,12 +672,13 @@ __device__ __forceinline__ void quotient_body(const QuotientArgs& a) {
   // position of the "next row" point: natural index + 2^rate_bits
   const uint32_t i_next = (i_nat + (1u << a.rate_bits)) & (uint32_t)(big - 1);
   const size_t p_next = gl::bitrev(i_next, lde_bits);
+  const size_t cstride = SUB ? (size_t)1 << a.stride_bits : big;
 
   const int NC = 2, NP = (int)a.num_partial_products, RW = (int)a.num_routed;
   // chunks of max_quotient_degree_factor routed wires (upstream partial_products.rs), NP + 1 of them
   const int nch = NP + 1, per = (int)a.quotient_degree_factor;
   const u32 boff = (u32)p * 8u;
-  const LaneCols csc{a.cs_lde, boff, big}, wrc{a.wires_lde, boff, big}, zsc{a.zs_lde, boff, big};
+  const LaneCols csc{a.cs_lde, boff, cstride}, wrc{a.wires_lde, boff, cstride}, zsc{a.zs_lde, boff, cstride};
   const int n_consts = (int)a.num_selectors;  // selectors first, then the 2 gate constants
 
   u64 res[2] = {0, 0};
@@ -732,7 +738,7 @@ __device__ __forceinline__ void quotient_body(const QuotientArgs& a) {
     const u64 k0 = csc.col(n_consts), k1 = csc.col(n_consts + 1);
     Ctx mc;          // the shared accumulator of the merged gates
     mc.wires = wrc;
-    mc.big = big;
+    mc.big = cstride;
     mc.apl = apl;
     mc.reset();
     u64 bs_sum = 0, bs_w0 = 0;
@@ -836,7 +842,7 @@ __device__ __forceinline__ void quotient_body(const QuotientArgs& a) {
       for (int c = 0; c < NC; c++) {
         const u64 np = c ? np1 : np0, dp = c ? dp1 : dp0;
         u64 prev = k == 0 ? zsc.col(c) : zsc.col(NC + c * NP + k - 1);
-        u64 next = k == NP ? a.zs_lde[(size_t)c * big + p_next] : zsc.col(NC + c * NP + k);
+        u64 next = k == NP ? a.zs_lde[(size_t)c * cstride + p_next] : zsc.col(NC + c * NP + k);
         u64 t = gl::sub_nc(gl::mul_nc(prev, np), gl::mul_nc(next, dp));
         int ti = NC + c * nch + k;
         res[0] = gl::mad_nc(t, ap[ti], res[0]);
@@ -848,7 +854,7 @@ __device__ __forceinline__ void quotient_body(const QuotientArgs& a) {
   {
     Ctx cx;
     cx.wires = wrc;
-    cx.big = big;
+    cx.big = cstride;
     cx.apl = apl;
     const u64 k0 = csc.col(n_consts), k1 = csc.col(n_consts + 1);
     u64 g0 = mg0, g1 = mg1;
@@ -861,7 +867,7 @@ __device__ __forceinline__ void quotient_body(const QuotientArgs& a) {
         // Column descriptors are loop-invariant and the compiler would hoist ALL of them (every column of every
         // evaluator) out of this loop, into hundreds of spilled scalar registers; an opaque copy of the stride per
         // iteration keeps each one next to its load.
-        size_t bg = big;
+        size_t bg = cstride;
         asm volatile("" : "+s"(bg));
         cx.wires.big = bg;
       }
@@ -911,9 +917,14 @@ __device__ __forceinline__ void quotient_body(const QuotientArgs& a) {
 }
 
 __global__ __launch_bounds__(128, Q_WAVES) void k_quotient(QuotientArgs a) {
-  P25_WAVE_PRIO(P25_PRIO_BULK); quotient_body<false>(a); }
+  P25_WAVE_PRIO(P25_PRIO_BULK); quotient_body<false, false>(a); }
 __global__ __launch_bounds__(128, QREC_WAVES) void k_quotient_rec(QuotientArgs a) {
-  P25_WAVE_PRIO(P25_PRIO_BULK); quotient_body<true>(a); }
+  P25_WAVE_PRIO(P25_PRIO_BULK); quotient_body<true, false>(a); }
+// the same two over a sub-coset of a higher-rate LDE
+__global__ __launch_bounds__(128, Q_WAVES) void k_quotient_sub(QuotientArgs a) {
+  P25_WAVE_PRIO(P25_PRIO_BULK); quotient_body<false, true>(a); }
+__global__ __launch_bounds__(128, QREC_WAVES) void k_quotient_rec_sub(QuotientArgs a) {
+  P25_WAVE_PRIO(P25_PRIO_BULK); quotient_body<true, true>(a); }
 
 // out[p] = 1 / (n (x_p - 1)), x_p = g w_big^rev(p): the point-dependent factor of L_0(x) = Z_H(x) / (n (x - 1)).
 __global__ __launch_bounds__(256) void k_l0_inv(const u64* __restrict__ pow_big, uint32_t degree_bits,
@@ -940,10 +951,12 @@ void launch_quotient(const QuotientArgs& a, hipStream_t st) {
   bool rec = false;
   for (uint32_t gi = 0; gi < a.n_gates; gi++) rec |= a.gates[gi].kind >= G_ARITH_EXT;   // the recursion gate set
   const unsigned grid = (unsigned)((big + 127) / 128);
+  if (a.stride_bits < a.degree_bits + a.rate_bits) throw std::runtime_error("quotient: column stride below the number of points");
+  const bool sub = a.stride_bits != a.degree_bits + a.rate_bits;
   if (rec)
-    hipLaunchKernelGGL(k_quotient_rec, dim3(grid), dim3(128), 0, st, a);
+    hipLaunchKernelGGL(sub ? k_quotient_rec_sub : k_quotient_rec, dim3(grid), dim3(128), 0, st, a);
   else
-    hipLaunchKernelGGL(k_quotient, dim3(grid), dim3(128), 0, st, a);
+    hipLaunchKernelGGL(sub ? k_quotient_sub : k_quotient, dim3(grid), dim3(128), 0, st, a);
 }
 
 }  // namespace p25

@@ -6,7 +6,8 @@
 // NT = 2^log_nt sub-transforms make a polynomial.  Lane tid handles the elements e = tid + k * nth, e < T * R.  nth is a
 // multiple of T, so in the t-contiguous kinds a lane's t never changes and its i advances by nth / T: every quantity is
 // an add away from its predecessor.  In the i-contiguous kinds the global offset is tile base + e.  All offsets are in
-// words inside one polynomial (one coset of it) and fit 32 bits: a polynomial has at most 2^25 words.
+// words inside one polynomial (one coset of it in pass 1 of an LDE, all 2^rate_bits cosets in its pass 2) and fit 32
+// bits: a polynomial has at most 2^25 words.
 #pragma once
 #include <stdint.h>
 
@@ -66,6 +67,9 @@ NTTIX_HD BlockId decode_block(uint32_t L, uint32_t log_g, uint32_t n_tiles, uint
   const uint32_t r = m / n_cosets;
   return BlockId{(r % tiles_g) * (1u << log_g) + (L & ((1u << log_g) - 1u)), r / tiles_g, m % n_cosets};
 }
+
+// Coset c of an LDE over 2^log_cosets cosets is stored as the block of N words number rev(c): the LDE's bit-reversed order
+NTTIX_HD uint32_t coset_block(uint32_t coset, int log_cosets) { return brev(coset, log_cosets); }
 
 // The load phase: global offset, LDS slot and element index i of the lane's current element; next() moves to e + nth.
 template <int IN>

@@ -830,8 +830,8 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
 }
 
 
-Circuit build_gadget_circuit(int kind, int param) {
-  CircuitBuilder cb;
+Circuit build_gadget_circuit(int kind, int param, const CircuitConfig& cfg) {
+  CircuitBuilder cb(cfg);
   auto in = [&]() {
     Target t = cb.add_virtual_target();
     cb.input_targets.push_back(t);

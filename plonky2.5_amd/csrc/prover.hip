@@ -4,6 +4,7 @@
 #include <map>
 #include <mutex>
 #include <string.h>
+#include "circuit_io.h"
 #include "poseidon.h"
 #include "staging.h"
 
@@ -229,8 +230,8 @@ struct DeviceCircuit::Ctx : WorkingSet {
 };
 
 DeviceCircuit::DeviceCircuit(Circuit c) : c_(std::move(c)) {
-  if (c_.cfg.num_challenges != 2 || c_.cfg.rate_bits > 3 || c_.gates.size() > 16)
-    throw std::invalid_argument("unsupported circuit configuration");
+  if (c_.cfg.num_challenges != 2 || c_.gates.size() > 16) throw std::invalid_argument("unsupported circuit configuration");
+  check_rate(c_.degree_bits, c_.cfg.rate_bits, c_.cfg.max_quotient_degree_factor, "unsupported circuit configuration: ");
   if (c_.fri_reduction_arity_bits.size() > 8) throw std::invalid_argument("too many FRI layers");
   // register / LDS capacities of k_zpp_* and k_quotient (also enforced when a blob is imported)
   if (c_.num_partial_products + 1 > MAX_CHUNKS || c_.cfg.num_routed_wires > MAX_ROUTED ||
@@ -240,7 +241,7 @@ DeviceCircuit::DeviceCircuit(Circuit c) : c_(std::move(c)) {
   layout_ = make_proof_layout(c_);
   shape_ = make_prover_shape(c_, layout_);
   const size_t n = shape_.n, B = shape_.B, tw = shape_.tw, capw = shape_.capw;
-  const int ncs = (int)shape_.oracle_width[0], db = shape_.degree_bits, rb = shape_.rate_bits;
+  const int ncs = (int)shape_.oracle_width[0], db = shape_.degree_bits, rb = shape_.rate_bits, qb = shape_.quotient_bits;
   // witness program
   WitnessProgram wp = build_witness_program(c_);
   auto up32 = [&](const std::vector<uint32_t>& v) {
@@ -326,7 +327,7 @@ DeviceCircuit::DeviceCircuit(Circuit c) : c_(std::move(c)) {
   // quotient argument prototype
   memset(&qa_proto_, 0, sizeof(qa_proto_));
   qa_proto_.cs_lde = cs_lde_.p;
-  qa_proto_.pow_big = tables_.pow_table(db + rb, false);
+  qa_proto_.pow_big = tables_.pow_table(db + qb, false);   // the quotient's coset: 2^qb n points, qb = min(rb, 3)
   qa_proto_.k_is = k_is_.p;
   qa_proto_.n_gates = (uint32_t)c_.gates.size();
   for (size_t i = 0; i < c_.gates.size(); i++) {
@@ -339,17 +340,18 @@ DeviceCircuit::DeviceCircuit(Circuit c) : c_(std::move(c)) {
   qa_proto_.num_partial_products = shape_.NP;
   qa_proto_.quotient_degree_factor = c_.cfg.max_quotient_degree_factor;
   qa_proto_.degree_bits = db;
-  qa_proto_.rate_bits = rb;
+  qa_proto_.rate_bits = qb;
+  qa_proto_.stride_bits = db + rb;
   {
     u64 g_pow_n = gl::exp_pow2(gl::GENERATOR, db);
-    u64 wr = gl::root_of_unity(rb);
-    for (int k = 0; k < (1 << rb); k++) {
+    u64 wr = gl::root_of_unity(qb);
+    for (int k = 0; k < (1 << qb); k++) {
       qa_proto_.zh[k] = gl::sub(gl::mul(g_pow_n, gl::pow(wr, k)), 1);
       qa_proto_.zh_inv[k] = gl::inv(qa_proto_.zh[k]);
     }
   }
-  l0_inv_ = DevMem(B);
-  launch_l0_inv(qa_proto_.pow_big, db, rb, l0_inv_.p, stream_);
+  l0_inv_ = DevMem(shape_.QB);
+  launch_l0_inv(qa_proto_.pow_big, db, qb, l0_inv_.p, stream_);
   P25_HIP(hipStreamSynchronize(stream_));
   qa_proto_.l0_inv = l0_inv_.p;
 }
@@ -637,9 +639,10 @@ void DeviceCircuit::enqueue_partial_products(Ctx& x, hipStream_t st) {
 }
 
 // "compute quotient polys": quotient values on the coset from the wires / Z LDEs and the challenge block, then the
-// coset iNTT to 8n coefficients per challenge (= the NC x 8 chunks of n, contiguous).
+// coset iNTT to 8n coefficients per challenge (= the NC x 8 chunks of n, contiguous).  Both run on the quotient's own coset
+// of QB = 2^min(rate_bits, 3) n points, which the kernel reads from the first QB words of every LDE column.
 void DeviceCircuit::enqueue_quotient(Ctx& x, hipStream_t st, bool alpha_table) {
-  const size_t B = shape_.B;
+  const size_t QB = shape_.QB;
   u64* chal = x.chal.p;
   if (alpha_table) launch_alpha_pows(chal, x.alpha_pows.p, st);  // prove_one: the transcript launch that drew the alphas wrote it
   {
@@ -653,7 +656,7 @@ void DeviceCircuit::enqueue_quotient(Ctx& x, hipStream_t st, bool alpha_table) {
     launch_quotient(qa, st);
   }
   // coset iNTT of the 2 value vectors (stored at bit-reversed positions) -> 8n coefficients each
-  ntt_inverse(tables_, x.q_vals.p, B, true, x.q_tmp.p, B, x.q_coeffs.p, B, shape_.degree_bits + shape_.rate_bits, shape_.NC,
+  ntt_inverse(tables_, x.q_vals.p, QB, true, x.q_tmp.p, QB, x.q_coeffs.p, QB, shape_.degree_bits + shape_.quotient_bits, shape_.NC,
               gl::GENERATOR, st);
 }
 
@@ -709,7 +712,7 @@ void DeviceCircuit::quotient(const u64* wires, const u64* zs_pp, const u64* beta
   ntt_inverse_then_lde(tables_, x.wires_vals.p, n, x.tmp.p, n, x.wires_coeffs.p, n, x.wires_lde.p, B, db, rb, W, gl::GENERATOR, st);
   ntt_inverse_then_lde(tables_, x.zs_vals.p, n, x.tmp.p, n, x.zs_coeffs.p, n, x.zs_lde.p, B, db, rb, nz, gl::GENERATOR, st);
   enqueue_quotient(x, st);
-  P25_HIP(hipMemcpyAsync(out, x.q_coeffs.p, (size_t)NC * B * 8, hipMemcpyDeviceToHost, st));
+  P25_HIP(hipMemcpyAsync(out, x.q_coeffs.p, (size_t)NC * shape_.QB * 8, hipMemcpyDeviceToHost, st));
   // context 0 goes back to proving: a circuit without registered public inputs never rewrites the hash words, so put
   // hash_no_pad([]) back instead of leaving the caller's (possibly arbitrary) wires there
   if (c_.pi_row >= 0) P25_HIP(hipMemcpyAsync(x.preamble.p + 4, preamble_.p + 4, 32, hipMemcpyDeviceToDevice, st));
@@ -764,7 +767,7 @@ void fri_prove_standalone(NttTables& tables, const u64* coeffs, const FriShape& 
     bits -= a;
     if (deg < 0 || bits < (int)sh.cap_height) throw std::invalid_argument("FRI layer smaller than the Merkle cap");
   }
-  if (sh.num_queries < 1 || sh.num_queries > 64 || sh.pow_bits < 0 || sh.pow_bits > 32 || sh.rate_bits < 0 || sh.rate_bits > 3)
+  if (sh.num_queries < 1 || sh.num_queries > 64 || sh.pow_bits < 0 || sh.pow_bits > 32 || sh.rate_bits < 0 || sh.rate_bits > MAX_RATE_BITS)
     throw std::invalid_argument("FRI parameters out of range");
   FriWork w;
   w.alloc(sh.log_n, sh.rate_bits, sh.cap_height, sh.arity_bits);

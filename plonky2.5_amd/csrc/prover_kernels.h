@@ -89,9 +89,11 @@ struct GateEntry {
   uint32_t kind, selector_index, group_start, group_end;
 };
 struct QuotientArgs {
-  const u64* cs_lde;     // [num_cs][big]  selectors | constants | sigmas, bit-reversed positions
-  const u64* wires_lde;  // [num_wires][big]
-  const u64* zs_lde;     // [NC*(1+NP)][big]
+  // big = 2^(degree_bits + rate_bits) points of the quotient's coset; the LDE columns are 2^stride_bits words apart and the
+  // points are the first `big` words of each (rate_bits = min(the circuit's rate_bits, 3), stride_bits = degree_bits + the circuit's)
+  const u64* cs_lde;     // [num_cs][2^stride_bits]  selectors | constants | sigmas, bit-reversed positions
+  const u64* wires_lde;  // [num_wires][2^stride_bits]
+  const u64* zs_lde;     // [NC*(1+NP)][2^stride_bits]
   const u64* pow_big;    // w_big^e, e < big
   const u64* k_is;       // [num_routed]
   const u64* chal;       // challenge block
@@ -103,6 +105,7 @@ struct QuotientArgs {
   u64 zh[8], zh_inv[8];  // Z_H on the coset (index = i mod 2^rate_bits), and inverses
   const u64* l0_inv;     // [big] 1 / (n (x - 1)) at bit-reversed positions (per circuit)
   const u64* pi_hash;    // [4] public-inputs hash of this proof (PublicInputGate: wire_i - hash_i)
+  uint32_t stride_bits;  // log2 of the words between two LDE columns (read by the sub-coset instantiations only)
 };
 void launch_l0_inv(const u64* d_pow_big, uint32_t degree_bits, uint32_t rate_bits, u64* d_out, hipStream_t st);
 void launch_alpha_pows(const u64* d_chal, u64* d_alpha_pows, hipStream_t st);

@@ -34,8 +34,9 @@ inline size_t eval_scratch_words(uint32_t n_points, size_t total_polys, uint32_t
 // from a Circuit and its ProofLayout; DeviceCircuit keeps it.
 struct ProverShape {
   int degree_bits, rate_bits;
+  int quotient_bits;       // min(rate_bits, 3): the quotient has degree below 8n and is evaluated on 2^quotient_bits n points
   unsigned cap_height;
-  size_t n, B;             // rows; size of the LDE domain
+  size_t n, B, QB;         // rows; size of the LDE domain; of the quotient's coset (= B up to rate_bits 3)
   int W, NC, NP, nz, nq;   // wires, challenges, partial products per challenge, Z + partial-product polynomials, quotient chunks
   size_t capw, tw;         // words of a Merkle cap; of a tree over B leaves
   uint32_t oracle_width[4];   // constants|sigmas, wires, Zs|partial products, quotient chunks
@@ -55,6 +56,8 @@ inline ProverShape prover_shape(int degree_bits, int rate_bits, unsigned cap_hei
   s.cap_height = cap_height;
   s.n = (size_t)1 << degree_bits;
   s.B = s.n << rate_bits;
+  s.quotient_bits = rate_bits < 3 ? rate_bits : 3;
+  s.QB = s.n << s.quotient_bits;
   s.W = wires;
   s.NC = challenges;
   s.NP = partial_products;

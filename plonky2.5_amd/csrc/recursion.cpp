@@ -838,4 +838,17 @@ Circuit build_recursive_verifier(const Circuit& inner, const u64 digest[4], cons
   return cb.build();
 }
 
+Circuit build_shrink_circuit(const Circuit& inner, const u64 digest[4], const std::vector<u64>& cs_cap, const CircuitConfig& cfg) {
+  if (cs_cap.size() != ((size_t)4 << inner.cfg.cap_height)) throw std::invalid_argument("shrink circuit: bad cap size");
+  CircuitBuilder cb(cfg);
+  Hash dg;
+  for (int i = 0; i < 4; i++) dg[i] = cb.constant(digest[i]);
+  std::vector<Hash> cap(cs_cap.size() / 4);
+  for (size_t k = 0; k < cap.size(); k++)
+    for (int i = 0; i < 4; i++) cap[k][i] = cb.constant(cs_cap[4 * k + i]);
+  const ProofTargets pt = verify_one(cb, inner, dg, cap);
+  cb.register_public_inputs(pt.public_inputs);
+  return cb.build();
+}
+
 }  // namespace p25

@@ -52,4 +52,10 @@ Circuit build_gate_eval_circuit(GateKind kind);
 Circuit build_recursive_verifier(const Circuit& inner, const u64 digest[4], const std::vector<u64>& cs_cap, int n_proofs,
                                  bool expose_commitment = false);
 
+// The shrink step (upstream's single-proof recursion under another config): verifies ONE proof of `inner` exactly as
+// build_recursive_verifier(inner, .., 1) does, in a circuit built under `cfg`, and registers the inner proof's public
+// inputs as its own, the same words in the same order (upstream `register_public_inputs(&proof.public_inputs)`) -- none
+// if the inner circuit has none.  An aggregate's commitment survives any number of shrink steps unchanged.
+Circuit build_shrink_circuit(const Circuit& inner, const u64 digest[4], const std::vector<u64>& cs_cap, const CircuitConfig& cfg);
+
 }  // namespace p25

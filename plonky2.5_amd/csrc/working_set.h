@@ -56,7 +56,7 @@ struct WorkingSet {
   }
   template <class F>
   void each_buffer(const ProverShape& s, F&& f) {
-    const size_t n = s.n, B = s.B, W = s.W, NC = s.NC, NP = s.NP, nz = s.nz, nq = s.nq, blocks = (n + 255) / 256;
+    const size_t n = s.n, B = s.B, QB = s.QB, W = s.W, NC = s.NC, NP = s.NP, nz = s.nz, nq = s.nq, blocks = (n + 255) / 256;
     f(wires_vals, W * n);
     f(wires_coeffs, W * n);
     f(tmp, W * n);
@@ -69,9 +69,9 @@ struct WorkingSet {
     f(zpp_chunk, NC * (NP + 1) * n);
     f(zpp_tot, NC * n);
     f(zpp_btot, NC * blocks + 16);
-    f(q_vals, NC * B);
-    f(q_tmp, NC * B);
-    f(q_coeffs, NC * B);
+    f(q_vals, NC * QB);
+    f(q_tmp, NC * QB);
+    f(q_coeffs, NC * QB);
     f(q_lde, nq * B);
     f(q_tree, s.tw);
     f(preamble, 8);

@@ -133,8 +133,13 @@ __device__ __forceinline__ void mds_rc(u64 s[WIDTH], rc_ptr k, u32 rows = 0xFFF)
   for (int r = 0; r < WIDTH; r++) {
     if (!((rows >> r) & 1u)) continue;
     u64 al, ah, dm, t;
-    asm("v_mad_u64_u32 %0, %1, %2, 17, %3" : "=v"(al), "=s"(dm) : "v"(lo[r]), "s"(k[2 * r]));
-    asm("v_mad_u64_u32 %0, %1, %2, 17, %3" : "=v"(ah), "=s"(dm) : "v"(hi[r]), "s"(k[2 * r + 1]));
+    if (r == 0) {   // the diagonal: 17 + 8
+      asm("v_mad_u64_u32 %0, %1, %2, 25, %3" : "=v"(al), "=s"(dm) : "v"(lo[r]), "s"(k[2 * r]));
+      asm("v_mad_u64_u32 %0, %1, %2, 25, %3" : "=v"(ah), "=s"(dm) : "v"(hi[r]), "s"(k[2 * r + 1]));
+    } else {
+      asm("v_mad_u64_u32 %0, %1, %2, 17, %3" : "=v"(al), "=s"(dm) : "v"(lo[r]), "s"(k[2 * r]));
+      asm("v_mad_u64_u32 %0, %1, %2, 17, %3" : "=v"(ah), "=s"(dm) : "v"(hi[r]), "s"(k[2 * r + 1]));
+    }
 #define P25_MDS_TERM(i, C)            \
   mad_k<C>(al, lo[(i + r) % WIDTH]); \
   mad_k<C>(ah, hi[(i + r) % WIDTH]);
@@ -150,10 +155,6 @@ __device__ __forceinline__ void mds_rc(u64 s[WIDTH], rc_ptr k, u32 rows = 0xFFF)
     P25_MDS_TERM(10, 34)
     P25_MDS_TERM(11, 20)
 #undef P25_MDS_TERM
-    if (r == 0) {
-      mad_k<8>(al, lo[0]);
-      mad_k<8>(ah, hi[0]);
-    }
     // value = al + ah * 2^32, al < 2^43, ah < 2^42:  X = al + (ah >> 32) * (2^32 - 1) < 2^44, then
     // add (ah & 0xffffffff) << 32; a carry out of bit 64 is worth 2^32 - 1 and cannot ripple
     // (after a wrap the high word is < 2^12).
@@ -176,8 +177,11 @@ static_assert(MDS_CIRC[0] == 17 && MDS_CIRC[1] == 15 && MDS_CIRC[2] == 41 && MDS
                   MDS_CIRC[9] == 18 && MDS_CIRC[10] == 34 && MDS_CIRC[11] == 20 && MDS_DIAG0 == 8,
               "mds_rc hard-codes the MDS entries as inline constants");
 
+#endif
+
 #include "poseidon_p3r.h"
 
+#if defined(__HIP_DEVICE_COMPILE__)
 // x^7 of the round-0 constants of the capacity words: what the first S-box layer yields for them when the capacity
 // enters as zero (the first permutation of every sponge, every two_to_one) -- 4 of that layer's 12 S-boxes.
 constexpr u64 sbox_const(u64 x) {
@@ -216,12 +220,8 @@ __device__ __forceinline__ void permute_dev(u64 s[WIDTH], u32 rows, bool cap0 = 
   }
 #pragma unroll
   for (int i = 0; i < WIDTH; i++) s[i] = sbox(s[i]);
-  // the 22 partial rounds: head block (MDS of round 3 + rounds 4, 5), six blocks of three, tail block of two
-  p3r::tbl_ptr tp = (p3r::tbl_ptr)&p3r::TBL;
-  asm("" : "+s"(tp));
-  p3r::three_rounds<true>(s, tp, tp->kh);
-  for (int b = 0; b < p3r::BLOCKS; b++) p3r::three_rounds<false>(s, tp, tp->kc[b]);
-  p3r::two_rounds(s, tp);
+  // the 22 partial rounds: head block (MDS of round 3 + rounds 4, 5), then five blocks of four
+  p3r::partial_rounds(s);
   r = HALF_FULL + N_PARTIAL + 1;
   for (int k = 0; k < HALF_FULL - 1; k++, r++) {
 #pragma unroll
@@ -297,7 +297,8 @@ GL_HD void hash_no_pad_strided(const u64* in, size_t stride, int n, u64 out[4]) 
     int m = n - off < RATE ? n - off : RATE;
     for (int i = 0; i < m; i++) s[i] = in[(size_t)(off + i) * stride];
     const int next = n - (off + RATE);  // inputs still to absorb after this permutation
-    permute_rows(s, next <= 0 ? ROWS_DIGEST : (next >= RATE ? ROWS_CAPACITY : ROWS_ALL), off == 0);
+    // a last partial block overwrites words 0 .. next-1 and keeps the rest
+    permute_rows(s, next <= 0 ? ROWS_DIGEST : (next >= RATE ? ROWS_CAPACITY : ROWS_ALL & ~((1u << next) - 1u)), off == 0);
   }
 #pragma unroll
   for (int i = 0; i < 4; i++) out[i] = s[i];

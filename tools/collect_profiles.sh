@@ -4,6 +4,7 @@
 # Writes gpurun_out/<tag>_*; copy what should be judged into profiles/ (tools/make_traffic_json.py <tag> rewrites
 # profiles/pmc_hash_leaves.json from the FETCH/WRITE passes).
 # A second argument selects sections (a gpurun call is limited to 20 minutes): tests | pmc | bench | agg | config5 (default: all).
+# pmc-valu is a section too: the first pass of pmc alone (the instruction counters: what bench.py's VALU view reads).
 # Order for a final bundle: pmc, agg and config5 first, copy the PMC json files into profiles/ (bench.py's VALU views read
 # them and check the kernel sources' hash), then bench.
 set -u
@@ -24,12 +25,17 @@ python -m pytest tests -m gpu -q --durations=8 > $OUT/${TAG}_pytest_gpu.txt 2>&1
 python -c "import __graft_entry__ as g; g.smoke()" >> $OUT/${TAG}_pytest_gpu.txt 2>&1
 tail -3 $OUT/${TAG}_pytest_gpu.txt
 fi
-if want pmc; then
-# PMC passes (each alone with --kernel-trace): a batch of 4 = the kernels of the throughput path
-for C in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_INSTS_LDS" "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU"; do
+if want pmc || want pmc-valu; then
+# PMC passes (each alone with --kernel-trace, counters in a run of their own): a batch of 4 = the kernels of the throughput path.
+# Every pass runs under its own time limit, and a pass that fails ends the script: nothing more is started on the GPU.
+SETS=("SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_INSTS_LDS")
+want pmc && SETS+=("FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU")
+for C in "${SETS[@]}"; do
   N=$(echo $C | cut -d' ' -f1)
   rm -rf $OUT/_pmc
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/_pmc -- python3 tools/prove_one.py 4 > $OUT/_pmc.log 2>&1
+  timeout -k 10 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/_pmc -- python3 tools/prove_one.py 4 > $OUT/_pmc.log 2>&1
+  rc=$?
+  if [ $rc -ne 0 ]; then echo "PMC pass $N failed (rc=$rc); stopping" >&2; tail -5 $OUT/_pmc.log >&2; exit $rc; fi
   python3 tools/pmc_summary.py $OUT/_pmc $OUT/${TAG}_pmc_${N}.json 4 > $OUT/${TAG}_pmc_${N}.txt
   rm -rf $OUT/_pmc
 done

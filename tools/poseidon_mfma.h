@@ -322,11 +322,7 @@ __device__ __forceinline__ void permute_wave(u64 s[WIDTH], u32 rows, const Ctx& 
   to_pairs(s, A, B);
   full_rounds<0, 3, true>(A, B, c, 7);
   from_pairs(s, A, B);
-  p3r::tbl_ptr tp = (p3r::tbl_ptr)&p3r::TBL;
-  asm("" : "+s"(tp));
-  p3r::three_rounds<true>(s, tp, tp->kh);
-  for (int blk = 0; blk < p3r::BLOCKS; blk++) p3r::three_rounds<false>(s, tp, tp->kc[blk]);
-  p3r::two_rounds(s, tp);
+  p3r::partial_rounds(s);
   to_pairs(s, A, B);
   const u32 umask = ((rows & 0x00F) ? 1u : 0u) | ((rows & 0x0F0) ? 2u : 0u) | ((rows & 0xF00) ? 4u : 0u);
   full_rounds<3, 4, false>(A, B, c, umask);

@@ -255,7 +255,61 @@ p25_status p25_circuit_build_p3_verifier(const p25_p3_config* cfg, int32_t air, 
  *              the function without the suffix plus `periodic`, copies what it is given, and with periodic = NULL or
  *              n_columns = 0 IS that function (same words, same circuit blob).  The functions without it return
  *              P25_ERR_INVALID_ARG for an AIR that contains op 7, name the _pc form and write nothing.  The batch entry
- *              points need no new form: the handle carries the AIR. */
+ *              points need no new form: the handle carries the AIR.
+ *
+ * PREPROCESSED COLUMNS (this library's extension, like public values and periodic columns: the reference's `Air` trait,
+ * src/p3/air.rs:10-27, has none; plonky3's uni-stark, Winterfell and ethSTARK call it the preprocessed trace).  Fixed data
+ * that is not periodic or is longer than 256 rows -- opcode selectors of a program, a ROM or operand column, an irregular
+ * boundary flag, a long table of round keys: a matrix of PW known columns as high as the trace, COMMITTED ONCE.  Its
+ * commitment is part of the verifying key; the matrix is opened at zeta and zeta w_n and queried like the main trace.
+ * Restated from plonky3's conventions, not from the reference, so UNPINNED like public values and periodic columns.
+ *   Nodes      node.op 8 PREP_LOCAL(a): preprocessed column a < width at the current row; 9 PREP_NEXT(a): at the next row,
+ *              cyclic as NEXT is.  Both COUNT AS DEGREE 1, exactly like LOCAL, and cost the device form no slot.
+ *   Columns    p25_air cannot grow, so they travel beside it in p25_air_preprocessed: values[2^log_n][width], row-major
+ *              like a trace, copied by every function that takes them.  An index >= width, a width above
+ *              P25_AIR_MAX_PREPROCESSED (64), a log_n that differs from the trace's and a value >= p are
+ *              P25_ERR_INVALID_ARG; the message names the limit.
+ *   Commitment 4 words: the Poseidon2 MMCS root over the columns' LDE on 7 H_{n 2^log_blowup} in bit-reversed leaf order --
+ *              the commit the trace gets, applied to a matrix of `width` columns.  Verifying-key data, NOT part of a
+ *              proof's words.  p25_p3_preprocessed_commit computes it on the host (the host prover's MMCS);
+ *              p25_p3_prover_preprocessed_commit returns what a handle computed on the device.  They agree word for word.
+ *   Words      p25_p3_config does not change.  num_inputs = the words p25_p3_config describes + 4 PW (the openings) +
+ *              num_queries (PW + 4 (log_n + log_blowup)) (a third batch per query) + n_public.  The flat layout is
+ *              `add_virtual_to` order with two insertions:
+ *                trace_commit | quotient_commit | trace_local E[W] | trace_next E[W] | chunks E[2 Q]
+ *                | prep_local E[PW] | prep_next E[PW]
+ *                | commit_phase_commits | query_proofs | final_poly | pow_witness
+ *                | per query: trace batch | quotient batch | preprocessed batch {row u64[PW], path H[log_n + log_blowup]}
+ *                | public values
+ *              The JSON forms (p25_p3_proof_from_json, p25_p3_inputs_to_json) follow the reference's serde model, which has
+ *              no such fields: they do not cover these proofs.
+ *   Transcript the 4 commitment words are observed directly after the trace commitment, before the public values and
+ *              before alpha is sampled.  Opened values are treated exactly as the trace's are.
+ *   Openings   the batches run in the order trace, quotient, preprocessed; inside the preprocessed batch the points are
+ *              (zeta, prep_local) then (zeta w_n, prep_next).  The matrix has the trace's height, so it shares the trace's
+ *              log_height slot of the reduced openings and its alpha powers CONTINUE where that slot stands after the
+ *              quotient chunks: what the reference's generic loop (verifier.rs:242-344) does with a third entry.
+ *   Circuit    p25_circuit_build_p3_verifier_air_pp holds the commitment as FOUR CONSTANTS, observes it at the place stated
+ *              above and passes a third (commitment, matrices, points) entry; no new gate kind, no new generator.  A
+ *              proof made under other columns fails the outer proof with P25_ERR_WITNESS_CONFLICT.
+ *   Device     a p25_p3_prover made by p25_p3_prover_create_pp builds the columns' coefficients (PW 2^log_n words), LDE
+ *              (PW 2^(log_n + log_blowup)) and tree (8 * 2^(log_n + log_blowup)) ONCE, on the device, on its first proving
+ *              call, with the launches the trace takes.  They are constant tables shared by every proof of every group:
+ *              outside the 12 GiB group budget, counted by p25_p3_prover_scratch_bytes under proving_out.  That first
+ *              call blocks the host until the tables stand (a third exception beside the two of p25_p3_prove_batch_dev).
+ *              A handle that only verifies computes the 4 root words in a temporary, frees it, and reports
+ *              proving_out = 0.
+ *   Verifying  p25_p3_verify_batch[_dev] check the third batch against the HANDLE's root, not against proof words.  A failure
+ *              of it is P25_P3_REJECT_INPUT_MERKLE (32).  For handles with preprocessed columns the order of the input
+ *              checks is trace, quotient, preprocessed batch of query 0, then of query 1, ...: key 2 + 3 q + b, and the FRI
+ *              keys start at F = 2 + 3 num_queries; for all other handles the keys (2 + 2 q + b) are what they were.
+ *   Interface  p25_p3_prove_air_pp, p25_p3_prover_create_pp, p25_circuit_build_p3_verifier_air_pp: each is the _pc function
+ *              plus `preprocessed`, takes `periodic` and `preprocessed` (either may be NULL), and with preprocessed = NULL
+ *              or width = 0 IS the _pc function (same words, same circuit blob, byte for byte).  Every function that takes no
+ *              p25_air_preprocessed returns P25_ERR_INVALID_ARG for an AIR that contains op 8 or 9, names the _pp form and
+ *              writes nothing.  The batch entry points need no new form: the handle carries the AIR and its columns.
+ *   Not here   more than one preprocessed matrix, heights other than the trace's, lookup or permutation arguments over the
+ *              columns, the JSON forms. */
 enum { P25_AIR_MAX_PUBLIC = 64 };
 enum { P25_AIR_MAX_PERIODIC = 32, P25_AIR_MAX_LOG_PERIOD = 8 };
 typedef struct {
@@ -275,12 +329,23 @@ typedef struct {
   const uint32_t* log_period;    /* [n_columns] */
   const uint64_t* values;        /* the columns back to back: column c has 2^log_period[c] words */
 } p25_air_periodic;
+enum { P25_AIR_MAX_PREPROCESSED = 64 };
+typedef struct {
+  uint32_t width;          /* 0..P25_AIR_MAX_PREPROCESSED columns */
+  uint32_t log_n;          /* must equal the trace's log height */
+  const uint64_t* values;  /* [2^log_n][width], row-major like a trace, every word < p */
+} p25_air_preprocessed;
 /* p3_verify_proof for a user AIR: `builder.p3_verify_proof::<H>(proof, &air, fri_config)` with any `impl Air`
  * (src/p3/mod.rs:66-94, 239-250).  cfg->trace_width must equal air->width. */
 p25_status p25_circuit_build_p3_verifier_air(const p25_p3_config* cfg, const p25_air* air, p25_circuit** out);
 /* The same for an AIR with periodic columns (PERIODIC COLUMNS above); log_period is checked against cfg->log_trace_height. */
 p25_status p25_circuit_build_p3_verifier_air_pc(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
                                                 p25_circuit** out);
+/* The same for an AIR with preprocessed columns (PREPROCESSED COLUMNS above); either of `periodic` and `preprocessed` may
+ * be NULL.  preprocessed->log_n is checked against cfg->log_trace_height.  The columns' commitment for cfg's log_blowup is
+ * computed here (as p25_p3_preprocessed_commit does) and held by the circuit as four constants. */
+p25_status p25_circuit_build_p3_verifier_air_pp(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
+                                                const p25_air_preprocessed* preprocessed, p25_circuit** out);
 /* Native plonky3 prover (see p25_p3_prove_fibonacci) for a user AIR and its trace, trace[row * width + col],
  * 2^log_n rows.  P25_ERR_INVALID_ARG if the trace does not satisfy the AIR. */
 p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t num_queries,
@@ -309,6 +374,17 @@ p25_status p25_p3_prove_air_pc(const p25_air* air, const uint64_t* trace, const 
                                const p25_air_periodic* periodic, int32_t log_n, int32_t log_blowup, int32_t num_queries,
                                int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
                                size_t* n_out, p25_p3_config* cfg_out);
+/* p25_p3_prove_air_pc for an AIR with preprocessed columns (PREPROCESSED COLUMNS above); either of `periodic` and
+ * `preprocessed` may be NULL.  *n_out = the words p25_p3_config describes + 4 PW + num_queries (PW + 4 (log_n + log_blowup))
+ * + n_public, PW = preprocessed->width.  P25_ERR_INVALID_ARG if the trace does not satisfy the AIR under these columns. */
+p25_status p25_p3_prove_air_pp(const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
+                               const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed, int32_t log_n,
+                               int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start, int32_t threads,
+                               uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out);
+/* The commitment of preprocessed columns under `log_blowup` (1..4): verifying-key data, 4 words.  Host only; the host
+ * prover's MMCS.  width 0 is P25_ERR_INVALID_ARG here (there is nothing to commit), as are the limits named above. */
+p25_status p25_p3_preprocessed_commit(const p25_air_preprocessed* preprocessed, int32_t log_blowup, int32_t threads,
+                                      uint64_t commit_out[4]);
 
 /* Small circuits mirroring the reference's gadget tests (src/p3/mod.rs:271-494 test_p3_and / xor / lsh /
  * rsh / reverse, src/p3/commit.rs:173-198 test_compress): kind 0 and(x,y) 1 xor(x,y) 2 lsh(x,param)
@@ -595,7 +671,7 @@ p25_status p25_verify_batch_dev(p25_circuit* c, const uint64_t* digest4, const u
  * p25_p3_prover_create   host only, works without a GPU.  Replaces the shape half of p25_p3_prove_air_ex: validates exactly
  *     what that function validates, with the same P25_ERR_INVALID_ARG cases (the AIR itself; log_n 1..22, log_blowup 1..4,
  *     log_n + log_blowup <= 24; num_queries >= 1; pow_bits 0..30; log_quotient_degree <= log_blowup), and compiles the AIR
- *     into the register program the quotient kernel interprets.  LOCAL / NEXT / CONST / PUBLIC / PERIODIC nodes cost nothing; the device form's
+ *     into the register program the quotient kernel interprets.  LOCAL / NEXT / CONST / PUBLIC / PERIODIC / PREP_LOCAL / PREP_NEXT nodes cost nothing; the device form's
  *     own limits are 64 arithmetic-node values alive at the same time (after a liveness pass over the DAG in constraint
  *     order), 2^20 instructions and 65535 queries: an AIR beyond them is refused HERE, with a message naming the limit,
  *     never later.  Width 64 and 512 nodes are within them.  No device memory is touched before the first compute call.
@@ -655,6 +731,14 @@ p25_status p25_p3_prover_create(const p25_air* air, int32_t log_n, int32_t log_b
  * tables on the first compute call.  A PERIODIC node costs the device form nothing, like LOCAL. */
 p25_status p25_p3_prover_create_pc(const p25_air* air, const p25_air_periodic* periodic, int32_t log_n, int32_t log_blowup,
                                    int32_t num_queries, int32_t pow_bits, p25_p3_prover** out);
+/* The same for an AIR with preprocessed columns (PREPROCESSED COLUMNS, above); either of `periodic` and `preprocessed` may be
+ * NULL, preprocessed->log_n is checked against log_n here, and the matrix is copied.  Host only like the others. */
+p25_status p25_p3_prover_create_pp(const p25_air* air, const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed,
+                                   int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits, p25_p3_prover** out);
+/* The 4 words of the preprocessed commitment as the handle computed them on the device (on this call, if no compute call
+ * has done so yet): word for word what p25_p3_preprocessed_commit returns.  P25_ERR_INVALID_ARG for a handle without
+ * preprocessed columns, then P25_ERR_NO_DEVICE without a GPU. */
+p25_status p25_p3_prover_preprocessed_commit(p25_p3_prover* p, uint64_t commit_out[4]);
 void p25_p3_prover_destroy(p25_p3_prover* p);
 p25_status p25_p3_prover_config(const p25_p3_prover* p, p25_p3_config* cfg_out, size_t* num_inputs_out);
 p25_status p25_p3_prove_batch(p25_p3_prover* p, const uint64_t* traces, size_t n_proofs, const uint64_t* pow_starts,
@@ -677,7 +761,8 @@ p25_status p25_p3_prover_set_scratch_budget(p25_p3_prover* p, size_t bytes);
  * writes, p25_p3_proof_from_json imports and p25_prove_batch reads -- for the AIR and shape of a p25_p3_prover handle: a
  * screen before the outer prover, which can only answer P25_ERR_WITNESS_CONFLICT.  Per proof, P25_OK or the P25_P3_REJECT_*
  * code of the FIRST check the sequential verifier fails, in that file's statement order: a word >= p anywhere; the proof of
- * work; the input openings (trace batch, then quotient batch) of every query in index order; then per query the Merkle
+ * work; the input openings (trace batch, then quotient batch, then -- for a handle with preprocessed columns -- their batch,
+ * checked against the handle's commitment) of every query in index order; then per query the Merkle
  * opening of every FRI round in order and the comparison of the folded value with final_poly -- so a final-polynomial
  * failure of query 0 precedes a Merkle failure of query 1 --; the quotient identity at zeta last.  A zero denominator x - z
  * in a reduced opening (zeta in the base field, on the LDE coset) counts as that query's final-polynomial failure and is

@@ -7,7 +7,7 @@ import numpy as np
 __all__ = ["P25Error", "lib", "lib_path", "device_init", "shader_clock_hz", "poseidon_permute", "poseidon2_permute",
            "merkle_commit", "merkle_tree_words", "lde_commit", "EXPORTED_SYMBOLS", "P",
            "P3Config", "Circuit", "CircuitConfig", "p3_proof_from_json", "Timings", "p3_prove_fibonacci", "p3_inputs_to_json",
-           "Air", "p3_prove_air", "P3Prover", "transcript", "fri_prove", "eval_polys", "RuntimeInfo", "runtime_info", "Comm",
+           "Air", "p3_prove_air", "p3_preprocessed_commit", "P3Prover", "transcript", "fri_prove", "eval_polys", "RuntimeInfo", "runtime_info", "Comm",
            "comm_unique_id", "WARN_HW_QUEUES_LATE", "REJECT_VANISHING", "REJECT_POW", "REJECT_MALFORMED",
            "REJECT_INITIAL_MERKLE", "REJECT_FRI_EVAL", "REJECT_FRI_MERKLE", "REJECT_FINAL_POLY"]
 
@@ -62,6 +62,10 @@ class AirPeriodicC(C.Structure):
     _fields_ = [("n_columns", C.c_uint32), ("log_period", C.POINTER(C.c_uint32)), ("values", C.POINTER(C.c_uint64))]
 
 
+class AirPreprocessedC(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("log_n", C.c_uint32), ("values", C.POINTER(C.c_uint64))]
+
+
 class Air:
     """An AIR as an expression DAG (p25_air in include/p25.h): the data form of the reference's `Air` trait
     (src/p3/air.rs:10-18).  Build it like the trait's `eval` body:
@@ -74,11 +78,20 @@ class Air:
 
     periodic: a list of 1-D uint64 arrays, the AIR's periodic columns (include/p25.h, PERIODIC COLUMNS): column i has
     2^k values, 1 <= k <= min(log_n, 8), is read with air.periodic(i) and is its values[row mod 2^k] on every trace row.
+
+    preprocessed: uint64[2^log_n][PW], the AIR's preprocessed columns (include/p25.h, PREPROCESSED COLUMNS): a matrix as
+    high as the trace, committed once (the commitment is verifying-key data), read with air.prep_local(a) / air.prep_next(a).
     """
     ALWAYS, FIRST_ROW, LAST_ROW, TRANSITION = 0, 1, 2, 3
 
-    def __init__(self, width, n_public=0, periodic=None):
+    def __init__(self, width, n_public=0, periodic=None, preprocessed=None):
         self.width, self.n_public, self.nodes, self.constraints = width, int(n_public), [], []
+        self.preprocessed = None
+        if preprocessed is not None:
+            pp = np.ascontiguousarray(preprocessed, dtype=np.uint64)
+            if pp.ndim != 2:
+                raise ValueError("preprocessed must be [2^log_n][PW]")
+            self.preprocessed = pp
         self.periodic_columns = [np.ascontiguousarray(c, dtype=np.uint64).reshape(-1) for c in (periodic or [])]
 
     def _n(self, op, a=0, b=0, value=0):
@@ -90,6 +103,8 @@ class Air:
     def const(self, v): return self._n(2, 0, 0, int(v))
     def public(self, i): return self._n(6, int(i))
     def periodic(self, i): return self._n(7, int(i))
+    def prep_local(self, a): return self._n(8, int(a))
+    def prep_next(self, a): return self._n(9, int(a))
     def add(self, x, y): return self._n(3, x, y)
     def sub(self, x, y): return self._n(4, x, y)
     def mul(self, x, y): return self._n(5, x, y)
@@ -132,6 +147,18 @@ class Air:
         vals = np.ascontiguousarray(np.concatenate(self.periodic_columns), dtype=np.uint64)
         c = AirPeriodicC(len(logs), lp, vals.ctypes.data_as(C.POINTER(C.c_uint64)))
         c._keep = (lp, vals)
+        return c
+
+
+    def preprocessed_to_c(self):
+        """p25_air_preprocessed of the columns (for the _pp entry points), or None without columns."""
+        pp = self.preprocessed
+        if pp is None or pp.shape[1] == 0:
+            return None
+        if pp.shape[0] < 2 or pp.shape[0] & (pp.shape[0] - 1):
+            raise ValueError("the preprocessed matrix holds 2^log_n rows")
+        c = AirPreprocessedC(pp.shape[1], int(pp.shape[0]).bit_length() - 1, pp.ctypes.data_as(C.POINTER(C.c_uint64)))
+        c._keep = pp
         return c
 
 
@@ -277,6 +304,12 @@ EXPORTED_SYMBOLS = {
     "p25_p3_prover_create_pc": (i32, [C.POINTER(AirC), vp, i32, i32, i32, i32, C.POINTER(vp)]),
     "p25_circuit_build_p3_verifier_air_pc": (i32, [C.POINTER(P3Config), C.POINTER(AirC), vp,
                                                    C.POINTER(vp)]),
+    "p25_p3_prove_air_pp": (i32, [C.POINTER(AirC), vp, vp, vp, vp, i32, i32, i32, i32, C.c_uint64, i32, vp, sz,
+                                  C.POINTER(sz), C.POINTER(P3Config)]),
+    "p25_p3_prover_create_pp": (i32, [C.POINTER(AirC), vp, vp, i32, i32, i32, i32, C.POINTER(vp)]),
+    "p25_circuit_build_p3_verifier_air_pp": (i32, [C.POINTER(P3Config), C.POINTER(AirC), vp, vp, C.POINTER(vp)]),
+    "p25_p3_preprocessed_commit": (i32, [vp, i32, i32, vp]),
+    "p25_p3_prover_preprocessed_commit": (i32, [vp, vp]),
     "p25_p3_prover_sync": (i32, [vp]),
     "p25_p3_verify_batch": (i32, [vp, vp, sz, sz, vp]),
     "p25_p3_verify_batch_dev": (i32, [vp, vp, sz, sz, vp, vp]),
@@ -507,6 +540,22 @@ def p3_prove_fibonacci(log_n=6, num_queries=100, pow_bits=16, pow_start=0, threa
     return out, cfg
 
 
+def _ref(c_struct):
+    """byref of a ctypes structure, or NULL for None."""
+    return C.byref(c_struct) if c_struct is not None else None
+
+
+def p3_preprocessed_commit(preprocessed, log_blowup=1, threads=None):
+    """The 4-word commitment of preprocessed columns uint64[2^log_n][PW] under `log_blowup` (p25_p3_preprocessed_commit):
+    verifying-key data, computed on the host."""
+    pp = Air(1, preprocessed=preprocessed).preprocessed_to_c()
+    if pp is None:
+        raise ValueError("no preprocessed columns to commit")
+    out = np.zeros(4, dtype=np.uint64)
+    _check(lib().p25_p3_preprocessed_commit(C.byref(pp), log_blowup, threads or min(16, os.cpu_count() or 1), _ptr(out)))
+    return out
+
+
 def _public_rows(public_values, n, n_public):
     """public_values -> uint64[n][n_public] (None allowed when the AIR has none)."""
     if public_values is None:
@@ -523,7 +572,7 @@ def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=
     """Native plonky3 proof of `air` (binding.Air) on `trace` (uint64[2^log_n][width]) -> (inputs, P3Config).
     log_blowup: FriConfig.log_blowup (1 = the reference's; 2 / 3 for AIRs of constraint degree up to 5 / 9).
     public_values: the air.n_public values of this proof; they end up as the last words of `inputs`.
-    An AIR with periodic columns goes through p25_p3_prove_air_pc."""
+    An AIR with periodic columns goes through p25_p3_prove_air_pc, one with preprocessed columns through p25_p3_prove_air_pp."""
     threads = threads or min(16, os.cpu_count() or 1)
     t = np.ascontiguousarray(trace, dtype=np.uint64)
     if t.ndim != 2 or t.shape[1] != air.width or t.shape[0] & (t.shape[0] - 1) or t.shape[0] < 2:
@@ -532,6 +581,13 @@ def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=
     ac = air.to_c()
     cfg = P3Config()
     pc = air.periodic_to_c()
+    pp = air.preprocessed_to_c()
+    if pp is not None:
+        pv = _public_rows(public_values, 1, air.n_public)
+        out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_pp(C.byref(ac), _ptr(t), _ptr(pv), _ref(pc), C.byref(pp), log_n,
+                                                                   log_blowup, num_queries, pow_bits, pow_start, threads, buf, cap,
+                                                                   n, C.byref(cfg)), np.uint64)
+        return out, cfg
     if pc is not None:
         pv = _public_rows(public_values, 1, air.n_public)
         out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_pc(C.byref(ac), _ptr(t), _ptr(pv), C.byref(pc), log_n, log_blowup,
@@ -558,7 +614,11 @@ class P3Prover:
         ac = air.to_c()
         h = vp()
         pc = air.periodic_to_c()
-        if pc is None:
+        pp = air.preprocessed_to_c()
+        if pp is not None:
+            _check(lib().p25_p3_prover_create_pp(C.byref(ac), _ref(pc), C.byref(pp), log_n, log_blowup, num_queries, pow_bits,
+                                                 C.byref(h)))
+        elif pc is None:
             _check(lib().p25_p3_prover_create(C.byref(ac), log_n, log_blowup, num_queries, pow_bits, C.byref(h)))
         else:
             _check(lib().p25_p3_prover_create_pc(C.byref(ac), C.byref(pc), log_n, log_blowup, num_queries, pow_bits, C.byref(h)))
@@ -627,6 +687,12 @@ class P3Prover:
         _check(lib().p25_p3_prover_scratch_bytes(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def preprocessed_commit(self):
+        """The 4-word commitment of the handle's preprocessed columns, as the handle computed it on the device."""
+        out = np.zeros(4, dtype=np.uint64)
+        _check(lib().p25_p3_prover_preprocessed_commit(self._h, _ptr(out)))
+        return out
+
     def sync(self):
         _check(lib().p25_p3_prover_sync(self._h))
 
@@ -669,6 +735,9 @@ class Circuit:
         """`builder.p3_verify_proof::<H>(proof, &air, fri_config)` for a user AIR (binding.Air)."""
         ac = air.to_c()
         pc = air.periodic_to_c()
+        pp = air.preprocessed_to_c()
+        if pp is not None:
+            return _new_circuit(lib().p25_circuit_build_p3_verifier_air_pp, C.byref(cfg), C.byref(ac), _ref(pc), C.byref(pp))
         if pc is not None:
             return _new_circuit(lib().p25_circuit_build_p3_verifier_air_pc, C.byref(cfg), C.byref(ac), C.byref(pc))
         return _new_circuit(lib().p25_circuit_build_p3_verifier_air, C.byref(cfg), C.byref(ac))

@@ -296,8 +296,10 @@ P3Config checked_p3_config(const p25_p3_config* cfg) {
   return from_c(cfg);
 }
 // `periodic`: the AIR's periodic columns (null: none), copied.  `pc_form`: set by the entry points that take no columns,
-// the name of the one that does -- they refuse an AIR that reads a column (op 7) and name it.
-AirProgram air_from_c(const p25_air* air, const p25_air_periodic* periodic = nullptr, const char* pc_form = nullptr) {
+// the name of the one that does -- they refuse an AIR that reads a column (op 7) and name it.  `prep`, `pp_form`: the same
+// for the preprocessed columns (ops 8 and 9) and the _pp entry points.
+AirProgram air_from_c(const p25_air* air, const p25_air_periodic* periodic = nullptr, const char* pc_form = nullptr,
+                      const p25_air_preprocessed* prep = nullptr, const char* pp_form = nullptr) {
   if (!air || !air->nodes || !air->constraints) throw std::invalid_argument("null AIR");
   if (air->n_nodes > (1u << 20) || air->n_constraints > (1u << 16)) throw std::invalid_argument("AIR too large");
   AirProgram p;
@@ -305,6 +307,20 @@ AirProgram air_from_c(const p25_air* air, const p25_air_periodic* periodic = nul
     for (uint32_t i = 0; i < air->n_nodes; i++)
       if (air->nodes[i].op == AirProgram::PERIODIC)
         throw std::invalid_argument(std::string("the AIR reads periodic columns (node op 7 PERIODIC): use ") + pc_form);
+  if (pp_form)
+    for (uint32_t i = 0; i < air->n_nodes; i++)
+      if (air->nodes[i].op == AirProgram::PREP_LOCAL || air->nodes[i].op == AirProgram::PREP_NEXT)
+        throw std::invalid_argument(std::string("the AIR reads preprocessed columns (node op 8 PREP_LOCAL / 9 PREP_NEXT): use ") + pp_form);
+  if (prep && prep->width) {
+    if (prep->width > (uint32_t)AirProgram::MAX_PREPROCESSED)
+      throw std::invalid_argument("AIR: more than 64 preprocessed columns (P25_AIR_MAX_PREPROCESSED)");
+    if (prep->log_n < 1 || prep->log_n > 22)
+      throw std::invalid_argument("AIR: the preprocessed columns' log_n differs from the trace's log height (log_n)");
+    if (!prep->values) throw std::invalid_argument("null preprocessed columns");
+    p.prep.width = prep->width;
+    p.prep.log_n = prep->log_n;
+    p.prep.values.assign(prep->values, prep->values + ((size_t)prep->width << prep->log_n));
+  }
   if (periodic && periodic->n_columns) {
     if (periodic->n_columns > (uint32_t)AirProgram::MAX_PERIODIC)
       throw std::invalid_argument("AIR: more than 32 periodic columns (P25_AIR_MAX_PERIODIC)");
@@ -333,7 +349,7 @@ AirProgram air_from_c(const p25_air* air, const p25_air_periodic* periodic = nul
 // proof's), without proving; otherwise prove() completes pc and returns the inputs.
 template <class F>
 p25_status p3_prove_out(const P3ProveParams& prm, P3Config& pc, F&& prove, uint64_t* inputs_out, size_t cap, size_t* n_out,
-                        p25_p3_config* cfg_out, size_t n_public = 0) {
+                        p25_p3_config* cfg_out, size_t n_public = 0 /* and the words of the preprocessed columns */) {
   if (!inputs_out) {
     if (prm.log_n < 1 || prm.log_n > 22 || prm.num_queries < 1) throw std::invalid_argument("bad parameters");
     *n_out = pc.num_inputs() + n_public;
@@ -612,13 +628,16 @@ p25_status p25_circuit_build_p3_verifier(const p25_p3_config* cfg, int32_t air, 
     return build_verifier(cfg, fib, out);
   });
 }
-// p25_circuit_build_p3_verifier_air (pc_form false: refuses an AIR that reads periodic columns) and its _pc form
-static p25_status p3_build_verifier_air(bool pc_form, const p25_p3_config* cfg, const p25_air* air,
-                                        const p25_air_periodic* periodic, p25_circuit** out) {
+// p25_circuit_build_p3_verifier_air (form 0: refuses an AIR that reads periodic or preprocessed columns), its _pc form
+// (1: refuses preprocessed columns) and its _pp form (2)
+static p25_status p3_build_verifier_air(int form, const p25_p3_config* cfg, const p25_air* air,
+                                        const p25_air_periodic* periodic, const p25_air_preprocessed* prep, p25_circuit** out) {
   return host_guarded([&]() -> p25_status {
     if (!cfg || !air || !out) throw std::invalid_argument("null argument");
-    AirProgram prog = air_from_c(air, periodic, pc_form ? nullptr : "p25_circuit_build_p3_verifier_air_pc");
+    AirProgram prog = air_from_c(air, periodic, form >= 1 ? nullptr : "p25_circuit_build_p3_verifier_air_pc", prep,
+                                 form >= 2 ? nullptr : "p25_circuit_build_p3_verifier_air_pp");
     prog.check_periodic(cfg->log_trace_height);
+    prog.check_preprocessed(cfg->log_trace_height);
     // the chunk count follows from the AIR (uni-stark get_log_quotient_degree): the shape must say the same
     if (prog.log_quotient_degree() != cfg->log_quotient_degree)
       throw std::invalid_argument("an AIR of constraint degree " + std::to_string(prog.max_constraint_degree()) + " has 2^" +
@@ -628,11 +647,15 @@ static p25_status p3_build_verifier_air(bool pc_form, const p25_p3_config* cfg, 
   });
 }
 p25_status p25_circuit_build_p3_verifier_air(const p25_p3_config* cfg, const p25_air* air, p25_circuit** out) {
-  return p3_build_verifier_air(false, cfg, air, nullptr, out);
+  return p3_build_verifier_air(0, cfg, air, nullptr, nullptr, out);
 }
 p25_status p25_circuit_build_p3_verifier_air_pc(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
                                                 p25_circuit** out) {
-  return p3_build_verifier_air(true, cfg, air, periodic, out);
+  return p3_build_verifier_air(1, cfg, air, periodic, nullptr, out);
+}
+p25_status p25_circuit_build_p3_verifier_air_pp(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
+                                                const p25_air_preprocessed* preprocessed, p25_circuit** out) {
+  return p3_build_verifier_air(2, cfg, air, periodic, preprocessed, out);
 }
 
 p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t num_queries,
@@ -641,15 +664,18 @@ p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t l
   return p25_p3_prove_air_ex(air, trace, log_n, 1, num_queries, pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
 // p25_p3_prove_air_ex (pv_form false: refuses an AIR with public values), p25_p3_prove_air_pv and p25_p3_prove_air_pc
-// (pc_form: the name of the form that takes periodic columns, for the two that do not and refuse an AIR reading one)
-static p25_status p3_prove_air_host(bool pv_form, const char* pc_form, const p25_air* air, const uint64_t* trace,
-                                    const uint64_t* public_values, const p25_air_periodic* periodic,
+// (pc_form: the name of the form that takes periodic columns, for the two that do not and refuse an AIR reading one;
+// pp_form: the same for preprocessed columns, null in p25_p3_prove_air_pp alone)
+static p25_status p3_prove_air_host(bool pv_form, const char* pc_form, const char* pp_form, const p25_air* air,
+                                    const uint64_t* trace, const uint64_t* public_values, const p25_air_periodic* periodic,
+                                    const p25_air_preprocessed* prep,
                                     int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start,
                                     int32_t threads, uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out) {
   return host_guarded([&]() -> p25_status {
     if (!air || !n_out) throw std::invalid_argument("null argument");
-    AirProgram prog = air_from_c(air, periodic, pc_form);
+    AirProgram prog = air_from_c(air, periodic, pc_form, prep, pp_form);
     prog.check_periodic(log_n);
+    prog.check_preprocessed(log_n);
     if (!pv_form && prog.n_public > 0)
       throw std::invalid_argument("the AIR has public values (n_public > 0): use p25_p3_prove_air_pv");
     if (log_blowup < 1 || log_blowup > 4) throw std::invalid_argument("log_blowup must be 1..4");
@@ -674,35 +700,63 @@ static p25_status p3_prove_air_host(bool pv_form, const char* pc_form, const p25
         throw std::invalid_argument(e.what());
       }
     };
-    return p3_prove_out(prm, pc, prove, inputs_out, cap, n_out, cfg_out, (size_t)prog.n_public);
+    return p3_prove_out(prm, pc, prove, inputs_out, cap, n_out, cfg_out,
+                        (size_t)prog.n_public + p3_preprocessed_words((int)prog.prep.width, log_n, log_blowup, num_queries));
   });
 }
 p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t log_blowup, int32_t num_queries,
                                int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
                                size_t* n_out, p25_p3_config* cfg_out) {
-  return p3_prove_air_host(false, "p25_p3_prove_air_pc", air, trace, nullptr, nullptr, log_n, log_blowup, num_queries, pow_bits,
+  return p3_prove_air_host(false, "p25_p3_prove_air_pc", "p25_p3_prove_air_pp", air, trace, nullptr, nullptr, nullptr, log_n, log_blowup, num_queries, pow_bits,
                            pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
 p25_status p25_p3_prove_air_pv(const p25_air* air, const uint64_t* trace, const uint64_t* public_values, int32_t log_n,
                                int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start, int32_t threads,
                                uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out) {
-  return p3_prove_air_host(true, "p25_p3_prove_air_pc", air, trace, public_values, nullptr, log_n, log_blowup, num_queries,
+  return p3_prove_air_host(true, "p25_p3_prove_air_pc", "p25_p3_prove_air_pp", air, trace, public_values, nullptr, nullptr, log_n, log_blowup, num_queries,
                            pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
 p25_status p25_p3_prove_air_pc(const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
                                const p25_air_periodic* periodic, int32_t log_n, int32_t log_blowup, int32_t num_queries,
                                int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
                                size_t* n_out, p25_p3_config* cfg_out) {
-  return p3_prove_air_host(true, nullptr, air, trace, public_values, periodic, log_n, log_blowup, num_queries, pow_bits,
-                           pow_start, threads, inputs_out, cap, n_out, cfg_out);
+  return p3_prove_air_host(true, nullptr, "p25_p3_prove_air_pp", air, trace, public_values, periodic, nullptr, log_n, log_blowup,
+                           num_queries, pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
+}
+p25_status p25_p3_prove_air_pp(const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
+                               const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed, int32_t log_n,
+                               int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start, int32_t threads,
+                               uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out) {
+  return p3_prove_air_host(true, nullptr, nullptr, air, trace, public_values, periodic, preprocessed, log_n, log_blowup,
+                           num_queries, pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
+}
+p25_status p25_p3_preprocessed_commit(const p25_air_preprocessed* preprocessed, int32_t log_blowup, int32_t threads,
+                                      uint64_t commit_out[4]) {
+  return host_guarded([&]() -> p25_status {
+    if (!preprocessed || !commit_out) throw std::invalid_argument("null argument");
+    if (!preprocessed->width || preprocessed->width > (uint32_t)AirProgram::MAX_PREPROCESSED)
+      throw std::invalid_argument("preprocessed columns: width must be 1..64 (P25_AIR_MAX_PREPROCESSED)");
+    if (preprocessed->log_n < 1 || preprocessed->log_n > 22) throw std::invalid_argument("preprocessed columns: log_n must be 1..22");
+    if (!preprocessed->values) throw std::invalid_argument("null preprocessed columns");
+    AirProgram::Preprocessed pp;
+    pp.width = preprocessed->width;
+    pp.log_n = preprocessed->log_n;
+    pp.values.assign(preprocessed->values, preprocessed->values + ((size_t)pp.width << pp.log_n));
+    const std::array<u64, 4> root = p3_preprocessed_commit(pp, log_blowup, threads);
+    for (int i = 0; i < 4; i++) commit_out[i] = root[i];
+    return P25_OK;
+  });
 }
 
 // ---- the plonky3 prover on the device -------------------------------------------------------------------------------
-static p25_status p3_prover_create(bool pc_form, const p25_air* air, const p25_air_periodic* periodic, int32_t log_n,
-                                   int32_t log_blowup, int32_t num_queries, int32_t pow_bits, p25_p3_prover** out) {
+// form: 0 p25_p3_prover_create, 1 its _pc form, 2 its _pp form (as p3_build_verifier_air)
+static p25_status p3_prover_create(int form, const p25_air* air, const p25_air_periodic* periodic,
+                                   const p25_air_preprocessed* prep, int32_t log_n, int32_t log_blowup, int32_t num_queries,
+                                   int32_t pow_bits, p25_p3_prover** out) {
   return host_guarded([&]() -> p25_status {
     if (!air || !out) throw std::invalid_argument("null argument");
-    const AirProgram prog = air_from_c(air, periodic, pc_form ? nullptr : "p25_p3_prover_create_pc");
+    const AirProgram prog = air_from_c(air, periodic, form >= 1 ? nullptr : "p25_p3_prover_create_pc", prep,
+                                       form >= 2 ? nullptr : "p25_p3_prover_create_pp");
     std::unique_ptr<p25_p3_prover> h(new p25_p3_prover());
     h->dev.reset(new P3ProverDev(prog, log_n, log_blowup, num_queries, pow_bits));
     *out = h.release();
@@ -711,11 +765,27 @@ static p25_status p3_prover_create(bool pc_form, const p25_air* air, const p25_a
 }
 p25_status p25_p3_prover_create(const p25_air* air, int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits,
                                 p25_p3_prover** out) {
-  return p3_prover_create(false, air, nullptr, log_n, log_blowup, num_queries, pow_bits, out);
+  return p3_prover_create(0, air, nullptr, nullptr, log_n, log_blowup, num_queries, pow_bits, out);
 }
 p25_status p25_p3_prover_create_pc(const p25_air* air, const p25_air_periodic* periodic, int32_t log_n, int32_t log_blowup,
                                    int32_t num_queries, int32_t pow_bits, p25_p3_prover** out) {
-  return p3_prover_create(true, air, periodic, log_n, log_blowup, num_queries, pow_bits, out);
+  return p3_prover_create(1, air, periodic, nullptr, log_n, log_blowup, num_queries, pow_bits, out);
+}
+p25_status p25_p3_prover_create_pp(const p25_air* air, const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed,
+                                   int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits, p25_p3_prover** out) {
+  return p3_prover_create(2, air, periodic, preprocessed, log_n, log_blowup, num_queries, pow_bits, out);
+}
+p25_status p25_p3_prover_preprocessed_commit(p25_p3_prover* p, uint64_t commit_out[4]) {
+  return host_guarded([&]() -> p25_status {
+    if (!p || !commit_out) throw std::invalid_argument("null argument");
+    if (!p->dev->preprocessed_width())
+      throw std::invalid_argument("p25_p3_prover_preprocessed_commit: the prover's AIR has no preprocessed columns");
+    const p25_status s = ensure_device();
+    if (s != P25_OK) return s;
+    P25_LOCK(p);
+    p->dev->preprocessed_commit(commit_out);
+    return P25_OK;
+  });
 }
 void p25_p3_prover_destroy(p25_p3_prover* p) { delete p; }
 p25_status p25_p3_prover_config(const p25_p3_prover* p, p25_p3_config* cfg_out, size_t* num_inputs_out) {

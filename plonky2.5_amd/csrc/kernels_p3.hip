@@ -202,6 +202,8 @@ __global__ __launch_bounds__(64) void k_p3_chain(P3Shape sh, P3Bufs b, uint32_t 
       u64* dst = hdr + 4 * phase;
       if (lane < 4) dst[lane] = root[lane];
       ch.observe_digest(root);
+      // the preprocessed commitment (the handle's shared tree: no group offset), directly behind the trace root
+      if (phase == P3_CH_TRACE && sh.PW) ch.observe_digest(b.ptree + p3_level_off(N2, sh.L));
       if (phase == P3_CH_TRACE) {   // the proof's public values, between the trace root and alpha (p3_prover.cpp)
         const u64* pub = b.pub + (size_t)g * sh.n_public;
         for (uint32_t i = 0; i < sh.n_public; i++) ch.observe(pub[i]);
@@ -226,7 +228,7 @@ __global__ __launch_bounds__(64) void k_p3_chain(P3Shape sh, P3Bufs b, uint32_t 
         st_e2(s->fri_alpha, fa);
         u64* ap = hdr + sh.o_apow;
         E2 p = gl::e2(1);
-        for (uint32_t i = 0; i < 2 * sh.W + 2 * sh.Q; i++) {
+        for (uint32_t i = 0; i < 2 * sh.W + 2 * sh.Q + 2 * sh.PW; i++) {
           st_e2(ap + 2 * i, p);
           p = gl::mul(p, fa);
         }
@@ -236,7 +238,7 @@ __global__ __launch_bounds__(64) void k_p3_chain(P3Shape sh, P3Bufs b, uint32_t 
     case P3_CH_FRI_ROUND: {
       const size_t h = N2 >> (round + 1);
       const u64* root = b.ftrees + (size_t)g * 8 * N2 + p3_ftree_off(N2, round) + p3_level_off(h, sh.L - round - 1);
-      u64* dst = hdr + 8 + 4 * sh.W + 4 * sh.Q + 4 * round;
+      u64* dst = hdr + sh.o_fri + 4 * round;
       if (lane < 4) dst[lane] = root[lane];
       ch.observe_digest(root);
       const E2 beta = ch.sample_ext();
@@ -285,7 +287,10 @@ __global__ __launch_bounds__(256) void k_p3_quotient(P3Shape sh, P3Bufs b) {
   const u64 is_trans = gl::sub(x, sh.g_inv);
   const u64 sel[4] = {0, gl::mul(zhx, gl::inv(gl::sub(x, 1))), gl::mul(zhx, gl::inv(is_trans)), is_trans};
   const E2 alpha = ld_e2(b.state[g].alpha);
-  auto load = [&](int next, uint32_t c) -> u64 { return lde[(size_t)c * N2 + (next ? pos1 : p)]; };
+  // the preprocessed columns: the handle's shared LDE at the same two positions
+  auto load = [&](int which, uint32_t c) -> u64 {
+    return ((which & 2) ? b.plde : lde)[(size_t)c * N2 + ((which & 1) ? pos1 : p)];
+  };
   // A periodic column at x_j: its table by j mod (P Q) -- the NATURAL index j, whose low bits are the reversed top bits of
   // p.  256 consecutive p share their top bits once n >= 256 P, so a block then reads one word: a plain load.
   const u64* ptab = b.consts + sh.per_tab;
@@ -300,7 +305,8 @@ __global__ __launch_bounds__(256) void k_p3_quotient(P3Shape sh, P3Bufs b) {
   dst[n] = q.b;
 }
 
-// Openings: job < W: trace column at zeta; < 2 W: at zeta w_n; then the chunk components at zeta / s_c.  Lane t sums the
+// Openings: job < W: trace column at zeta; < 2 W: at zeta w_n; then the chunk components at zeta / s_c; then the shared
+// preprocessed columns at this proof's zeta and zeta w_n, behind the chunk openings.  Lane t sums the
 // coefficients t, t + 1024, ... by Horner in x^1024, scales by x^t; the block adds up.
 __global__ __launch_bounds__(1024) void k_p3_eval(P3Shape sh, P3Bufs b) {
   P25_WAVE_PRIO(P25_PRIO_BULK);
@@ -313,6 +319,10 @@ __global__ __launch_bounds__(1024) void k_p3_eval(P3Shape sh, P3Bufs b) {
   if (job < 2 * sh.W) {
     c = b.tcoef + ((size_t)g * sh.W + (job % sh.W)) * n;
     x = ld_e2(hdr + sh.o_points + 2 * (job / sh.W));
+  } else if (job >= 2 * sh.W + 2 * sh.Q) {
+    const uint32_t pj = job - 2 * sh.W - 2 * sh.Q;
+    c = b.pcoef + (size_t)(pj % sh.PW) * n;
+    x = ld_e2(hdr + sh.o_points + 2 * (pj / sh.PW));
   } else {
     const uint32_t q = job - 2 * sh.W;
     c = b.qcoef + (((size_t)(q >> 1) * sh.G + g) * 2 + (q & 1)) * n;
@@ -352,7 +362,10 @@ __global__ __launch_bounds__(64) void k_p3_identity(P3Shape sh, P3Bufs b) {
   const E2 z_h = gl::sub(gl::exp_pow2(zeta, sh.k), gl::e2(1));
   const E2 is_trans = gl::sub(zeta, gl::e2(sh.g_inv));
   const E2 sel[4] = {gl::e2(0), gl::mul(z_h, gl::inv(gl::sub(zeta, gl::e2(1)))), gl::mul(z_h, gl::inv(is_trans)), is_trans};
-  auto load = [&](int next, uint32_t c) -> E2 { return ld_e2(open + 2 * ((next ? sh.W : 0) + c)); };
+  const u64* popen = open + 4 * sh.W + 4 * sh.Q;   // the preprocessed openings, behind the chunks'
+  auto load = [&](int which, uint32_t c) -> E2 {
+    return (which & 2) ? ld_e2(popen + 2 * (((which & 1) ? sh.PW : 0) + c)) : ld_e2(open + 2 * (((which & 1) ? sh.W : 0) + c));
+  };
   const u64* pcoef = b.consts + sh.per_coef;
   auto per = [&](uint32_t i) -> E2 { return p3_periodic_at(pcoef + p3_per_offset(i), p3_per_log_period(i), sh.k, zeta); };
   const E2 acc = run_air<ExtF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, load, per, sel, alpha);
@@ -394,6 +407,13 @@ __global__ __launch_bounds__(256) void k_p3_reduced(P3Shape sh, P3Bufs b) {
   for (uint32_t c = 0; c < Q2; c++) {
     const E2 v = gl::e2(b.qlde[(((size_t)(c >> 1) * sh.G + g) * 2 + (c & 1)) * N2 + i]);
     s_z = gl::add(s_z, gl::mul(ld_e2(ap + 2 * (2 * W + c)), gl::sub(v, ld_e2(open + 2 * (2 * W + c)))));
+  }
+  // the third batch: the preprocessed matrix at zeta, then at zeta w_n; the powers go on behind the chunks'
+  for (uint32_t c = 0; c < sh.PW; c++) {
+    const E2 v = gl::e2(b.plde[(size_t)c * N2 + i]);
+    const uint32_t t0 = 2 * W + Q2 + c, t1 = t0 + sh.PW;
+    s_z = gl::add(s_z, gl::mul(ld_e2(ap + 2 * t0), gl::sub(v, ld_e2(open + 2 * t0))));
+    s_zn = gl::add(s_zn, gl::mul(ld_e2(ap + 2 * t1), gl::sub(v, ld_e2(open + 2 * t1))));
   }
   st_e2(b.layers + (size_t)g * 4 * N2 + 2 * i, gl::add(gl::mul(s_z, inv_z), gl::mul(s_zn, inv_zn)));
 }
@@ -451,7 +471,7 @@ __global__ __launch_bounds__(1024) void k_p3_fri_tail(P3Shape sh, P3Bufs b) {
     }
     if (tid < 64) {
       const u64* root = tree + p3_level_off(h, n_levels);
-      u64* dst = hdr + 8 + 4 * sh.W + 4 * sh.Q + 4 * r;
+      u64* dst = hdr + sh.o_fri + 4 * r;
       if (lane < 4) dst[lane] = root[lane];
       ch.observe_digest(root);
       const E2 beta = ch.sample_ext();
@@ -498,7 +518,8 @@ __global__ __launch_bounds__(256) void k_p3_pow_search(P3Shape sh, P3Bufs b, con
   }
 }
 
-// Flattening (p3_prover.cpp:423-445).  Block q of a proof writes query q's two sections, block 0 the fixed words and the
+// Flattening (p3_prover.cpp:423-445).  Block q of a proof writes query q's two sections (the second ends in the third
+// batch, row and path from the handle's shared LDE and tree, for an AIR with preprocessed columns), block 0 the fixed words and the
 // public values behind the last query's section as well.  A failed proof's words are zeros, that tail included.
 __global__ __launch_bounds__(64) void k_p3_gather(P3Shape sh, P3Bufs b, u64* __restrict__ out_base, size_t out_stride,
                                                   uint32_t* __restrict__ d_status) {
@@ -566,6 +587,15 @@ __global__ __launch_bounds__(64) void k_p3_gather(P3Shape sh, P3Bufs b, u64* __r
       const uint32_t l = e >> 2;
       w[e] = qt[p3_level_off(N2, l) + 4 * (((size_t)ix >> l) ^ 1) + (e & 3)];
     }
+    if (sh.PW) {
+      w += 4 * sh.L;
+      for (uint32_t c = t; c < sh.PW; c += 64) w[c] = b.plde[(size_t)c * N2 + ix];
+      w += sh.PW;
+      for (uint32_t e = t; e < 4 * sh.L; e += 64) {
+        const uint32_t l = e >> 2;
+        w[e] = b.ptree[p3_level_off(N2, l) + 4 * (((size_t)ix >> l) ^ 1) + (e & 3)];
+      }
+    }
   }
 }
 
@@ -615,7 +645,7 @@ void p3_launch_quotient(const P3Shape& s, const P3Bufs& b, hipStream_t st) {
   hipLaunchKernelGGL(k_p3_quotient, dim3((unsigned)((nq + 255) / 256), s.G), dim3(256), 0, st, s, b);
 }
 void p3_launch_openings(const P3Shape& s, const P3Bufs& b, hipStream_t st) {
-  hipLaunchKernelGGL(k_p3_eval, dim3(2 * s.W + 2 * s.Q, s.G), dim3(1024), 0, st, s, b);
+  hipLaunchKernelGGL(k_p3_eval, dim3(2 * s.W + 2 * s.Q + 2 * s.PW, s.G), dim3(1024), 0, st, s, b);
   hipLaunchKernelGGL(k_p3_identity, dim3((s.G + 63) / 64), dim3(64), 0, st, s, b);
 }
 void p3_launch_reduced(const P3Shape& s, const P3Bufs& b, hipStream_t st) {

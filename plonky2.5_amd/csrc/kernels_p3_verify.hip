@@ -92,6 +92,8 @@ __global__ __launch_bounds__(64) void k_p3v_transcript(P3VerifyArgs a) {
     }
   };
   ch.observe_digest(proof);
+  if (a.PW)   // the handle's preprocessed commitment: one address for the whole grid
+    for (int j = 0; j < 4; j++) ch.observe(a.prep_root[j]);
   for (uint32_t i = 0; i < a.n_public; i++) ch.observe(proof[a.o_public + i]);   // one address per group: the value is uniform in it
   draw(P3VC_ALPHA, 2);
   ch.observe_digest(proof + 4);
@@ -128,10 +130,12 @@ __global__ __launch_bounds__(64) void k_p3v_fold(P3VerifyArgs a) {
   if (key != P3VKEY_NONE) atomicMin(a.status + p, key);
 }
 
-__global__ __launch_bounds__(64) void k_p3v_merkle(P3VerifyArgs a) {
+// Five waves per SIMD stated, not left to the scheduler: with the third tree kind in the lane function it settles on 112
+// registers (four waves) unasked, and on the 93 it took before (no scratch) when asked.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void k_p3v_merkle(P3VerifyArgs a) {
   const size_t per_tree = (size_t)a.n_proofs * a.num_queries;
   const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= per_tree * (2 + a.k)) return;
+  if (gid >= per_tree * (a.nb + a.k)) return;
   const uint32_t p = (uint32_t)((gid % per_tree) / a.num_queries);
   const uint32_t key = p3vlane::merkle_lane(a, (uint32_t)(gid / per_tree), p, (uint32_t)(gid % a.num_queries));   // task-major
   if (key != P3VKEY_NONE) atomicMin(a.status + p, key);
@@ -149,7 +153,7 @@ void launch_p3_verify(const P3VerifyArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_p3v_transcript, dim3(blocks_of(a.n_proofs, PROOFS_PER_WAVE)), dim3(64), 0, st, a);
   hipLaunchKernelGGL(k_p3v_identity, dim3(blocks_of(a.n_proofs, 64)), dim3(64), 0, st, a);
   hipLaunchKernelGGL(k_p3v_fold, dim3(blocks_of(pq, 64)), dim3(64), 0, st, a);
-  hipLaunchKernelGGL(k_p3v_merkle, dim3(blocks_of(pq * (2 + a.k), 64)), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_p3v_merkle, dim3(blocks_of(pq * (a.nb + a.k), 64)), dim3(64), 0, st, a);
   hipLaunchKernelGGL(k_p3v_verdict, dim3(blocks_of(a.n_proofs, 64)), dim3(64), 0, st, a);
 }
 

@@ -38,7 +38,8 @@ GL_HD gl::E2 p3_periodic_at(const u64* __restrict__ coef, uint32_t lp, uint32_t 
   }
   return acc;
 }
-// Runs the register program: `load(next, column)` reads the row, `per(index)` gives the periodic column of a
+// Runs the register program: `load(which, column)` reads the row (which: P3_LOAD_*, the trace's or the preprocessed matrix's,
+// current or next), `per(index)` gives the periodic column of a
 // P3_OPND_PERIODIC operand (p3_per_log_period, p3_per_offset of its index) at the caller's point, `pub` is the proof's own
 // row of public values (read only by P3_OPND_PUBLIC operands: may be null without them), the constraints are folded in
 // program order.
@@ -51,8 +52,10 @@ GL_HD gl::E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u
     const uint32_t kind = o >> 28, i = o & 0x0fffffffu;
     switch (kind) {
       case P3_OPND_SLOT: return slot[i];
-      case P3_OPND_LOCAL: return load(0, i);
-      case P3_OPND_NEXT: return load(1, i);
+      case P3_OPND_LOCAL: return load(P3_LOAD_LOCAL, i);
+      case P3_OPND_NEXT: return load(P3_LOAD_NEXT, i);
+      case P3_OPND_PREP_LOCAL: return load(P3_LOAD_PREP_LOCAL, i);
+      case P3_OPND_PREP_NEXT: return load(P3_LOAD_PREP_NEXT, i);
       case P3_OPND_PUBLIC: return F::cst(pub[i]);
       case P3_OPND_PERIODIC: return per(i);
       default: return F::cst(consts[i]);

@@ -381,13 +381,13 @@ void FibonacciAir::eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) co
 
 // ---------------------------------------------------------------- AIR programs
 // Nodes refer to earlier nodes only (validate), so one pass in index order has every operand's degree at hand.  CONST and
-// PUBLIC are the degree-0 leaves, a PERIODIC column has degree n - n/P <= n - 1 and counts as 1 like LOCAL; a product's
-// degree saturates, so that no chain of squarings wraps it.
+// PUBLIC are the degree-0 leaves, a PERIODIC column has degree n - n/P <= n - 1 and counts as 1 like LOCAL, a preprocessed
+// column (PREP_LOCAL, PREP_NEXT) is a polynomial of degree < n exactly as a trace column is; a product's degree saturates, so that no chain of squarings wraps it.
 std::vector<int> AirProgram::node_degrees() const {
   std::vector<int> deg(nodes.size(), 0);
   for (size_t k = 0; k < nodes.size(); k++) {
     const Node& nd = nodes[k];
-    if (nd.op == LOCAL || nd.op == NEXT || nd.op == PERIODIC) deg[k] = 1;
+    if (nd.op == LOCAL || nd.op == NEXT || nd.op == PERIODIC || nd.op == PREP_LOCAL || nd.op == PREP_NEXT) deg[k] = 1;
     else if (nd.op == CONST || nd.op == PUBLIC) deg[k] = 0;
     else if (nd.op == MUL) deg[k] = std::min(deg[nd.a] + deg[nd.b], DEGREE_SAT);
     else deg[k] = std::max(deg[nd.a], deg[nd.b]);
@@ -405,13 +405,24 @@ void AirProgram::validate() const {
     for (u64 v : pc.values)
       if (v >= gl::P) throw std::invalid_argument("AIR: non-canonical periodic value (>= p)");
   }
+  if (prep.width > (uint32_t)MAX_PREPROCESSED)
+    throw std::invalid_argument("AIR: more than 64 preprocessed columns (P25_AIR_MAX_PREPROCESSED)");
+  if (prep.width) {
+    if (prep.log_n < 1 || prep.log_n > 22) throw std::invalid_argument("AIR: the preprocessed columns' log_n must be the trace's log height");
+    if (prep.values.size() != ((size_t)prep.width << prep.log_n))
+      throw std::invalid_argument("AIR: the preprocessed matrix holds 2^log_n rows of `width` values");
+    for (u64 v : prep.values)
+      if (v >= gl::P) throw std::invalid_argument("AIR: non-canonical preprocessed value (>= p)");
+  }
   if (nodes.empty() || constraints.empty()) throw std::invalid_argument("AIR: empty program");
   for (size_t i = 0; i < nodes.size(); i++) {
     const Node& nd = nodes[i];
-    if (nd.op > PERIODIC) throw std::invalid_argument("AIR: unknown node op");
+    if (nd.op > PREP_NEXT) throw std::invalid_argument("AIR: unknown node op");
     if ((nd.op == LOCAL || nd.op == NEXT) && nd.a >= (uint32_t)width) throw std::invalid_argument("AIR: column out of range");
     if (nd.op == PUBLIC && nd.a >= (uint32_t)n_public) throw std::invalid_argument("AIR: public value index >= n_public");
     if (nd.op == PERIODIC && nd.a >= periodic.size()) throw std::invalid_argument("AIR: periodic column index >= n_columns");
+    if ((nd.op == PREP_LOCAL || nd.op == PREP_NEXT) && nd.a >= prep.width)
+      throw std::invalid_argument("AIR: preprocessed column index >= width");
     if (nd.op >= ADD && nd.op <= MUL && (nd.a >= i || nd.b >= i)) throw std::invalid_argument("AIR: node refers to a later node");
     if (nd.op == CONST && nd.value >= gl::P) throw std::invalid_argument("AIR: non-canonical constant");
   }
@@ -430,6 +441,10 @@ void AirProgram::check_periodic(int log_n) const {
   for (const Periodic& pc : periodic)
     if ((int)pc.log_period > log_n)
       throw std::invalid_argument("AIR: a periodic column's log_period exceeds the trace's log height (log_n)");
+}
+void AirProgram::check_preprocessed(int log_n) const {
+  if (prep.width && (int)prep.log_n != log_n)
+    throw std::invalid_argument("AIR: the preprocessed columns' log_n differs from the trace's log height (log_n)");
 }
 // q's coefficients: the inverse transform over <w_P>, a_i = 1/P sum_j v_j w_P^(-i j).  P <= 256: the plain sum will do.
 std::vector<u64> AirProgram::periodic_coefficients(size_t c) const {
@@ -479,6 +494,9 @@ struct CircuitExtOps {
   CircuitBuilder& cb;
   const std::vector<Ext>& public_values;
   const std::vector<Ext>& periodic;
+  const std::vector<Ext>&prep_l, &prep_n;
+  Ext prep_local(uint32_t c) { return prep_l.at(c); }
+  Ext prep_next(uint32_t c) { return prep_n.at(c); }
   Ext cst(u64 v) { return p3_field_to_arr(cb, p3_constant(cb, v)); }
   Ext pub(uint32_t i) { return public_values.at(i); }
   Ext per(uint32_t c) { return periodic.at(c); }
@@ -504,7 +522,7 @@ std::vector<Ext> ProgramAir::periodic_at(CircuitBuilder& cb, const Ext& zeta, in
   return out;
 }
 void ProgramAir::eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const {
-  CircuitExtOps ops{cb, folder.public_values, folder.periodic};
+  CircuitExtOps ops{cb, folder.public_values, folder.periodic, folder.prep_local, folder.prep_next};
   const Ext sel[4] = {Ext{}, folder.is_first_row, folder.is_last_row, folder.is_transition};
   prog.fold<Ext>(folder.trace_local, folder.trace_next, sel, ops, [&](const Ext& c) { folder.assert_zero(cb, c); });
 }
@@ -524,7 +542,9 @@ size_t P3Config::num_inputs() const {
         (chunks * opening_proof_query_openings_opened_values_length + 4 * opening_matrix_log_max_height));
   return n;
 }
-static P3ProofTarget add_virtual_proof(CircuitBuilder& cb, const P3Config& cfg) {
+// prep_width: the AIR's preprocessed columns (0: the reference's proof).  Their openings stand behind the chunk openings
+// and their batch is every query's third.
+static P3ProofTarget add_virtual_proof(CircuitBuilder& cb, const P3Config& cfg, int prep_width) {
   std::vector<Target>& in = cb.input_targets;
   auto vt = [&]() {
     Target t = cb.add_virtual_target();
@@ -543,6 +563,8 @@ static P3ProofTarget add_virtual_proof(CircuitBuilder& cb, const P3Config& cfg) 
     Ext b = vext();
     p.quotient_chunks.push_back({a, b});
   }
+  for (int i = 0; i < prep_width; i++) p.prep_local.push_back(vext());
+  for (int i = 0; i < prep_width; i++) p.prep_next.push_back(vext());
   for (int i = 0; i < cfg.log_trace_height; i++) p.commit_phase_commits.push_back(v4());
   for (int q = 0; q < cfg.fri_config.num_queries; q++) {
     std::vector<P3CommitPhaseStep> steps;
@@ -557,10 +579,11 @@ static P3ProofTarget add_virtual_proof(CircuitBuilder& cb, const P3Config& cfg) 
   p.final_poly = vext();
   p.pow_witness = vt();
   for (int q = 0; q < cfg.fri_config.num_queries; q++) {
-    std::array<P3BatchOpening, 2> bo;
-    int widths[2] = {cfg.trace_width, cfg.opening_proof_query_openings_opened_values_length};
-    for (int b = 0; b < 2; b++) {
-      const int mats = b == 0 ? 1 : (1 << cfg.log_quotient_degree);   // batch 1: one matrix per quotient chunk
+    const int n_batches = prep_width ? 3 : 2;
+    std::vector<P3BatchOpening> bo(n_batches);
+    int widths[3] = {cfg.trace_width, cfg.opening_proof_query_openings_opened_values_length, prep_width};
+    for (int b = 0; b < n_batches; b++) {
+      const int mats = b == 1 ? (1 << cfg.log_quotient_degree) : 1;   // batch 1: one matrix per quotient chunk
       for (int m = 0; m < mats; m++) {
         std::vector<Target> row;
         for (int i = 0; i < widths[b]; i++) row.push_back(vt());
@@ -660,7 +683,7 @@ void p3_verify_opening_proof(CircuitBuilder& cb, const P3FriConfig& config,
     for (auto& e : ro) e = Ext{cb.zero(), cb.zero()};
     Ext one = p3_ext_one(cb);
     std::vector<Ext> alpha_pow(32, one);
-    for (size_t b = 0; b < 2 && b < commits_and_points.size(); b++) {
+    for (size_t b = 0; b < query_opening.size() && b < commits_and_points.size(); b++) {
       const P3BatchOpening& batch_opening = query_opening[b];
       const CommitAndPoints& cp = commits_and_points[b];
       std::vector<Dimensions> batch_dims;
@@ -712,7 +735,8 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
     auto st = p3_arr12(cb);
     challenger.sponge_state.assign(st.begin(), st.end());
   }
-  P3ProofTarget proof = add_virtual_proof(cb, config);
+  const int prep_width = air.preprocessed_width();
+  P3ProofTarget proof = add_virtual_proof(cb, config, prep_width);
   // The proof's public values: input targets behind the proof's words (the tail of the flat input), exposed as the
   // circuit's public inputs.  None for the reference's AIRs, whose circuit this leaves as it was.
   std::vector<Target> public_values;
@@ -755,6 +779,14 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
   if (!valid_shape) throw std::logic_error("Invalid Proof Shape");  // verifier.rs:131-133
 
   p3_observe(cb, challenger, proof.trace_commit.begin(), proof.trace_commit.end());
+  // the preprocessed commitment: verifying-key data, four constants, observed directly behind the trace commitment as
+  // uni-stark observes it (unpinned: include/p25.h "PREPROCESSED COLUMNS").  No gate for an AIR without such columns.
+  std::array<Target, 4> prep_commit{};
+  if (prep_width) {
+    const std::array<u64, 4> root = air.preprocessed_commit(degree_bits, config.fri_config.log_blowup);
+    for (int i = 0; i < 4; i++) prep_commit[i] = p3_constant(cb, root[i]);
+    p3_observe(cb, challenger, prep_commit.begin(), prep_commit.end());
+  }
   // uni-stark's `challenger.observe_slice(public_values)`: between the trace commitment and alpha (unpinned: include/p25.h)
   p3_observe(cb, challenger, public_values.begin(), public_values.end());
   Ext alpha = p3_sample_ext(cb, challenger);
@@ -768,6 +800,11 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
   cps[1].commit = proof.quotient_commit;
   for (size_t i = 0; i < quotient_chunks_domains.size() && i < proof.quotient_chunks.size(); i++)
     cps[1].mats.push_back(MatPoints{quotient_chunks_domains[i], {{zeta, proof.quotient_chunks[i]}}});
+  if (prep_width) {   // the third batch: the trace's height, so it shares the trace's log_height slot of the reduced openings
+    cps.resize(3);
+    cps[2].commit = prep_commit;
+    cps[2].mats.push_back(MatPoints{trace_domain, {{zeta, proof.prep_local}, {zeta_next, proof.prep_next}}});
+  }
   p3_verify_opening_proof(cb, config.fri_config, cps, proof, challenger);
 
   // zps (verifier.rs:169-198)
@@ -815,6 +852,8 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
   VerifierConstraintFolder folder;
   folder.trace_local = proof.trace_local;
   folder.trace_next = proof.trace_next;
+  folder.prep_local = proof.prep_local;
+  folder.prep_next = proof.prep_next;
   for (Target t : public_values) folder.public_values.push_back(p3_field_to_arr(cb, t));
   folder.is_first_row = sels.is_first_row;
   folder.is_last_row = sels.is_last_row;

@@ -44,7 +44,11 @@ struct P3ProofTarget {
   std::vector<std::vector<P3CommitPhaseStep>> query_proofs;
   Ext final_poly;
   Target pow_witness;
-  std::vector<std::array<P3BatchOpening, 2>> query_openings;
+  // this library's extension (AirProgram::PREP_LOCAL / PREP_NEXT): the preprocessed columns at zeta and zeta w_n; empty
+  // for an AIR without preprocessed columns
+  std::vector<Ext> prep_local, prep_next;
+  // per query: the trace batch, the quotient batch and, for an AIR with preprocessed columns, the preprocessed batch
+  std::vector<std::vector<P3BatchOpening>> query_openings;
   int degree_bits;
 };
 
@@ -53,6 +57,7 @@ struct VerifierConstraintFolder {
   std::vector<Ext> trace_local, trace_next;
   std::vector<Ext> public_values;   // this library's extension (AirProgram::PUBLIC): base elements embedded in the extension
   std::vector<Ext> periodic;        // this library's extension (AirProgram::PERIODIC): the periodic columns at zeta, by column
+  std::vector<Ext> prep_local, prep_next;   // this library's extension (AirProgram::PREP_LOCAL / PREP_NEXT): the opened values
   Ext is_first_row, is_last_row, is_transition, alpha, accumulator;
   // air.rs:69-88, 90-118
   void assert_zero(CircuitBuilder& cb, Ext x);
@@ -69,6 +74,10 @@ struct Air {
   // the AIR's periodic columns at zeta, in column order (this library's extension; the reference's trait has none): emits
   // the gates that compute them and throws std::invalid_argument for a period above the trace height 2^log_n
   virtual std::vector<Ext> periodic_at(CircuitBuilder&, const Ext& /*zeta*/, int /*log_n*/) const { return {}; }
+  // the preprocessed columns (this library's extension; the reference's trait has none): their count, and the 4 words of
+  // their commitment for a trace of 2^log_n rows under this log_blowup -- verifying-key data the circuit holds as constants
+  virtual int preprocessed_width() const { return 0; }
+  virtual std::array<u64, 4> preprocessed_commit(int /*log_n*/, int /*log_blowup*/) const { return {}; }
   virtual void eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const = 0;
 };
 // src/p3/mod.rs:160-221 (the test's FibonacciAir)
@@ -88,12 +97,16 @@ struct AirProgram {
   // PUBLIC(a): public value a < n_public of the proof (uni-stark's `builder.public_values()[a]`): degree 0 like CONST
   // PERIODIC(a): periodic column a at the current row (this library's extension, like PUBLIC; include/p25.h "PERIODIC
   // COLUMNS"): degree 1 like LOCAL
-  enum Op : uint32_t { LOCAL = 0, NEXT = 1, CONST = 2, ADD = 3, SUB = 4, MUL = 5, PUBLIC = 6, PERIODIC = 7 };
+  // PREP_LOCAL(a) / PREP_NEXT(a): preprocessed column a at the current / the next row, cyclic as NEXT is (this library's
+  // extension; include/p25.h "PREPROCESSED COLUMNS"): degree 1 like LOCAL
+  enum Op : uint32_t { LOCAL = 0, NEXT = 1, CONST = 2, ADD = 3, SUB = 4, MUL = 5, PUBLIC = 6, PERIODIC = 7, PREP_LOCAL = 8,
+                       PREP_NEXT = 9 };
+  static constexpr int MAX_PREPROCESSED = 64;   // P25_AIR_MAX_PREPROCESSED
   static constexpr int MAX_PUBLIC = 64;   // P25_AIR_MAX_PUBLIC
   static constexpr int MAX_PERIODIC = 32, MAX_LOG_PERIOD = 8;   // P25_AIR_MAX_PERIODIC, P25_AIR_MAX_LOG_PERIOD
   enum When : uint32_t { ALWAYS = 0, FIRST_ROW = 1, LAST_ROW = 2, TRANSITION = 3 };
   struct Node {
-    uint32_t op, a, b;  // LOCAL/NEXT: a = column; PUBLIC: a = index; PERIODIC: a = periodic column; ADD/SUB/MUL: a, b = earlier node indices
+    uint32_t op, a, b;  // LOCAL/NEXT: a = column; PUBLIC: a = index; PERIODIC: a = periodic column; PREP_LOCAL/PREP_NEXT: a = preprocessed column; ADD/SUB/MUL: a, b = earlier node indices
     u64 value;          // CONST
   };
   struct Constraint {
@@ -108,6 +121,14 @@ struct AirProgram {
     std::vector<u64> values;   // [2^log_period], each < p
   };
   std::vector<Periodic> periodic;
+  // The preprocessed trace: a matrix of known columns as high as the trace, committed once like the trace (the commitment is
+  // verifying-key data, p3_preprocessed_commit in p3_prover.h), opened at zeta and zeta w_n and queried like the trace.
+  struct Preprocessed {
+    uint32_t width = 0;        // 0..MAX_PREPROCESSED
+    uint32_t log_n = 0;        // the trace's log height (check_preprocessed)
+    std::vector<u64> values;   // [2^log_n][width], row-major like a trace, each < p
+  };
+  Preprocessed prep;
   std::vector<Node> nodes;
   std::vector<Constraint> constraints;
   // throws std::invalid_argument on malformed programs (a PUBLIC index >= n_public, n_public > MAX_PUBLIC, a PERIODIC index
@@ -117,6 +138,8 @@ struct AirProgram {
   void validate() const;
   // the one check that needs the trace height: throws std::invalid_argument for a column with log_period > log_n
   void check_periodic(int log_n) const;
+  // the same for the preprocessed matrix: throws std::invalid_argument if it has columns and its log_n is not the trace's
+  void check_preprocessed(int log_n) const;
   // coefficients of column c's interpolant q (degree < P, q(w_P^j) = values[j]): what the evaluation at zeta and the
   // table on the quotient coset (p3_periodic_table, p3_prover.h) start from
   std::vector<u64> periodic_coefficients(size_t c) const;
@@ -132,7 +155,8 @@ struct AirProgram {
   static AirProgram fibonacci();
 
   // Generic evaluation, nodes computed on demand in constraint order (so that the circuit form emits
-  // its gates in the order the reference's hand-written `eval` does).  ops: cst(u64), pub(index), per(column), add, sub, mul.
+  // its gates in the order the reference's hand-written `eval` does).  ops: cst(u64), pub(index), per(column),
+  // prep_local(column), prep_next(column), add, sub, mul.
   template <class T, class Ops, class Emit>
   void fold(const std::vector<T>& local, const std::vector<T>& next, const T sel[4], Ops& ops, Emit&& emit) const {
     std::vector<T> val(nodes.size());
@@ -157,6 +181,10 @@ struct AirProgram {
           val[i] = ops.pub(nd.a);
         } else if (nd.op == PERIODIC) {
           val[i] = ops.per(nd.a);
+        } else if (nd.op == PREP_LOCAL) {
+          val[i] = ops.prep_local(nd.a);
+        } else if (nd.op == PREP_NEXT) {
+          val[i] = ops.prep_next(nd.a);
         } else {
           if (!have[nd.a]) {
             stack.push_back(nd.a);
@@ -183,13 +211,18 @@ struct ProgramAir : Air {
   int n_public() const override { return prog.n_public; }
   // emission order: p3_circuit.cpp
   std::vector<Ext> periodic_at(CircuitBuilder& cb, const Ext& zeta, int log_n) const override;
+  int preprocessed_width() const override { return (int)prog.prep.width; }
+  std::array<u64, 4> preprocessed_commit(int log_n, int log_blowup) const override;   // p3_prover.cpp
   void eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const override;
 };
 
 // CircuitBuilderP3Arithmetic::p3_verify_proof (src/p3/mod.rs:66-94).  Registers the proof's virtual
 // targets as the circuit's per-proof inputs (cb.input_targets, `add_virtual_to` order).  An AIR with public values adds
 // air.n_public() input targets behind the proof's, observes them after the trace commitment (where uni-stark's verifier has
-// `challenger.observe_slice(public_values)`) and registers them as the circuit's public inputs, in order.
+// `challenger.observe_slice(public_values)`) and registers them as the circuit's public inputs, in order.  An AIR with
+// preprocessed columns adds their openings and a third batch per query to the proof's targets (include/p25.h "PREPROCESSED
+// COLUMNS" has the positions), holds their commitment as four constants, observes it directly after the trace commitment
+// and hands the opening proof a third (commitment, matrices, points) entry; without such columns the circuit is as it was.
 P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const Air& air);
 
 // gadget-level entry points (src/p3/mod.rs:40-45, 96-147), exposed for the gadget tests

@@ -11,9 +11,13 @@ namespace p25 {
 // Operands: kind << 28 | index.  LOCAL / NEXT / CONST / PUBLIC nodes never take a slot: they are re-read where they are
 // used (PUBLIC: from the proof's own row of public values).  PERIODIC is as free: its index is log_period << 24 | the
 // words of the columns before it (at most 31 * 256), and its value comes from the caller of run_air -- a table word in the
-// quotient kernel, q_c(zeta^(n/P)) in the identity lanes.
+// quotient kernel, q_c(zeta^(n/P)) in the identity lanes.  PREP_LOCAL / PREP_NEXT (index = preprocessed column) are read
+// through run_air's `load` like LOCAL / NEXT: from the handle's shared LDE in the quotient kernel, from the proof's
+// preprocessed openings in the identity lanes.
 enum : uint32_t { P3_OPND_SLOT = 0, P3_OPND_LOCAL = 1, P3_OPND_NEXT = 2, P3_OPND_CONST = 3, P3_OPND_PUBLIC = 4,
-                  P3_OPND_PERIODIC = 5 };
+                  P3_OPND_PERIODIC = 5, P3_OPND_PREP_LOCAL = 6, P3_OPND_PREP_NEXT = 7 };
+// what run_air's load(which, column) is asked for: bit 0 the next row, bit 1 the preprocessed matrix
+enum : int { P3_LOAD_LOCAL = 0, P3_LOAD_NEXT = 1, P3_LOAD_PREP_LOCAL = 2, P3_LOAD_PREP_NEXT = 3 };
 GL_HD uint32_t p3_per_log_period(uint32_t index) { return index >> 24; }
 GL_HD uint32_t p3_per_offset(uint32_t index) { return index & 0xffffffu; }
 enum : uint32_t { P3_OP_ADD = 3, P3_OP_SUB = 4, P3_OP_MUL = 5, P3_OP_EMIT = 6 };  // ADD..MUL as AirProgram::Op
@@ -60,13 +64,15 @@ struct P3Shape {
   // with `off` words of columns before it: its P coefficients at per_coef + off, its table of P Q values on the quotient
   // coset (p3_periodic_table) at per_tab + off * Q.
   uint32_t per_coef, per_tab;
+  // The preprocessed columns: PW of them (0: none), in P3Bufs::pcoef / plde / ptree, shared like the periodic tables.
+  uint32_t PW;
   u64 w[26], w_inv[26];           // primitive 2^i-th roots of unity and their inverses
   u64 zh[8], zh_inv[8];           // x^n - 1 on the quotient coset, by chunk
   u64 s_inv[8];                   // 1 / s_c
   u64 g_inv;                      // 1 / w_n
-  // hdr: the proof's first words (trace root | quotient root | trace_local | trace_next | chunks | FRI roots), then
-  // points (zeta, zeta w_n, zeta / s_c), powers of fri_alpha, betas, query indices
-  uint32_t hdr_words, o_points, o_apow, o_betas, o_idx, hdr_stride;
+  // hdr: the proof's first words (trace root | quotient root | trace_local | trace_next | chunks | prep_local | prep_next |
+  // FRI roots from o_fri), then points (zeta, zeta w_n, zeta / s_c), powers of fri_alpha, betas, query indices
+  uint32_t hdr_words, o_fri, o_points, o_apow, o_betas, o_idx, hdr_stride;
   uint32_t sz_a, sz_b;            // words per query: commit-phase openings, input openings
 };
 struct P3Bufs {
@@ -81,6 +87,10 @@ struct P3Bufs {
   // [G][n_public]: the public values of THIS GROUP's proofs -- the batch's array advanced by the group's first proof, like
   // every other per-proof pointer of a group (blockIdx.y counts inside the group); null when n_public = 0
   const u64* pub;
+  // The preprocessed columns' coefficients [PW][n], LDE on 7 H_{N2} in bit-reversed order [PW][N2] and tree (8 N2 words):
+  // constant tables of the handle, made once on the device (P3ProverDev::ensure_preprocessed), the same for every proof
+  // of every group -- no blockIdx.y offset ever applies to them; null when PW = 0
+  const u64 *pcoef, *plde, *ptree;
 };
 
 // words of level l of a tree over h leaves (levels concatenated, 4 words per digest), FRI layer r, FRI tree r
@@ -120,11 +130,21 @@ class P3ProverDev {
   ~P3ProverDev();
   const P3Config& config() const { return cfg_; }
   // words of a flat proof: the proof's in `add_virtual_to` order, then its n_public public values
-  size_t num_inputs() const { return cfg_.num_inputs() + shape_.n_public; }
+  // (cfg_.num_inputs() + n_public without preprocessed columns; with them, their openings and third batches as well)
+  size_t num_inputs() const {
+    return (size_t)shape_.hdr_words + (size_t)shape_.num_queries * (shape_.sz_a + shape_.sz_b) + 3 + shape_.n_public;
+  }
   uint32_t n_public() const { return shape_.n_public; }
   size_t trace_words() const { return ((size_t)1 << cfg_.log_trace_height) * (size_t)cfg_.trace_width; }
   size_t scratch_words_per_proof() const;
   size_t group_size(size_t n_proofs) const;
+  // The preprocessed columns' constant tables (coefficients PW n, LDE PW N2, tree 8 N2 words): outside the group budget,
+  // counted by scratch_bytes under `proving` once a proving call has made them.
+  size_t preprocessed_table_words() const;
+  uint32_t preprocessed_width() const { return shape_.PW; }
+  // The 4 words of the preprocessed commitment as the device computed them (the first call computes them: a handle that
+  // has only verified, or done nothing yet, makes the tables in a temporary and frees it).  Throws without columns.
+  void preprocessed_commit(u64 out[4]);
   void set_scratch_budget(size_t bytes) { budget_bytes_ = bytes ? bytes : P3_SCRATCH_BUDGET_BYTES; }
   // enqueue-only on `st`.  d_public: [n_proofs][n_public], packed (unread when n_public = 0)
   void prove_dev(const u64* d_traces, size_t trace_stride, const u64* d_public, size_t n_proofs, const u64* d_pow_starts,
@@ -150,12 +170,18 @@ class P3ProverDev {
 
  private:
   void ensure_impl();
+  // the preprocessed tables on the device, made on `st` behind the handle's earlier work: keep = false computes the root
+  // in a temporary (the verifying side needs nothing else); no-op once done or without columns
+  void ensure_preprocessed(bool keep, hipStream_t st);
   void run_group(const u64* d_traces, size_t trace_stride, const u64* d_public, uint32_t G, const u64* d_pow_starts,
                  u64* d_inputs, size_t input_stride, uint32_t* d_status, hipStream_t st);
   P3Config cfg_;
   P3AirDevice prog_;
   P3Shape shape_;
   std::vector<u64> zfirst_inv_;
+  std::vector<u64> prep_values_;   // [n][PW] row-major, until the device has them
+  u64 prep_root_[4] = {0, 0, 0, 0};
+  bool prep_root_known_ = false;
   size_t budget_bytes_;
   P3ProverImpl* impl_ = nullptr;   // device state, made by the first compute call
 };

@@ -162,9 +162,59 @@ std::vector<u64> p3_periodic_table(const std::vector<u64>& coef, int log_n, int 
 }
 
 namespace {
+// The preprocessed matrix as the trace is committed: per column the coefficients and the LDE on 7 H_{n 2^B} in natural
+// order, the matrix [N2][width] in bit-reversed row order, and its tree.
+struct PrepCommit {
+  std::vector<std::vector<u64>> coef, lde_nat;
+  std::vector<u64> rows;
+  Tree tree;
+};
+PrepCommit commit_preprocessed(const AirProgram::Preprocessed& pp, int B, int threads) {
+  const int k = (int)pp.log_n, L = k + B, PW = (int)pp.width;
+  const size_t n = (size_t)1 << k, N2 = n << B;
+  PrepCommit pc;
+  pc.coef.assign(PW, std::vector<u64>(n));
+  for (size_t r = 0; r < n; r++)
+    for (int c = 0; c < PW; c++) pc.coef[c][r] = pp.values[r * PW + c];
+  for (auto& c : pc.coef) intt(c);
+  pc.lde_nat.resize(PW);
+  for (int c = 0; c < PW; c++) pc.lde_nat[c] = lde(pc.coef[c], gl::GENERATOR, B);
+  pc.rows.resize(N2 * PW);
+  for (size_t i = 0; i < N2; i++) {
+    const size_t r = gl::bitrev((u32)i, L);
+    for (int c = 0; c < PW; c++) pc.rows[i * PW + c] = pc.lde_nat[c][r];
+  }
+  pc.tree = commit(pc.rows, PW, threads);
+  return pc;
+}
+void check_preprocessed_matrix(const AirProgram::Preprocessed& pp, int log_blowup) {
+  if (pp.width < 1 || pp.width > (uint32_t)AirProgram::MAX_PREPROCESSED)
+    throw std::invalid_argument("preprocessed columns: width must be 1..64 (P25_AIR_MAX_PREPROCESSED)");
+  if (pp.log_n < 1 || pp.log_n > 22 || log_blowup < 1 || log_blowup > 4 || (int)pp.log_n + log_blowup > 24)
+    throw std::invalid_argument("preprocessed columns: unsupported log_n / log_blowup");
+  if (pp.values.size() != ((size_t)pp.width << pp.log_n))
+    throw std::invalid_argument("preprocessed columns: the matrix holds 2^log_n rows of `width` values");
+  for (u64 v : pp.values)
+    if (v >= gl::P) throw std::invalid_argument("preprocessed columns: non-canonical value (>= p)");
+}
+}  // namespace
+
+std::array<u64, 4> p3_preprocessed_commit(const AirProgram::Preprocessed& pp, int log_blowup, int threads) {
+  check_preprocessed_matrix(pp, log_blowup);
+  return commit_preprocessed(pp, log_blowup, threads < 1 ? 1 : threads).tree.root();
+}
+std::array<u64, 4> ProgramAir::preprocessed_commit(int log_n, int log_blowup) const {
+  prog.check_preprocessed(log_n);
+  return p3_preprocessed_commit(prog.prep, log_blowup, 1);
+}
+
+namespace {
 struct BaseOps {
   const std::vector<u64>& pv;
   const std::vector<u64>& pc;   // the periodic columns at the current point
+  const std::vector<u64>&pl, &pn;   // the preprocessed columns at the current point and at the next row's
+  u64 prep_local(uint32_t c) { return pl[c]; }
+  u64 prep_next(uint32_t c) { return pn[c]; }
   u64 cst(u64 v) { return v; }
   u64 pub(uint32_t i) { return pv[i]; }
   u64 per(uint32_t c) { return pc[c]; }
@@ -175,6 +225,9 @@ struct BaseOps {
 struct ExtOps {
   const std::vector<u64>& pv;
   const std::vector<E2>& pc;    // the periodic columns at zeta
+  const std::vector<E2>&pl, &pn;    // the preprocessed columns at zeta and zeta w_n
+  E2 prep_local(uint32_t c) { return pl[c]; }
+  E2 prep_next(uint32_t c) { return pn[c]; }
   E2 cst(u64 v) { return gl::e2(v); }
   E2 pub(uint32_t i) { return gl::e2(pv[i]); }
   E2 per(uint32_t c) { return pc[c]; }
@@ -215,6 +268,7 @@ void p3_check_params(const AirProgram& air, int log_n, int log_blowup, int num_q
     throw std::invalid_argument("p3_prove: unsupported parameters");
   air.validate();
   air.check_periodic(log_n);
+  air.check_preprocessed(log_n);
   if (air.log_quotient_degree() > log_blowup)
     throw std::invalid_argument("p3_prove: the AIR's constraint degree needs more quotient chunks than log_blowup holds");
 }
@@ -260,8 +314,14 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
   }
   Tree trace_tree = commit(trace_rows, W, T);
 
+  // the preprocessed columns: committed as the trace is; the root is verifying-key data, observed behind the trace root
+  const int PW = (int)air.prep.width;
+  PrepCommit prep;
+  if (PW) prep = commit_preprocessed(air.prep, B, T);
+
   Challenger ch;
   ch.observe_digest(trace_tree.root());
+  if (PW) ch.observe_digest(prep.tree.root());
   for (u64 v : pub) ch.observe(v);   // uni-stark's challenger.observe_slice(public_values): unpinned (include/p25.h)
   const E2 alpha = ch.sample_ext();
 
@@ -291,13 +351,18 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
     std::vector<std::vector<u64>> ptab(NP);
     for (size_t c = 0; c < NP; c++) ptab[c] = p3_periodic_table(air.periodic_coefficients(c), k, lqd);
     std::vector<u64> per(NP);
-    BaseOps ops{pub, per};
+    std::vector<u64> ploc(PW), pnxt(PW);
+    BaseOps ops{pub, per, ploc, pnxt};
     std::vector<u64> loc(W), nxt(W);
     for (size_t j = 0; j < nq; j++, x = gl::mul(x, w_q)) {
       const size_t i0 = lde_step * j, i1 = (lde_step * j + row_step) % N2;   // the next ROW is x w_n = 2^B LDE points on
       for (int c = 0; c < W; c++) {
         loc[c] = lde_nat[c][i0];
         nxt[c] = lde_nat[c][i1];
+      }
+      for (int c = 0; c < PW; c++) {
+        ploc[c] = prep.lde_nat[c][i0];
+        pnxt[c] = prep.lde_nat[c][i1];
       }
       for (size_t c = 0; c < NP; c++) per[c] = ptab[c][j & (ptab[c].size() - 1)];
       // two_adic.rs:100-147: selectors at a point of the quotient coset
@@ -347,6 +412,11 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
     t_local[c] = eval_ext(coef[c], zeta);
     t_next[c] = eval_ext(coef[c], zeta_next);
   }
+  std::vector<E2> p_local(PW), p_next(PW);
+  for (int c = 0; c < PW; c++) {
+    p_local[c] = eval_ext(prep.coef[c], zeta);
+    p_next[c] = eval_ext(prep.coef[c], zeta_next);
+  }
   std::vector<E2> qz(2 * Q);                      // q_c's components at zeta = P_c at zeta / s_c
   for (size_t c = 0; c < Q; c++) {
     const E2 z_over_s = gl::mul(zeta, gl::inv(s_c[c]));
@@ -361,7 +431,7 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
     std::vector<E2> per;
     for (size_t c = 0; c < air.periodic.size(); c++)
       per.push_back(eval_ext(air.periodic_coefficients(c), gl::exp_pow2(zeta, k - (int)air.periodic[c].log_period)));
-    ExtOps ops{pub, per};
+    ExtOps ops{pub, per, p_local, p_next};
     E2 acc = gl::e2(0);
     air.fold<E2>(t_local, t_next, sel, ops, [&](E2 c) { acc = gl::add(gl::mul(acc, alpha), c); });
     E2 lhs = gl::mul(acc, gl::inv(z_h));
@@ -385,7 +455,7 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
   const E2 fri_alpha = ch.sample_ext();
   std::vector<E2> folded(N2);
   {
-    std::vector<E2> apow(2 * W + 2 * Q);
+    std::vector<E2> apow(2 * W + 2 * Q + 2 * PW);
     apow[0] = gl::e2(1);
     for (size_t i = 1; i < apow.size(); i++) apow[i] = gl::mul(apow[i - 1], fri_alpha);
     parallel_for(T, N2, [&](size_t b, size_t e) {
@@ -402,6 +472,11 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
           acc = gl::add(acc, gl::mul(apow[t], gl::mul(gl::sub(gl::e2(trace_rows[i * W + c]), t_next[c]), inv_zn)));
         for (size_t c = 0; c < 2 * Q; c++, t++)     // the chunk matrices in order, two columns each, all opened at zeta
           acc = gl::add(acc, gl::mul(apow[t], gl::mul(gl::sub(gl::e2(quot_rows[2 * Q * i + c]), qz[c]), inv_z)));
+        // the third batch: the preprocessed matrix at zeta, then at zeta w_n; same height as the trace, so the powers go on
+        for (int c = 0; c < PW; c++, t++)
+          acc = gl::add(acc, gl::mul(apow[t], gl::mul(gl::sub(gl::e2(prep.rows[i * PW + c]), p_local[c]), inv_z)));
+        for (int c = 0; c < PW; c++, t++)
+          acc = gl::add(acc, gl::mul(apow[t], gl::mul(gl::sub(gl::e2(prep.rows[i * PW + c]), p_next[c]), inv_zn)));
         folded[i] = acc;
       }
     });
@@ -469,6 +544,8 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
   for (auto& e : t_local) push_e(e);
   for (auto& e : t_next) push_e(e);
   for (auto& e : qz) push_e(e);
+  for (auto& e : p_local) push_e(e);
+  for (auto& e : p_next) push_e(e);
   for (auto& t : fri_trees) push_d(t.root());
   for (size_t ix : indices) {
     size_t idx = ix;
@@ -486,8 +563,12 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
     for (auto& d : trace_tree.prove(ix)) push_d(d);
     for (size_t c = 0; c < 2 * Q; c++) out.push_back(quot_rows[2 * Q * ix + c]);
     for (auto& d : quot_tree.prove(ix)) push_d(d);
+    if (PW) {
+      for (int c = 0; c < PW; c++) out.push_back(prep.rows[ix * PW + c]);
+      for (auto& d : prep.tree.prove(ix)) push_d(d);
+    }
   }
-  if (out.size() != cfg.num_inputs()) throw std::logic_error("p3 prover: flattened size mismatch");
+  if (out.size() != cfg.num_inputs() + p3_preprocessed_words(PW, k, B, prm.num_queries)) throw std::logic_error("p3 prover: flattened size mismatch");
   out.insert(out.end(), pub.begin(), pub.end());   // plonky3's Proof holds no public values: they travel behind it
   return out;
 }

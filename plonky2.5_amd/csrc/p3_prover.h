@@ -47,6 +47,16 @@ std::vector<u64> p3_prove_air(const AirProgram& air, const std::vector<std::vect
 // + air.n_public words in all).  With no public values the words are p3_prove_air's.
 std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::vector<u64>>& col, const std::vector<u64>& pub,
                                  const P3ProveParams& prm, P3Config& cfg_out);
+// Preprocessed columns (AirProgram::Preprocessed; include/p25.h "PREPROCESSED COLUMNS") travel in `air.prep`: every prover
+// here commits them as it commits the trace, observes the root behind the trace root, opens them at zeta and zeta w_n behind
+// the chunk openings and adds a third batch to every query; without columns the words are unchanged.
+// The words such a proof has beyond P3Config::num_inputs(): the two openings and every query's row and path.
+inline size_t p3_preprocessed_words(int prep_width, int log_n, int log_blowup, int num_queries) {
+  return prep_width ? 4 * (size_t)prep_width + (size_t)num_queries * ((size_t)prep_width + 4 * (size_t)(log_n + log_blowup)) : 0;
+}
+// The commitment of a preprocessed matrix: the Poseidon2 MMCS root over the columns' LDE on 7 H_{n 2^log_blowup} in
+// bit-reversed leaf order, the commit the trace gets.  Throws std::invalid_argument (width 0 included: nothing to commit).
+std::array<u64, 4> p3_preprocessed_commit(const AirProgram::Preprocessed& prep, int log_blowup, int threads);
 // A periodic column on the quotient coset 7 H_{n Q}, Q = 2^lqd (AirProgram::Periodic; include/p25.h "PERIODIC COLUMNS"):
 // T[r] = q(7^(n/P) u^r), u = w_{n Q}^(n/P) of order P Q, for r < P Q -- the coset LDE of the interpolant q whose P
 // coefficients are `coef`.  The column's value at the point of natural index j, x_j = 7 w_{n Q}^j, is T[j mod (P Q)].

@@ -10,7 +10,7 @@ namespace p25 {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // AirProgram -> register program.  Nodes are visited in the order AirProgram::fold evaluates them; a LOCAL / NEXT / CONST /
-// PUBLIC / PERIODIC node becomes an operand, an arithmetic node takes a slot from its evaluation to its last use.
+// PUBLIC / PERIODIC / PREP_LOCAL / PREP_NEXT node becomes an operand, an arithmetic node takes a slot from its evaluation to its last use.
 // ---------------------------------------------------------------------------------------------------------------------
 P3AirDevice P3AirDevice::compile(const AirProgram& air) {
   typedef AirProgram A;
@@ -46,6 +46,8 @@ P3AirDevice P3AirDevice::compile(const AirProgram& air) {
     if (nd.op == A::LOCAL) return (P3_OPND_LOCAL << 28) | nd.a;
     if (nd.op == A::NEXT) return (P3_OPND_NEXT << 28) | nd.a;
     if (nd.op == A::PUBLIC) return (P3_OPND_PUBLIC << 28) | nd.a;
+    if (nd.op == A::PREP_LOCAL) return (P3_OPND_PREP_LOCAL << 28) | nd.a;
+    if (nd.op == A::PREP_NEXT) return (P3_OPND_PREP_NEXT << 28) | nd.a;
     if (nd.op == A::PERIODIC) {
       uint32_t off = 0;   // words of the columns before it
       for (uint32_t c = 0; c < nd.a; c++) off += 1u << air.periodic[c].log_period;
@@ -125,6 +127,9 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
   s.num_queries = num_queries; s.pow_bits = pow_bits;
   s.n_instr = (uint32_t)prog_.instr.size();
   s.n_public = (uint32_t)air.n_public;
+  s.PW = air.prep.width;
+  if (s.PW) prep_values_ = air.prep.values;
+  const uint32_t PW = s.PW;
   // the periodic columns go up with the constants: every column's coefficients, then every column's table
   s.per_coef = (uint32_t)prog_.consts.size();
   std::vector<u64> tables;
@@ -154,16 +159,18 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
   for (size_t c = 0; c < Q; c++)
     for (size_t j = 0; j < Q; j++)
       if (j != c) zfirst_inv_[c * Q + j] = gl::inv(gl::sub(gl::pow(gl::mul(s_c[c], s.s_inv[j]), n), 1));
-  s.hdr_words = 8 + 4 * W + 4 * (uint32_t)Q + 4 * k;
+  s.o_fri = 8 + 4 * W + 4 * (uint32_t)Q + 4 * PW;
+  s.hdr_words = s.o_fri + 4 * k;
   s.o_points = s.hdr_words;
   s.o_apow = s.o_points + 2 * (2 + (uint32_t)Q);
-  s.o_betas = s.o_apow + 2 * (2 * W + 2 * (uint32_t)Q);
+  s.o_betas = s.o_apow + 2 * (2 * W + 2 * (uint32_t)Q + 2 * PW);
   s.o_idx = s.o_betas + 2 * k;
   s.hdr_stride = s.o_idx + (num_queries + 1) / 2;
   s.sz_a = 0;
   for (int r = 0; r < k; r++) s.sz_a += 2 + 4 * (L - r - 1);
-  s.sz_b = W + 4 * L + 2 * (uint32_t)Q + 4 * L;
-  if ((size_t)s.hdr_words + (size_t)num_queries * (s.sz_a + s.sz_b) + 3 != cfg_.num_inputs())   // the public values follow
+  s.sz_b = W + 4 * L + 2 * (uint32_t)Q + 4 * L + (PW ? PW + 4 * L : 0);
+  if ((size_t)s.hdr_words + (size_t)num_queries * (s.sz_a + s.sz_b) + 3 !=
+      cfg_.num_inputs() + p3_preprocessed_words((int)PW, k, B, num_queries))   // the public values follow
     throw std::logic_error("p3 device prover: flattened size mismatch");
   budget_bytes_ = P3_SCRATCH_BUDGET_BYTES;
 }
@@ -214,6 +221,56 @@ size_t P3ProverDev::group_size(size_t n_proofs) const {
   return std::min(g, n_proofs);
 }
 
+size_t P3ProverDev::preprocessed_table_words() const {
+  const size_t n = (size_t)1 << shape_.k, N2 = (size_t)1 << shape_.L;
+  return shape_.PW ? shape_.PW * n + shape_.PW * N2 + 8 * N2 : 0;
+}
+
+// The preprocessed columns' tables, by the launches the trace takes with a group of one: rows -> columns -> coefficients ->
+// LDE on 7 H_{n 2^B} in bit-reversed order -> tree.  The values and an NTT temporary (PW n words each) are freed behind a
+// synchronisation; so is everything but the root when `keep` is false.  Blocks the host: it runs once per handle.
+void P3ProverDev::ensure_preprocessed(bool keep, hipStream_t st) {
+  if (!shape_.PW || impl_->prep.words || (!keep && prep_root_known_)) return;
+  const P3Shape& s = shape_;
+  const size_t n = (size_t)1 << s.k, N2 = (size_t)1 << s.L, PW = s.PW;
+  DevMem tables(preprocessed_table_words()), rows(PW * n), vals(PW * n), tmp(PW * n);
+  if (!impl_->prep_root.words) impl_->prep_root = DevMem(4);
+  u64 *coef = tables.p, *lde = coef + PW * n, *tree = lde + PW * N2;
+  if (impl_->recorded) P25_HIP(hipStreamWaitEvent(st, impl_->done, 0));
+  P25_HIP(hipMemcpyAsync(rows.p, prep_values_.data(), PW * n * 8, hipMemcpyHostToDevice, st));
+  P3Shape ts = s;    // the transpose reads k, W and G alone
+  ts.W = (uint32_t)PW;
+  ts.G = 1;
+  P3Bufs tb{};
+  tb.tvals = vals.p;
+  p3_launch_transpose(rows.p, PW * n, ts, tb, st);
+  NttTables& nt = impl_->tables;
+  ntt_inverse(nt, vals.p, n, false, tmp.p, n, coef, n, (int)s.k, (int)PW, 1, st);
+  if (s.B <= 3) {
+    ntt_lde_bitrev(nt, coef, n, lde, N2, (int)s.k, (int)s.B, (int)PW, gl::GENERATOR, st);
+  } else {   // 16 cosets as two interleaved sets of 8, as run_group's lde
+    ntt_lde_bitrev(nt, coef, n, lde, N2, (int)s.k, 3, (int)PW, gl::GENERATOR, st);
+    ntt_lde_bitrev(nt, coef, n, lde + N2 / 2, N2, (int)s.k, 3, (int)PW, gl::mul(gl::GENERATOR, gl::root_of_unity(s.L)), st);
+  }
+  p3_launch_commit_cols(lde, PW * N2, 2 * N2, N2, (uint32_t)PW, N2, tree, 8 * N2, 1, st);
+  P25_HIP(hipGetLastError());
+  P25_HIP(hipMemcpyAsync(impl_->prep_root.p, tree + p3_level_off(N2, s.L), 32, hipMemcpyDeviceToDevice, st));
+  P25_HIP(hipMemcpyAsync(prep_root_, tree + p3_level_off(N2, s.L), 32, hipMemcpyDeviceToHost, st));
+  P25_HIP(hipStreamSynchronize(st));
+  prep_root_known_ = true;
+  if (keep) {
+    impl_->prep = std::move(tables);
+    prep_values_.clear();
+    prep_values_.shrink_to_fit();
+  }
+}
+void P3ProverDev::preprocessed_commit(u64 out[4]) {
+  if (!shape_.PW) throw std::invalid_argument("p25_p3_prover_preprocessed_commit: the prover's AIR has no preprocessed columns");
+  ensure_impl();
+  ensure_preprocessed(false, impl_->host_stream());
+  for (int i = 0; i < 4; i++) out[i] = prep_root_[i];
+}
+
 void P3ProverDev::sync() {
   if (!impl_ || !impl_->recorded) return;
   P25_HIP(hipEventSynchronize(impl_->done));
@@ -237,6 +294,7 @@ void P3ProverDev::prove_dev(const u64* d_traces, size_t trace_stride, const u64*
                             const u64* d_pow_starts, u64* d_inputs, size_t input_stride, uint32_t* d_status, hipStream_t st) {
   if (!n_proofs) return;
   ensure_impl();
+  ensure_preprocessed(true, st);
   const size_t G = group_size(n_proofs), need = G * scratch_words_per_proof();
   if (impl_->scratch.words < need) {
     sync();   // an earlier call may still be using the old allocation
@@ -271,6 +329,11 @@ void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, const u64*
   b.consts = impl_->consts.p;
   b.zfirst_inv = impl_->zfirst.p;
   b.pub = d_public;
+  if (s.PW) {   // the handle's constant tables: the same pointers for every group
+    b.pcoef = impl_->prep.p;
+    b.plde = b.pcoef + (size_t)s.PW * n;
+    b.ptree = b.plde + (size_t)s.PW * N2;
+  }
 
   // the LDE on shift * <w_{n 2^B}> in bit-reversed order; 16 cosets as two interleaved sets of 8 (coset 2 c + e of the
   // first kind is coset c of the set with shift * w^e, and lands in half e of the bit-reversed output)

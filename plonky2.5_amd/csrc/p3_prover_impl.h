@@ -9,6 +9,8 @@ namespace p25 {
 struct P3ProverImpl {
   NttTables tables;
   DevMem prog, consts, zfirst, scratch;
+  DevMem prep;       // the preprocessed columns' tables: coefficients | LDE | tree (p3_prover_dev.hip); empty until a proving call
+  DevMem prep_root;  // the 4 words of the preprocessed commitment: all the verifying side keeps of the columns
   DevMem vscratch;   // the verifier's: challenge blocks and folded values (p3_verify_dev.hip)
   DevStream own_stream;   // the host entry points' (prove_host, verify_host): created by the first of them
   // Recorded behind the last launch of every compute call.  The next call's stream waits for it before it touches the

@@ -14,7 +14,7 @@ size_t P3ProverDev::verify_chunk(size_t n_proofs) const {
   return std::min(std::max<size_t>(1, c), n_proofs);
 }
 void P3ProverDev::scratch_bytes(size_t* proving, size_t* verifying) const {
-  if (proving) *proving = impl_ ? impl_->scratch.words * 8 : 0;
+  if (proving) *proving = impl_ ? (impl_->scratch.words + impl_->prep.words) * 8 : 0;   // the preprocessed tables count here
   if (verifying) *verifying = impl_ ? impl_->vscratch.words * 8 : 0;
 }
 
@@ -32,8 +32,11 @@ P3VerifyArgs P3ProverDev::verify_args() const {
   a.n_public = s.n_public;
   a.o_public = a.num_inputs - s.n_public;
   a.per_coef = s.per_coef;
+  a.PW = s.PW;
+  a.nb = s.PW ? 3 : 2;
+  a.prep_root = prep_root_;   // the host's copy, known once a compute call has made it; verify_dev puts the device's in its place
   a.o_open = 8;
-  a.o_roots = 8 + 4 * s.W + 4 * s.Q;
+  a.o_roots = s.o_fri;
   a.o_qp = s.hdr_words;
   a.sz_a = s.sz_a;
   a.o_final = a.o_qp + s.num_queries * s.sz_a;
@@ -57,11 +60,13 @@ P3VerifyArgs P3ProverDev::verify_args() const {
 void P3ProverDev::verify_dev(const u64* d_inputs, size_t n_proofs, size_t input_stride, uint32_t* d_status, hipStream_t st) {
   if (!n_proofs) return;
   ensure_impl();
+  ensure_preprocessed(false, st);   // the 4 words of the preprocessed commitment: all this side needs of the columns
   P3VerifyArgs a = verify_args();
   a.stride = input_stride;
   a.prog = reinterpret_cast<const P3Instr*>(impl_->prog.p);
   a.consts = impl_->consts.p;
   a.zfirst_inv = impl_->zfirst.p;
+  a.prep_root = impl_->prep_root.p;
 
   const size_t C = verify_chunk(n_proofs), per = verify_scratch_words_per_proof(), need = C * per;
   if (impl_->vscratch.words < need) {

@@ -19,8 +19,9 @@ namespace p25 {
 // statement order of verifier.rs (atomicMin: never the last writer); the verdict lane turns it into the code.
 //   0                            a word >= p
 //   1                            proof of work (:376)
-//   2 + 2 q + b                  input batch b (0 trace, 1 quotient) of query q (:288-294; all queries before any FRI step)
-//   F + q (k + 2)                a zero denominator in query q's reduced opening, F = 2 + 2 num_queries: reported as the
+//   2 + nb q + b                 input batch b (0 trace, 1 quotient, 2 preprocessed) of query q (:288-294; all queries before
+//                                any FRI step); nb = 2, or 3 for a handle with preprocessed columns
+//   F + q (k + 2)                a zero denominator in query q's reduced opening, F = 2 + nb num_queries: reported as the
 //                                query's final-polynomial failure, ahead of its FRI rounds, whose leaves it spoils
 //   F + q (k + 2) + 1 + r        FRI round r of query q (:471-481)
 //   F + q (k + 2) + 1 + k        the final polynomial of query q (:413)
@@ -53,13 +54,17 @@ struct P3VerifyArgs {
   uint32_t n_public, o_public;
   // the periodic columns' coefficients: consts + per_coef (P3Shape::per_coef), read by the identity lane alone
   uint32_t per_coef;
+  // the preprocessed columns: their count (0: none), the input batches of a query (2, or 3 with such columns) and the
+  // handle's commitment, which the transcript observes behind the trace root and the third batch's paths must reach
+  uint32_t PW, nb;
+  const u64* prep_root;   // 4 words (the handle's: device memory on the device); unread when PW = 0
   u64 w_L, w_L_inv;    // primitive root of the LDE domain and its inverse
   u64 w_n, g_inv;      // generator of the trace domain and its inverse
   u64 neg2_inv;        // 1 / -2
   u64 s_inv[8];        // 1 / s_c, s_c the shift of chunk c's domain
 };
 
-GL_HD uint32_t p3v_key_fri(const P3VerifyArgs& a) { return P3VKEY_INPUT + 2 * a.num_queries; }
+GL_HD uint32_t p3v_key_fri(const P3VerifyArgs& a) { return P3VKEY_INPUT + a.nb * a.num_queries; }
 GL_HD uint32_t p3v_key_constraints(const P3VerifyArgs& a) { return p3v_key_fri(a) + a.num_queries * (a.k + 2); }
 // round r of a query's commit-phase openings: sibling_value (2 words), then L - r - 1 digests
 GL_HD uint32_t p3v_round_off(const P3VerifyArgs& a, uint32_t r) { return 2 * r + 4 * (r * (a.L - 1) - r * (r - 1) / 2); }
@@ -109,6 +114,8 @@ GL_HD uint32_t transcript_lane(const P3VerifyArgs& a, uint32_t p) {
     for (uint32_t i = 0; i < n; i++) chal[slot + i] = ch.sample();
   };
   for (int i = 0; i < 4; i++) ch.observe(proof[i]);
+  if (a.PW)
+    for (int i = 0; i < 4; i++) ch.observe(a.prep_root[i]);
   for (uint32_t i = 0; i < a.n_public; i++) ch.observe(proof[a.o_public + i]);
   draw(P3VC_ALPHA, 2);
   for (int i = 0; i < 4; i++) ch.observe(proof[4 + i]);
@@ -137,7 +144,10 @@ GL_HD bool identity_lane(const P3VerifyArgs& a, uint32_t p) {
   const E2 is_trans = gl::sub(zeta, gl::e2(a.g_inv));
   const E2 sel[4] = {gl::e2(0), gl::mul(z_h, gl::inv(gl::sub(zeta, gl::e2(1)))), gl::mul(z_h, gl::inv(is_trans)), is_trans};
   const uint32_t W = a.W;
-  auto load = [&](int next, uint32_t c) -> E2 { return ld(open + 2 * ((next ? W : 0) + c)); };
+  const u64* popen = open + 4 * W + 4 * a.Q;   // the preprocessed openings, behind the chunks'
+  auto load = [&](int which, uint32_t c) -> E2 {
+    return (which & 2) ? ld(popen + 2 * (((which & 1) ? a.PW : 0) + c)) : ld(open + 2 * (((which & 1) ? W : 0) + c));
+  };
   const u64* pcoef = a.consts + a.per_coef;
   auto per = [&](uint32_t i) -> E2 { return p3_periodic_at(pcoef + p3_per_offset(i), p3_per_log_period(i), a.k, zeta); };
   const E2 acc = run_air<ExtF>(a.prog, a.n_instr, a.consts, proof + a.o_public, load, per, sel, alpha);
@@ -192,6 +202,16 @@ GL_HD uint32_t fold_lane(const P3VerifyArgs& a, uint32_t p, uint32_t q) {
     ro = gl::add(ro, gl::mul(ap, gl::mul(diff, inv_z)));
     ap = gl::mul(ap, fri_alpha);
   }
+  if (a.PW) {   // the third batch: the preprocessed row at zeta, then at zeta w_n; the powers go on
+    const u64* row_p = row_q + Q2 + 4 * L;
+    const u64* popen = open + 4 * W + 2 * Q2;
+    for (uint32_t pt = 0; pt < 2; pt++)
+      for (uint32_t c = 0; c < a.PW; c++) {
+        const E2 diff = gl::sub(gl::e2(row_p[c]), ld(popen + 2 * (pt * a.PW + c)));
+        ro = gl::add(ro, gl::mul(ap, gl::mul(diff, pt ? inv_zn : inv_z)));
+        ap = gl::mul(ap, fri_alpha);
+      }
+  }
   // every matrix has the height of the LDE domain: the reduced opening enters before round 0 and nothing later
   E2 f = ro;
   const u64* qp = proof + a.o_qp + (size_t)q * a.sz_a;
@@ -217,7 +237,8 @@ GL_HD uint32_t fold_lane(const P3VerifyArgs& a, uint32_t p, uint32_t q) {
 }
 
 // Tree `tree` of query q of proof p: 0 the trace batch, 1 the quotient batch (all chunk matrices have one height: their rows
-// are hashed as one), 2 + r the commit of FRI round r, whose leaf is the pair (own value, sibling value) in index order.
+// are hashed as one), with preprocessed columns (a.nb = 3) 2 their batch, checked against the handle's root; a.nb + r the
+// commit of FRI round r, whose leaf is the pair (own value, sibling value) in index order.
 // hash_iter_slices (commit.rs:23-46) of the leaf, then a compress per sibling; leaf chunks and path steps share ONE
 // permutation call site.
 GL_HD uint32_t merkle_lane(const P3VerifyArgs& a, uint32_t tree, uint32_t p, uint32_t q) {
@@ -229,15 +250,16 @@ GL_HD uint32_t merkle_lane(const P3VerifyArgs& a, uint32_t tree, uint32_t p, uin
   u64 s[12];
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = 0;
-  if (tree < 2) {
-    width = tree ? 2 * a.Q : a.W;
-    leaf = tree ? qo + a.W + 4 * a.L : qo;
+  const bool prep = a.nb == 3 && tree == 2;
+  if (tree < a.nb) {
+    width = prep ? a.PW : tree ? 2 * a.Q : a.W;
+    leaf = qo + (tree ? a.W + 4 * a.L : 0) + (prep ? 2 * a.Q + 4 * a.L : 0);
     sibs = leaf + width;
     depth = a.L;
-    root = proof + 4 * tree;
-    key = P3VKEY_INPUT + 2 * q + tree;
+    root = prep ? a.prep_root : proof + 4 * tree;   // the preprocessed batch's root is the handle's, not the proof's
+    key = P3VKEY_INPUT + a.nb * q + tree;
   } else {
-    const uint32_t r = tree - 2;
+    const uint32_t r = tree - a.nb;
     const u64* step = proof + a.o_qp + (size_t)q * a.sz_a + p3v_round_off(a, r);
     const u64* own = a.folded + (((size_t)p * a.num_queries + q) * a.k + r) * 2;
     idx >>= r;

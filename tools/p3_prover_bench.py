@@ -10,6 +10,13 @@ distinct pow_starts.  For each shape:
 Writes one JSON (default profiles/p3_prover_bench.json) and prints it as one line; exits non-zero if the device form is not
 faster per proof than the host form at the largest log_n of the run.  There is no CPU path: without a GPU the
 first compute call raises.
+
+--prep-machine LOG_N adds the cost of preprocessed columns (include/p25.h, PREPROCESSED COLUMNS) at one shape: a width-1
+machine next0 = local0 + sel c with sel, c two preprocessed columns, against the same width and degree without columns
+(next0 = local0^2 + 3); 2^LOG_N rows, the largest batch of --batches.  Reported under "preprocessed": the one-off build of
+the handle's tables (first p25_p3_prover_preprocessed_commit on a fresh handle, after another handle has loaded the code
+objects; it includes that handle's own constant tables) and the device time per proof with and without columns; the rows
+with columns are asserted equal to the host prover's.
 """
 import argparse
 import json
@@ -39,6 +46,69 @@ def fib_trace(log_n):
     return t
 
 
+def machine(p25, log_n, with_columns):
+    """-> (air, trace[n][1], public values[2]) of the --prep-machine shape."""
+    n = 1 << log_n
+    rng = np.random.default_rng(4242)
+    prep = rng.integers(0, P, size=(n, 2), dtype=np.uint64)
+    prep[:, 0] &= np.uint64(1)
+    air = p25.Air(1, n_public=2, preprocessed=prep if with_columns else None)
+    x = air.local(0)
+    air.when_first_row(air.sub(x, air.public(0)))
+    step = air.add(x, air.mul(air.prep_local(0), air.prep_local(1))) if with_columns else air.add(air.mul(x, x), air.const(3))
+    air.when_transition(air.sub(air.next(0), step))
+    air.when_last_row(air.sub(x, air.public(1)))
+    t = np.zeros((n, 1), dtype=np.uint64)
+    v = 5
+    for i in range(n):
+        t[i, 0] = v
+        v = (v + int(prep[i, 0]) * int(prep[i, 1])) % P if with_columns else (v * v + 3) % P
+    return air, t, np.array([int(t[0, 0]), int(t[n - 1, 0])], dtype=np.uint64)
+
+
+def bench_preprocessed(p25, torch, dev, args):
+    log_n, b = args.prep_machine, max(args.batches)
+    out = {"log_n": log_n, "batch": b, "columns": 2}
+    for with_columns in (True, False):
+        air, trace, pv = machine(p25, log_n, with_columns)
+        pr = p25.P3Prover(air, log_n, 1, args.queries, args.pow_bits)
+        ni = pr.num_inputs
+        d_traces = torch.from_numpy(trace.view(np.int64).copy()).to(dev).reshape(1, -1).repeat(b, 1).contiguous()
+        d_pv = torch.from_numpy(pv.view(np.int64).copy()).to(dev).reshape(1, -1).repeat(b, 1).contiguous()
+        d_inputs = torch.zeros((b, ni), dtype=torch.int64, device=dev)
+        d_status = torch.zeros(b, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+
+        def call():
+            pr.prove_dev(d_traces.data_ptr(), trace.size, b, 0, d_inputs.data_ptr(), ni, d_status.data_ptr(),
+                         d_public_values=d_pv.data_ptr())
+            pr.sync()
+
+        call()   # warm-up: code objects, scratch, the handle's tables
+        if with_columns:
+            fresh = p25.P3Prover(air, log_n, 1, args.queries, args.pow_bits)
+            t0 = time.perf_counter()
+            root = fresh.preprocessed_commit()
+            out["table_build_s"] = time.perf_counter() - t0
+            assert root.tolist() == pr.preprocessed_commit().tolist()
+            fresh.close()
+        times = []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call()
+            times.append(time.perf_counter() - t0)
+        assert d_status.cpu().numpy().tolist() == [0] * b, "device prover reported a failure"
+        if with_columns:
+            row, _cfg = p25.p3_prove_air(air, trace, num_queries=args.queries, pow_bits=args.pow_bits, threads=args.threads,
+                                         public_values=pv)
+            assert np.array_equal(d_inputs.cpu().numpy().view(np.uint64)[b - 1], row), "proof differs from the host prover's"
+        key = "with_columns" if with_columns else "without_columns"
+        out[key] = {"num_inputs": ni, "gpu_call_s": [round(t, 6) for t in times], "gpu_s_per_proof": float(np.median(times)) / b}
+        pr.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-n", type=int, nargs="+", default=[12, 16, 20])
@@ -48,6 +118,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3, help="timed device calls per shape (the median is reported)")
     ap.add_argument("--host-proofs", type=int, default=2, help="distinct host proofs timed and compared per log_n")
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--prep-machine", type=int, default=0, metavar="LOG_N",
+                    help="also measure an AIR with two preprocessed columns at 2^LOG_N rows (0 = off)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "p3_prover_bench.json"))
     args = ap.parse_args()
 
@@ -107,6 +179,8 @@ def main():
                                      "rows_compared_equal": min(len(host_rows), b)})
             del d_traces, d_inputs
         pr.close()
+    if args.prep_machine:
+        result["preprocessed"] = bench_preprocessed(p25, torch, dev, args)
     # the acceptance for speed: per proof, the device form beats the host form of the same run at the largest size
     top = max(args.log_n)
     result["acceptance"] = {"log_n": top, "gpu_faster_than_host": all(sh["host_over_gpu"] > 1.0 for sh in result["shapes"]

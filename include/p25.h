@@ -308,8 +308,69 @@ p25_status p25_circuit_build_p3_verifier(const p25_p3_config* cfg, int32_t air, 
  *              or width = 0 IS the _pc function (same words, same circuit blob, byte for byte).  Every function that takes no
  *              p25_air_preprocessed returns P25_ERR_INVALID_ARG for an AIR that contains op 8 or 9, names the _pp form and
  *              writes nothing.  The batch entry points need no new form: the handle carries the AIR and its columns.
- *   Not here   more than one preprocessed matrix, heights other than the trace's, lookup or permutation arguments over the
- *              columns, the JSON forms. */
+ *   Not here   more than one preprocessed matrix, heights other than the trace's, the JSON forms.
+ *
+ * AUXILIARY COLUMNS (this library's extension, like the three before it: the reference's `Air` trait has none; restated from
+ * LogUp, plonky3's lookup crates and Winterfell's auxiliary trace segments, so UNPINNED against upstream).  A second-phase
+ * trace: the prover draws challenges AFTER the trace is committed, builds running-sum columns in F_p^2 that depend on them,
+ * commits those as a fourth matrix and lets the AIR constrain them.  Range checks, memory consistency, ROM lookups and
+ * "column b is a permutation of column a" are all multiset arguments of this shape.
+ *   Nodes      node.op 10 CHALLENGE(a), a < n_challenges: an element of F_p^2, degree 0.  11 AUX_LOCAL(a) and 12 AUX_NEXT(a),
+ *              a < width: auxiliary column a at the current and the next row, cyclic as NEXT is.  Both COUNT AS DEGREE 1.
+ *   Values     an auxiliary column takes values in F_p^2 on the trace domain.  It is stored and committed as TWO base
+ *              columns, 2 a and 2 a + 1 -- the component split the quotient chunks use.
+ *   Field      an AIR that contains any of the three ops is evaluated in F_p^2 throughout, every other operand embedded;
+ *              an AIR without them is evaluated exactly as before.
+ *   Struct     p25_air cannot grow, so the description travels beside it in p25_air_aux: n_challenges, width and, per
+ *              column j, two node indices (num_j, den_j), copied by every function that takes them.
+ *   Filling    column j is the running sum of t_j(i) = num_j(i) / den_j(i) in F_p^2: the two nodes are evaluated on trace
+ *              row i (NEXT is row (i + 1) mod n; preprocessed, periodic, public and challenge operands are allowed),
+ *              S_j(0) = 0 and S_j(i + 1) = S_j(i) + t_j(i).  The prover fills it; the caller passes the main trace only.
+ *   Constraints stay the AIR's own.  The usual pair is: first row, AUX_LOCAL(j) = 0; every row,
+ *              (AUX_NEXT(j) - AUX_LOCAL(j)) * den_j - num_j = 0.  Because NEXT is cyclic, the second constraint on the LAST
+ *              row says S_j(0) - S_j(n - 1) = t_j(n - 1), i.e. that the total of t_j over all rows is ZERO: that is the
+ *              LogUp statement (sum of m / (g - t) - 1 / (g - f) vanishes iff the looked-up multiset is the table's).
+ *   Refusals   P25_ERR_INVALID_ARG with the limit named: a num or den that depends on op 11 or 12; a challenge, column or
+ *              node index out of range; n_challenges > 0 with width = 0; more than P25_AIR_MAX_CHALLENGES (8) challenges or
+ *              P25_AIR_MAX_AUX (16) columns.  width > 0 with n_challenges = 0 is allowed: a deterministic running sum.
+ *   Zero den   a den_j(i) = 0 fails that proof: the host prover returns P25_ERR_INVALID_ARG and names column and row.
+ *   Transcript observe the trace root, the preprocessed root if any and the public values, as before.  Then (1) sample
+ *              n_challenges extension elements in index order, (2) build the auxiliary matrix and commit it -- the
+ *              Poseidon2 MMCS over the 2 AW columns' LDE on 7 H_{n 2^log_blowup} in bit-reversed order, the trace's commit
+ *              -- (3) observe its root, (4) sample alpha.  Everything after is unchanged; without auxiliary columns the
+ *              transcript is word for word what it was.
+ *   Words      p25_p3_config does not change.  Two insertions: behind prep_next,
+ *                aux_commit u64[4] | aux_local E[2 AW] | aux_next E[2 AW]
+ *              and as the LAST batch of every query {row u64[2 AW], path H[log_n + log_blowup]}.  num_inputs grows by
+ *              4 + 8 AW + num_queries (2 AW + 4 (log_n + log_blowup)).  The JSON forms do not cover these proofs.
+ *   Openings   the batches run in the order trace, quotient, preprocessed (if any), auxiliary.  The auxiliary matrix has
+ *              the trace's height: it shares the trace's log_height slot and its alpha powers continue where the slot
+ *              stands.  At zeta column a is recomposed as o[2 a] + X o[2 a + 1], X the extension's generator, as the chunks
+ *              are.
+ *   Circuit    p25_circuit_build_p3_verifier_air_ax samples the challenges in the in-circuit challenger at the place
+ *              stated, observes aux_commit -- a PROOF TARGET, not a constant -- and passes one more (commitment, matrices,
+ *              points) entry; no new gate kind, no new generator.
+ *   Interface  p25_p3_prove_air_ax, p25_p3_prover_create_ax, p25_circuit_build_p3_verifier_air_ax: each is the _pp function
+ *              plus `aux`, and with aux = NULL, or width = 0 and n_challenges = 0, IS the _pp function (same words, same
+ *              circuit blob, byte for byte).  Every function that takes no p25_air_aux returns P25_ERR_INVALID_ARG for an
+ *              AIR that contains op 10, 11 or 12, names the _ax form and writes nothing.
+ *   Device     a p25_p3_prover made by p25_p3_prover_create_ax runs a challenge phase between the trace commit and the
+ *              quotient: the chain samples the challenges; a term kernel (one lane per row and proof, ONE F_p^2 inversion
+ *              per row over the row's AW denominators) writes t_j(i); an exclusive prefix sum in F_p^2 over the rows --
+ *              block scan, scan of the block totals, add-back, three launches, no block waits on another -- gives the
+ *              columns; they are committed with the trace's launches; the chain observes the root and samples alpha.  The
+ *              quotient of such an AIR runs in an F_p^2 kernel of its own.  A zero denominator gives that proof status
+ *              P25_ERR_INVALID_ARG and zero words, like a failed identity.  Per proof the group scratch grows by
+ *              4 AW 2^log_n + (2 AW + 8) 2^(log_n + log_blowup) words and the scan's block totals; a handle with auxiliary
+ *              AND preprocessed columns keeps the preprocessed VALUES (PW 2^log_n words) beside their tables, counted by
+ *              p25_p3_prover_scratch_bytes under proving_out with them.
+ *   Verifying  p25_p3_verify_batch[_dev] check the last batch against the PROOF's aux_commit.  With nb input batches per
+ *              query, nb = 2 + (PW > 0) + (AW > 0), the input keys are 2 + nb q + b and the FRI keys start at
+ *              F = 2 + nb num_queries; a failing auxiliary batch is P25_P3_REJECT_INPUT_MERKLE (32).  The verifier's
+ *              scratch per proof grows by 2 n_challenges words for such handles; for all other handles every key and the
+ *              scratch formula are what they were.
+ *   Not here   more than one auxiliary phase, auxiliary columns of other heights, cross-table buses (a non-zero, public
+ *              total), typed base / extension slots that would spare the all-extension quotient, the JSON forms. */
 enum { P25_AIR_MAX_PUBLIC = 64 };
 enum { P25_AIR_MAX_PERIODIC = 32, P25_AIR_MAX_LOG_PERIOD = 8 };
 typedef struct {
@@ -335,6 +396,12 @@ typedef struct {
   uint32_t log_n;          /* must equal the trace's log height */
   const uint64_t* values;  /* [2^log_n][width], row-major like a trace, every word < p */
 } p25_air_preprocessed;
+enum { P25_AIR_MAX_CHALLENGES = 8, P25_AIR_MAX_AUX = 16 };
+typedef struct { uint32_t num, den; } p25_air_aux_column;      /* node indices */
+typedef struct {
+  uint32_t n_challenges, width;          /* 0..P25_AIR_MAX_CHALLENGES, 0..P25_AIR_MAX_AUX */
+  const p25_air_aux_column* columns;     /* [width] */
+} p25_air_aux;
 /* p3_verify_proof for a user AIR: `builder.p3_verify_proof::<H>(proof, &air, fri_config)` with any `impl Air`
  * (src/p3/mod.rs:66-94, 239-250).  cfg->trace_width must equal air->width. */
 p25_status p25_circuit_build_p3_verifier_air(const p25_p3_config* cfg, const p25_air* air, p25_circuit** out);
@@ -346,6 +413,11 @@ p25_status p25_circuit_build_p3_verifier_air_pc(const p25_p3_config* cfg, const 
  * computed here (as p25_p3_preprocessed_commit does) and held by the circuit as four constants. */
 p25_status p25_circuit_build_p3_verifier_air_pp(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
                                                 const p25_air_preprocessed* preprocessed, p25_circuit** out);
+/* The same for an AIR with challenges and auxiliary columns (AUXILIARY COLUMNS above); any of `periodic`, `preprocessed` and
+ * `aux` may be NULL. */
+p25_status p25_circuit_build_p3_verifier_air_ax(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
+                                                const p25_air_preprocessed* preprocessed, const p25_air_aux* aux,
+                                                p25_circuit** out);
 /* Native plonky3 prover (see p25_p3_prove_fibonacci) for a user AIR and its trace, trace[row * width + col],
  * 2^log_n rows.  P25_ERR_INVALID_ARG if the trace does not satisfy the AIR. */
 p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t num_queries,
@@ -381,6 +453,15 @@ p25_status p25_p3_prove_air_pp(const p25_air* air, const uint64_t* trace, const 
                                const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed, int32_t log_n,
                                int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start, int32_t threads,
                                uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out);
+/* p25_p3_prove_air_pp for an AIR with challenges and auxiliary columns (AUXILIARY COLUMNS above); any of `periodic`,
+ * `preprocessed` and `aux` may be NULL.  `trace` is the main trace alone: the auxiliary columns are built here.  *n_out grows
+ * by 4 + 8 AW + num_queries (2 AW + 4 (log_n + log_blowup)), AW = aux->width.  P25_ERR_INVALID_ARG if the trace does not
+ * satisfy the AIR (for the usual constraint pair: if the terms do not sum to zero) or a denominator is zero on some row. */
+p25_status p25_p3_prove_air_ax(const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
+                               const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed,
+                               const p25_air_aux* aux, int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits,
+                               uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap, size_t* n_out,
+                               p25_p3_config* cfg_out);
 /* The commitment of preprocessed columns under `log_blowup` (1..4): verifying-key data, 4 words.  Host only; the host
  * prover's MMCS.  width 0 is P25_ERR_INVALID_ARG here (there is nothing to commit), as are the limits named above. */
 p25_status p25_p3_preprocessed_commit(const p25_air_preprocessed* preprocessed, int32_t log_blowup, int32_t threads,
@@ -735,6 +816,16 @@ p25_status p25_p3_prover_create_pc(const p25_air* air, const p25_air_periodic* p
  * NULL, preprocessed->log_n is checked against log_n here, and the matrix is copied.  Host only like the others. */
 p25_status p25_p3_prover_create_pp(const p25_air* air, const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed,
                                    int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits, p25_p3_prover** out);
+/* The same for an AIR with challenges and auxiliary columns (AUXILIARY COLUMNS above); any of `periodic`, `preprocessed` and
+ * `aux` may be NULL, and with aux = NULL (or empty) this IS p25_p3_prover_create_pp. */
+p25_status p25_p3_prover_create_ax(const p25_air* air, const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed,
+                                   const p25_air_aux* aux, int32_t log_n, int32_t log_blowup, int32_t num_queries,
+                                   int32_t pow_bits, p25_p3_prover** out);
+/* Measurement aid: the device time in ms (HIP events on the call's stream) that the challenge phase took in the LAST group
+ * of proofs this handle proved -- term kernel, prefix sum, the auxiliary matrix's transforms and tree, the chain launch that
+ * observes its root.  Waits for that group.  P25_ERR_INVALID_ARG for a handle without auxiliary columns or before its first
+ * proving call. */
+p25_status p25_p3_prover_aux_stage_ms(p25_p3_prover* p, double* ms_out);
 /* The 4 words of the preprocessed commitment as the handle computed them on the device (on this call, if no compute call
  * has done so yet): word for word what p25_p3_preprocessed_commit returns.  P25_ERR_INVALID_ARG for a handle without
  * preprocessed columns, then P25_ERR_NO_DEVICE without a GPU. */

@@ -66,6 +66,14 @@ class AirPreprocessedC(C.Structure):
     _fields_ = [("width", C.c_uint32), ("log_n", C.c_uint32), ("values", C.POINTER(C.c_uint64))]
 
 
+class AirAuxColumnC(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("den", C.c_uint32)]
+
+
+class AirAuxC(C.Structure):
+    _fields_ = [("n_challenges", C.c_uint32), ("width", C.c_uint32), ("columns", C.POINTER(AirAuxColumnC))]
+
+
 class Air:
     """An AIR as an expression DAG (p25_air in include/p25.h): the data form of the reference's `Air` trait
     (src/p3/air.rs:10-18).  Build it like the trait's `eval` body:
@@ -81,11 +89,16 @@ class Air:
 
     preprocessed: uint64[2^log_n][PW], the AIR's preprocessed columns (include/p25.h, PREPROCESSED COLUMNS): a matrix as
     high as the trace, committed once (the commitment is verifying-key data), read with air.prep_local(a) / air.prep_next(a).
+
+    aux: the number of challenges (include/p25.h, AUXILIARY COLUMNS), sampled after the trace is committed and read with
+    air.challenge(i).  air.aux_column(num, den) adds an auxiliary column -- the running sum over the rows of num / den in
+    F_p^2, built by the prover -- and returns its index, read with air.aux_local(a) / air.aux_next(a).
     """
     ALWAYS, FIRST_ROW, LAST_ROW, TRANSITION = 0, 1, 2, 3
 
-    def __init__(self, width, n_public=0, periodic=None, preprocessed=None):
+    def __init__(self, width, n_public=0, periodic=None, preprocessed=None, aux=0):
         self.width, self.n_public, self.nodes, self.constraints = width, int(n_public), [], []
+        self.n_challenges, self.aux_columns = int(aux), []
         self.preprocessed = None
         if preprocessed is not None:
             pp = np.ascontiguousarray(preprocessed, dtype=np.uint64)
@@ -105,6 +118,14 @@ class Air:
     def periodic(self, i): return self._n(7, int(i))
     def prep_local(self, a): return self._n(8, int(a))
     def prep_next(self, a): return self._n(9, int(a))
+    def challenge(self, i): return self._n(10, int(i))
+    def aux_local(self, a): return self._n(11, int(a))
+    def aux_next(self, a): return self._n(12, int(a))
+
+    def aux_column(self, num, den):
+        self.aux_columns.append((int(num), int(den)))
+        return len(self.aux_columns) - 1
+
     def add(self, x, y): return self._n(3, x, y)
     def sub(self, x, y): return self._n(4, x, y)
     def mul(self, x, y): return self._n(5, x, y)
@@ -149,6 +170,15 @@ class Air:
         c._keep = (lp, vals)
         return c
 
+
+    def aux_to_c(self):
+        """p25_air_aux of the challenges and auxiliary columns (for the _ax entry points), or None without either."""
+        if not self.n_challenges and not self.aux_columns:
+            return None
+        cols = (AirAuxColumnC * max(1, len(self.aux_columns)))(*[AirAuxColumnC(n, d) for n, d in self.aux_columns])
+        c = AirAuxC(self.n_challenges, len(self.aux_columns), cols)
+        c._keep = cols
+        return c
 
     def preprocessed_to_c(self):
         """p25_air_preprocessed of the columns (for the _pp entry points), or None without columns."""
@@ -308,6 +338,11 @@ EXPORTED_SYMBOLS = {
                                   C.POINTER(sz), C.POINTER(P3Config)]),
     "p25_p3_prover_create_pp": (i32, [C.POINTER(AirC), vp, vp, i32, i32, i32, i32, C.POINTER(vp)]),
     "p25_circuit_build_p3_verifier_air_pp": (i32, [C.POINTER(P3Config), C.POINTER(AirC), vp, vp, C.POINTER(vp)]),
+    "p25_p3_prove_air_ax": (i32, [C.POINTER(AirC), vp, vp, vp, vp, vp, i32, i32, i32, i32, C.c_uint64, i32, vp, sz,
+                                  C.POINTER(sz), C.POINTER(P3Config)]),
+    "p25_p3_prover_create_ax": (i32, [C.POINTER(AirC), vp, vp, vp, i32, i32, i32, i32, C.POINTER(vp)]),
+    "p25_circuit_build_p3_verifier_air_ax": (i32, [C.POINTER(P3Config), C.POINTER(AirC), vp, vp, vp, C.POINTER(vp)]),
+    "p25_p3_prover_aux_stage_ms": (i32, [vp, C.POINTER(C.c_double)]),
     "p25_p3_preprocessed_commit": (i32, [vp, i32, i32, vp]),
     "p25_p3_prover_preprocessed_commit": (i32, [vp, vp]),
     "p25_p3_prover_sync": (i32, [vp]),
@@ -572,7 +607,8 @@ def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=
     """Native plonky3 proof of `air` (binding.Air) on `trace` (uint64[2^log_n][width]) -> (inputs, P3Config).
     log_blowup: FriConfig.log_blowup (1 = the reference's; 2 / 3 for AIRs of constraint degree up to 5 / 9).
     public_values: the air.n_public values of this proof; they end up as the last words of `inputs`.
-    An AIR with periodic columns goes through p25_p3_prove_air_pc, one with preprocessed columns through p25_p3_prove_air_pp."""
+    An AIR with periodic columns goes through p25_p3_prove_air_pc, one with preprocessed columns through p25_p3_prove_air_pp,
+    one with challenges or auxiliary columns through p25_p3_prove_air_ax."""
     threads = threads or min(16, os.cpu_count() or 1)
     t = np.ascontiguousarray(trace, dtype=np.uint64)
     if t.ndim != 2 or t.shape[1] != air.width or t.shape[0] & (t.shape[0] - 1) or t.shape[0] < 2:
@@ -582,6 +618,13 @@ def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=
     cfg = P3Config()
     pc = air.periodic_to_c()
     pp = air.preprocessed_to_c()
+    ax = air.aux_to_c()
+    if ax is not None:
+        pv = _public_rows(public_values, 1, air.n_public)
+        out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_ax(C.byref(ac), _ptr(t), _ptr(pv), _ref(pc), _ref(pp), C.byref(ax),
+                                                                   log_n, log_blowup, num_queries, pow_bits, pow_start, threads,
+                                                                   buf, cap, n, C.byref(cfg)), np.uint64)
+        return out, cfg
     if pp is not None:
         pv = _public_rows(public_values, 1, air.n_public)
         out = _sized(lambda buf, cap, n: lib().p25_p3_prove_air_pp(C.byref(ac), _ptr(t), _ptr(pv), _ref(pc), C.byref(pp), log_n,
@@ -615,7 +658,11 @@ class P3Prover:
         h = vp()
         pc = air.periodic_to_c()
         pp = air.preprocessed_to_c()
-        if pp is not None:
+        ax = air.aux_to_c()
+        if ax is not None:
+            _check(lib().p25_p3_prover_create_ax(C.byref(ac), _ref(pc), _ref(pp), C.byref(ax), log_n, log_blowup, num_queries,
+                                                 pow_bits, C.byref(h)))
+        elif pp is not None:
             _check(lib().p25_p3_prover_create_pp(C.byref(ac), _ref(pc), C.byref(pp), log_n, log_blowup, num_queries, pow_bits,
                                                  C.byref(h)))
         elif pc is None:
@@ -696,6 +743,12 @@ class P3Prover:
     def sync(self):
         _check(lib().p25_p3_prover_sync(self._h))
 
+    def aux_stage_ms(self):
+        """Device ms (HIP events) of the challenge phase in the last group of proofs this handle proved."""
+        ms = C.c_double(0)
+        _check(lib().p25_p3_prover_aux_stage_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def set_scratch_budget(self, nbytes):
         """Bytes of device scratch a group of proofs may take (0 = the default, 12 GiB); at least one proof per group."""
         _check(lib().p25_p3_prover_set_scratch_budget(self._h, int(nbytes)))
@@ -736,6 +789,10 @@ class Circuit:
         ac = air.to_c()
         pc = air.periodic_to_c()
         pp = air.preprocessed_to_c()
+        ax = air.aux_to_c()
+        if ax is not None:
+            return _new_circuit(lib().p25_circuit_build_p3_verifier_air_ax, C.byref(cfg), C.byref(ac), _ref(pc), _ref(pp),
+                                C.byref(ax))
         if pp is not None:
             return _new_circuit(lib().p25_circuit_build_p3_verifier_air_pp, C.byref(cfg), C.byref(ac), _ref(pc), C.byref(pp))
         if pc is not None:

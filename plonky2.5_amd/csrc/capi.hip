@@ -297,9 +297,11 @@ P3Config checked_p3_config(const p25_p3_config* cfg) {
 }
 // `periodic`: the AIR's periodic columns (null: none), copied.  `pc_form`: set by the entry points that take no columns,
 // the name of the one that does -- they refuse an AIR that reads a column (op 7) and name it.  `prep`, `pp_form`: the same
-// for the preprocessed columns (ops 8 and 9) and the _pp entry points.
+// for the preprocessed columns (ops 8 and 9) and the _pp entry points.  `aux`, `ax_form`: the same for the challenges and
+// auxiliary columns (ops 10 to 12) and the _ax entry points.
 AirProgram air_from_c(const p25_air* air, const p25_air_periodic* periodic = nullptr, const char* pc_form = nullptr,
-                      const p25_air_preprocessed* prep = nullptr, const char* pp_form = nullptr) {
+                      const p25_air_preprocessed* prep = nullptr, const char* pp_form = nullptr,
+                      const p25_air_aux* aux = nullptr, const char* ax_form = nullptr) {
   if (!air || !air->nodes || !air->constraints) throw std::invalid_argument("null AIR");
   if (air->n_nodes > (1u << 20) || air->n_constraints > (1u << 16)) throw std::invalid_argument("AIR too large");
   AirProgram p;
@@ -311,6 +313,19 @@ AirProgram air_from_c(const p25_air* air, const p25_air_periodic* periodic = nul
     for (uint32_t i = 0; i < air->n_nodes; i++)
       if (air->nodes[i].op == AirProgram::PREP_LOCAL || air->nodes[i].op == AirProgram::PREP_NEXT)
         throw std::invalid_argument(std::string("the AIR reads preprocessed columns (node op 8 PREP_LOCAL / 9 PREP_NEXT): use ") + pp_form);
+  if (ax_form)
+    for (uint32_t i = 0; i < air->n_nodes; i++)
+      if (air->nodes[i].op >= AirProgram::CHALLENGE && air->nodes[i].op <= AirProgram::AUX_NEXT)
+        throw std::invalid_argument(std::string("the AIR reads challenges or auxiliary columns (node op 10 CHALLENGE / 11 AUX_LOCAL / 12 AUX_NEXT): use ") + ax_form);
+  if (aux && (aux->width || aux->n_challenges)) {
+    if (aux->n_challenges > (uint32_t)AirProgram::MAX_CHALLENGES)
+      throw std::invalid_argument("AIR: more than 8 challenges (P25_AIR_MAX_CHALLENGES)");
+    if (aux->width > (uint32_t)AirProgram::MAX_AUX)
+      throw std::invalid_argument("AIR: more than 16 auxiliary columns (P25_AIR_MAX_AUX)");
+    if (aux->width && !aux->columns) throw std::invalid_argument("null auxiliary columns");
+    p.aux.n_challenges = aux->n_challenges;
+    for (uint32_t j = 0; j < aux->width; j++) p.aux.columns.push_back(AirProgram::AuxColumn{aux->columns[j].num, aux->columns[j].den});
+  }
   if (prep && prep->width) {
     if (prep->width > (uint32_t)AirProgram::MAX_PREPROCESSED)
       throw std::invalid_argument("AIR: more than 64 preprocessed columns (P25_AIR_MAX_PREPROCESSED)");
@@ -629,13 +644,15 @@ p25_status p25_circuit_build_p3_verifier(const p25_p3_config* cfg, int32_t air, 
   });
 }
 // p25_circuit_build_p3_verifier_air (form 0: refuses an AIR that reads periodic or preprocessed columns), its _pc form
-// (1: refuses preprocessed columns) and its _pp form (2)
+// (1: refuses preprocessed columns), its _pp form (2: refuses challenges and auxiliary columns) and its _ax form (3)
 static p25_status p3_build_verifier_air(int form, const p25_p3_config* cfg, const p25_air* air,
-                                        const p25_air_periodic* periodic, const p25_air_preprocessed* prep, p25_circuit** out) {
+                                        const p25_air_periodic* periodic, const p25_air_preprocessed* prep,
+                                        const p25_air_aux* aux, p25_circuit** out) {
   return host_guarded([&]() -> p25_status {
     if (!cfg || !air || !out) throw std::invalid_argument("null argument");
     AirProgram prog = air_from_c(air, periodic, form >= 1 ? nullptr : "p25_circuit_build_p3_verifier_air_pc", prep,
-                                 form >= 2 ? nullptr : "p25_circuit_build_p3_verifier_air_pp");
+                                 form >= 2 ? nullptr : "p25_circuit_build_p3_verifier_air_pp", aux,
+                                 form >= 3 ? nullptr : "p25_circuit_build_p3_verifier_air_ax");
     prog.check_periodic(cfg->log_trace_height);
     prog.check_preprocessed(cfg->log_trace_height);
     // the chunk count follows from the AIR (uni-stark get_log_quotient_degree): the shape must say the same
@@ -647,15 +664,20 @@ static p25_status p3_build_verifier_air(int form, const p25_p3_config* cfg, cons
   });
 }
 p25_status p25_circuit_build_p3_verifier_air(const p25_p3_config* cfg, const p25_air* air, p25_circuit** out) {
-  return p3_build_verifier_air(0, cfg, air, nullptr, nullptr, out);
+  return p3_build_verifier_air(0, cfg, air, nullptr, nullptr, nullptr, out);
 }
 p25_status p25_circuit_build_p3_verifier_air_pc(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
                                                 p25_circuit** out) {
-  return p3_build_verifier_air(1, cfg, air, periodic, nullptr, out);
+  return p3_build_verifier_air(1, cfg, air, periodic, nullptr, nullptr, out);
 }
 p25_status p25_circuit_build_p3_verifier_air_pp(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
                                                 const p25_air_preprocessed* preprocessed, p25_circuit** out) {
-  return p3_build_verifier_air(2, cfg, air, periodic, preprocessed, out);
+  return p3_build_verifier_air(2, cfg, air, periodic, preprocessed, nullptr, out);
+}
+p25_status p25_circuit_build_p3_verifier_air_ax(const p25_p3_config* cfg, const p25_air* air, const p25_air_periodic* periodic,
+                                                const p25_air_preprocessed* preprocessed, const p25_air_aux* aux,
+                                                p25_circuit** out) {
+  return p3_build_verifier_air(3, cfg, air, periodic, preprocessed, aux, out);
 }
 
 p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t num_queries,
@@ -665,15 +687,16 @@ p25_status p25_p3_prove_air(const p25_air* air, const uint64_t* trace, int32_t l
 }
 // p25_p3_prove_air_ex (pv_form false: refuses an AIR with public values), p25_p3_prove_air_pv and p25_p3_prove_air_pc
 // (pc_form: the name of the form that takes periodic columns, for the two that do not and refuse an AIR reading one;
-// pp_form: the same for preprocessed columns, null in p25_p3_prove_air_pp alone)
-static p25_status p3_prove_air_host(bool pv_form, const char* pc_form, const char* pp_form, const p25_air* air,
+// pp_form: the same for preprocessed columns, null in p25_p3_prove_air_pp and _ax; ax_form: the same for challenges and
+// auxiliary columns, null in p25_p3_prove_air_ax alone)
+static p25_status p3_prove_air_host(bool pv_form, const char* pc_form, const char* pp_form, const char* ax_form, const p25_air* air,
                                     const uint64_t* trace, const uint64_t* public_values, const p25_air_periodic* periodic,
-                                    const p25_air_preprocessed* prep,
+                                    const p25_air_preprocessed* prep, const p25_air_aux* aux,
                                     int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start,
                                     int32_t threads, uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out) {
   return host_guarded([&]() -> p25_status {
     if (!air || !n_out) throw std::invalid_argument("null argument");
-    AirProgram prog = air_from_c(air, periodic, pc_form, prep, pp_form);
+    AirProgram prog = air_from_c(air, periodic, pc_form, prep, pp_form, aux, ax_form);
     prog.check_periodic(log_n);
     prog.check_preprocessed(log_n);
     if (!pv_form && prog.n_public > 0)
@@ -701,33 +724,42 @@ static p25_status p3_prove_air_host(bool pv_form, const char* pc_form, const cha
       }
     };
     return p3_prove_out(prm, pc, prove, inputs_out, cap, n_out, cfg_out,
-                        (size_t)prog.n_public + p3_preprocessed_words((int)prog.prep.width, log_n, log_blowup, num_queries));
+                        (size_t)prog.n_public + p3_preprocessed_words((int)prog.prep.width, log_n, log_blowup, num_queries) +
+                            p3_aux_words((int)prog.aux.width(), log_n, log_blowup, num_queries));
   });
 }
 p25_status p25_p3_prove_air_ex(const p25_air* air, const uint64_t* trace, int32_t log_n, int32_t log_blowup, int32_t num_queries,
                                int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
                                size_t* n_out, p25_p3_config* cfg_out) {
-  return p3_prove_air_host(false, "p25_p3_prove_air_pc", "p25_p3_prove_air_pp", air, trace, nullptr, nullptr, nullptr, log_n, log_blowup, num_queries, pow_bits,
+  return p3_prove_air_host(false, "p25_p3_prove_air_pc", "p25_p3_prove_air_pp", "p25_p3_prove_air_ax", air, trace, nullptr, nullptr, nullptr, nullptr, log_n, log_blowup, num_queries, pow_bits,
                            pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
 p25_status p25_p3_prove_air_pv(const p25_air* air, const uint64_t* trace, const uint64_t* public_values, int32_t log_n,
                                int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start, int32_t threads,
                                uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out) {
-  return p3_prove_air_host(true, "p25_p3_prove_air_pc", "p25_p3_prove_air_pp", air, trace, public_values, nullptr, nullptr, log_n, log_blowup, num_queries,
+  return p3_prove_air_host(true, "p25_p3_prove_air_pc", "p25_p3_prove_air_pp", "p25_p3_prove_air_ax", air, trace, public_values, nullptr, nullptr, nullptr, log_n, log_blowup, num_queries,
                            pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
 p25_status p25_p3_prove_air_pc(const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
                                const p25_air_periodic* periodic, int32_t log_n, int32_t log_blowup, int32_t num_queries,
                                int32_t pow_bits, uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap,
                                size_t* n_out, p25_p3_config* cfg_out) {
-  return p3_prove_air_host(true, nullptr, "p25_p3_prove_air_pp", air, trace, public_values, periodic, nullptr, log_n, log_blowup,
+  return p3_prove_air_host(true, nullptr, "p25_p3_prove_air_pp", "p25_p3_prove_air_ax", air, trace, public_values, periodic, nullptr, nullptr, log_n, log_blowup,
                            num_queries, pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
 p25_status p25_p3_prove_air_pp(const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
                                const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed, int32_t log_n,
                                int32_t log_blowup, int32_t num_queries, int32_t pow_bits, uint64_t pow_start, int32_t threads,
                                uint64_t* inputs_out, size_t cap, size_t* n_out, p25_p3_config* cfg_out) {
-  return p3_prove_air_host(true, nullptr, nullptr, air, trace, public_values, periodic, preprocessed, log_n, log_blowup,
+  return p3_prove_air_host(true, nullptr, nullptr, "p25_p3_prove_air_ax", air, trace, public_values, periodic, preprocessed, nullptr, log_n, log_blowup,
+                           num_queries, pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
+}
+p25_status p25_p3_prove_air_ax(const p25_air* air, const uint64_t* trace, const uint64_t* public_values,
+                               const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed,
+                               const p25_air_aux* aux, int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits,
+                               uint64_t pow_start, int32_t threads, uint64_t* inputs_out, size_t cap, size_t* n_out,
+                               p25_p3_config* cfg_out) {
+  return p3_prove_air_host(true, nullptr, nullptr, nullptr, air, trace, public_values, periodic, preprocessed, aux, log_n, log_blowup,
                            num_queries, pow_bits, pow_start, threads, inputs_out, cap, n_out, cfg_out);
 }
 p25_status p25_p3_preprocessed_commit(const p25_air_preprocessed* preprocessed, int32_t log_blowup, int32_t threads,
@@ -749,14 +781,15 @@ p25_status p25_p3_preprocessed_commit(const p25_air_preprocessed* preprocessed, 
 }
 
 // ---- the plonky3 prover on the device -------------------------------------------------------------------------------
-// form: 0 p25_p3_prover_create, 1 its _pc form, 2 its _pp form (as p3_build_verifier_air)
+// form: 0 p25_p3_prover_create, 1 its _pc form, 2 its _pp form, 3 its _ax form (as p3_build_verifier_air)
 static p25_status p3_prover_create(int form, const p25_air* air, const p25_air_periodic* periodic,
-                                   const p25_air_preprocessed* prep, int32_t log_n, int32_t log_blowup, int32_t num_queries,
+                                   const p25_air_preprocessed* prep, const p25_air_aux* aux, int32_t log_n, int32_t log_blowup, int32_t num_queries,
                                    int32_t pow_bits, p25_p3_prover** out) {
   return host_guarded([&]() -> p25_status {
     if (!air || !out) throw std::invalid_argument("null argument");
     const AirProgram prog = air_from_c(air, periodic, form >= 1 ? nullptr : "p25_p3_prover_create_pc", prep,
-                                       form >= 2 ? nullptr : "p25_p3_prover_create_pp");
+                                       form >= 2 ? nullptr : "p25_p3_prover_create_pp", aux,
+                                       form >= 3 ? nullptr : "p25_p3_prover_create_ax");
     std::unique_ptr<p25_p3_prover> h(new p25_p3_prover());
     h->dev.reset(new P3ProverDev(prog, log_n, log_blowup, num_queries, pow_bits));
     *out = h.release();
@@ -765,15 +798,20 @@ static p25_status p3_prover_create(int form, const p25_air* air, const p25_air_p
 }
 p25_status p25_p3_prover_create(const p25_air* air, int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits,
                                 p25_p3_prover** out) {
-  return p3_prover_create(0, air, nullptr, nullptr, log_n, log_blowup, num_queries, pow_bits, out);
+  return p3_prover_create(0, air, nullptr, nullptr, nullptr, log_n, log_blowup, num_queries, pow_bits, out);
 }
 p25_status p25_p3_prover_create_pc(const p25_air* air, const p25_air_periodic* periodic, int32_t log_n, int32_t log_blowup,
                                    int32_t num_queries, int32_t pow_bits, p25_p3_prover** out) {
-  return p3_prover_create(1, air, periodic, nullptr, log_n, log_blowup, num_queries, pow_bits, out);
+  return p3_prover_create(1, air, periodic, nullptr, nullptr, log_n, log_blowup, num_queries, pow_bits, out);
 }
 p25_status p25_p3_prover_create_pp(const p25_air* air, const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed,
                                    int32_t log_n, int32_t log_blowup, int32_t num_queries, int32_t pow_bits, p25_p3_prover** out) {
-  return p3_prover_create(2, air, periodic, preprocessed, log_n, log_blowup, num_queries, pow_bits, out);
+  return p3_prover_create(2, air, periodic, preprocessed, nullptr, log_n, log_blowup, num_queries, pow_bits, out);
+}
+p25_status p25_p3_prover_create_ax(const p25_air* air, const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed,
+                                   const p25_air_aux* aux, int32_t log_n, int32_t log_blowup, int32_t num_queries,
+                                   int32_t pow_bits, p25_p3_prover** out) {
+  return p3_prover_create(3, air, periodic, preprocessed, aux, log_n, log_blowup, num_queries, pow_bits, out);
 }
 p25_status p25_p3_prover_preprocessed_commit(p25_p3_prover* p, uint64_t commit_out[4]) {
   return host_guarded([&]() -> p25_status {
@@ -903,6 +941,14 @@ p25_status p25_p3_verify_batch_dev(p25_p3_prover* p, const uint64_t* d_inputs, s
     if (s != P25_OK) return s;
     P25_LOCK(p);
     p->dev->verify_dev(d_inputs, n_proofs, input_stride_words, d_status, (hipStream_t)stream);
+    return P25_OK;
+  });
+}
+p25_status p25_p3_prover_aux_stage_ms(p25_p3_prover* p, double* ms_out) {
+  return host_guarded([&]() -> p25_status {
+    if (!p || !ms_out) throw std::invalid_argument("null argument");
+    P25_LOCK(p);
+    *ms_out = p->dev->aux_stage_ms();
     return P25_OK;
   });
 }

@@ -207,6 +207,13 @@ __global__ __launch_bounds__(64) void k_p3_chain(P3Shape sh, P3Bufs b, uint32_t 
       if (phase == P3_CH_TRACE) {   // the proof's public values, between the trace root and alpha (p3_prover.cpp)
         const u64* pub = b.pub + (size_t)g * sh.n_public;
         for (uint32_t i = 0; i < sh.n_public; i++) ch.observe(pub[i]);
+        if (sh.AW) {   // the challenge phase: the challenges to the header; alpha waits for the auxiliary root (P3_CH_AUX)
+          for (uint32_t i = 0; i < sh.NC; i++) {
+            const E2 c = ch.sample_ext();
+            if (lane == 0) st_e2(hdr + sh.o_chal + 2 * i, c);
+          }
+          break;
+        }
       }
       const E2 c = ch.sample_ext();
       if (lane == 0) {
@@ -222,13 +229,22 @@ __global__ __launch_bounds__(64) void k_p3_chain(P3Shape sh, P3Bufs b, uint32_t 
       }
       break;
     }
+    case P3_CH_AUX: {   // the auxiliary root: to the header, observed, then alpha
+      const u64* root = b.atree + (size_t)g * 8 * N2 + p3_level_off(N2, sh.L);
+      u64* dst = hdr + sh.o_aux;
+      if (lane < 4) dst[lane] = root[lane];
+      ch.observe_digest(root);
+      const E2 c = ch.sample_ext();
+      if (lane == 0) st_e2(s->alpha, c);
+      break;
+    }
     case P3_CH_FRI_ALPHA: {
       const E2 fa = ch.sample_ext();
       if (lane == 0) {
         st_e2(s->fri_alpha, fa);
         u64* ap = hdr + sh.o_apow;
         E2 p = gl::e2(1);
-        for (uint32_t i = 0; i < 2 * sh.W + 2 * sh.Q + 2 * sh.PW; i++) {
+        for (uint32_t i = 0; i < 2 * sh.W + 2 * sh.Q + 2 * sh.PW + 4 * sh.AW; i++) {
           st_e2(ap + 2 * i, p);
           p = gl::mul(p, fa);
         }
@@ -268,9 +284,126 @@ __global__ __launch_bounds__(64) void k_p3_chain(P3Shape sh, P3Bufs b, uint32_t 
 // ---------------------------------------------------------------------------------------------------------------------
 // The AIR program (run_air: p3_air_run.h)
 // ---------------------------------------------------------------------------------------------------------------------
+// The auxiliary columns' terms (include/p25.h "AUXILIARY COLUMNS"): one lane per (row, proof) runs the terms' program in
+// ExtF on the trace VALUES (natural order, next = (i + 1) mod n; the preprocessed columns' values from the handle, a
+// periodic column by row mod P), inverts the row's denominators with ONE F_p^2 inversion (Montgomery's trick over
+// AW <= 16) and writes t_j(i) = num_j / den_j component-split to tmp[g][2 j + component][i], where the scan takes it.  A
+// zero denominator fails the proof like a failed identity; its terms are zeros.
+__global__ __launch_bounds__(256) void k_p3_aux_terms(P3Shape sh, P3Bufs b) {
+  P25_WAVE_PRIO(P25_PRIO_BULK);
+  const size_t n = (size_t)1 << sh.k, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t g = blockIdx.y, AW = sh.AW;
+  const size_t i1 = (i + 1) & (n - 1);
+  const u64* tv = b.tvals + (size_t)g * sh.W * n;
+  auto load = [&](int which, uint32_t c) -> E2 {
+    return gl::e2(((which & 2) ? b.pvals : tv)[(size_t)c * n + ((which & 1) ? i1 : i)]);
+  };
+  const u64* pval = b.consts + sh.per_val;
+  auto per = [&](uint32_t x) -> E2 { return gl::e2(pval[p3_per_offset(x) + (i & (((size_t)1 << p3_per_log_period(x)) - 1))]); };
+  E2 num[AirProgram::MAX_AUX], den[AirProgram::MAX_AUX], pre[AirProgram::MAX_AUX];
+  run_program<ExtF>(b.aux_prog, sh.n_aux_instr, b.consts, b.pub + (size_t)g * sh.n_public,
+                    b.hdr + (size_t)g * sh.hdr_stride + sh.o_chal, load, per, [&](uint32_t out, const E2& x) {
+                      if (out & 1) den[out >> 1] = x;
+                      else num[out >> 1] = x;
+                    });
+  E2 acc = gl::e2(1);
+  bool zero = false;
+  for (uint32_t j = 0; j < AW; j++) {
+    pre[j] = acc;
+    if (gl::eq(den[j], gl::e2(0))) zero = true;
+    else acc = gl::mul(acc, den[j]);
+  }
+  if (zero) set_p3_status(b.state + g, 1);
+  E2 inv = zero ? gl::e2(0) : gl::inv(acc);
+  u64* dst = b.tmp + (size_t)g * 2 * AW * n + i;
+  for (uint32_t j = AW; j-- > 0;) {
+    const E2 t = gl::mul(num[j], gl::mul(inv, pre[j]));   // zero for a failed row: inv is
+    inv = gl::mul(inv, den[j]);
+    dst[(size_t)(2 * j) * n] = t.a;
+    dst[(size_t)(2 * j + 1) * n] = t.b;
+  }
+}
+
+// The exclusive prefix sum in F_p^2 of every (proof, column) -- blockIdx.y = g AW + j, whose two component columns stand
+// at tmp + blockIdx.y 2 n -- as k_zpp_scan_block / _totals / _finish do a running product: a block-local inclusive scan,
+// an exclusive scan of the block totals, the add-back, in separate launches.  No block waits on another.
+__global__ __launch_bounds__(P3_AUX_SCAN_BLOCK) void k_p3_aux_scan_block(P3Shape sh, P3Bufs b) {
+  P25_WAVE_PRIO(P25_PRIO_CHAIN);
+  __shared__ u64 sa[P3_AUX_SCAN_BLOCK], sb[P3_AUX_SCAN_BLOCK];
+  const size_t n = (size_t)1 << sh.k, r = (size_t)blockIdx.x * P3_AUX_SCAN_BLOCK + threadIdx.x;
+  const uint32_t t = threadIdx.x;
+  u64* va = b.tmp + (size_t)blockIdx.y * 2 * n;
+  u64* vb = va + n;
+  E2 v = r < n ? E2{va[r], vb[r]} : gl::e2(0);
+  sa[t] = v.a;
+  sb[t] = v.b;
+  __syncthreads();
+  for (uint32_t off = 1; off < (uint32_t)P3_AUX_SCAN_BLOCK; off <<= 1) {
+    const E2 o = t >= off ? E2{sa[t - off], sb[t - off]} : gl::e2(0);
+    __syncthreads();
+    v = gl::add(v, o);
+    sa[t] = v.a;
+    sb[t] = v.b;
+    __syncthreads();
+  }
+  if (r < n) {
+    va[r] = v.a;
+    vb[r] = v.b;
+  }
+  if (t == P3_AUX_SCAN_BLOCK - 1) st_e2(b.atot + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2, v);
+}
+// the block totals of one (proof, column) per workgroup, tile after tile with a carry
+__global__ __launch_bounds__(P3_AUX_TOTALS_TILE) void k_p3_aux_scan_totals(P3Bufs b, uint32_t n_blocks) {
+  P25_WAVE_PRIO(P25_PRIO_CHAIN);
+  __shared__ u64 sa[P3_AUX_TOTALS_TILE], sb[P3_AUX_TOTALS_TILE];
+  __shared__ u64 carry_s[2];
+  const uint32_t t = threadIdx.x;
+  u64* bt = b.atot + (size_t)blockIdx.x * n_blocks * 2;
+  if (t < 2) carry_s[t] = 0;
+  __syncthreads();
+  for (uint32_t base = 0; base < n_blocks; base += P3_AUX_TOTALS_TILE) {
+    const uint32_t i = base + t;
+    E2 v = i < n_blocks ? ld_e2(bt + 2 * i) : gl::e2(0);
+    sa[t] = v.a;
+    sb[t] = v.b;
+    __syncthreads();
+    for (uint32_t off = 1; off < (uint32_t)P3_AUX_TOTALS_TILE; off <<= 1) {
+      const E2 o = t >= off ? E2{sa[t - off], sb[t - off]} : gl::e2(0);
+      __syncthreads();
+      v = gl::add(v, o);
+      sa[t] = v.a;
+      sb[t] = v.b;
+      __syncthreads();
+    }
+    const E2 carry = E2{carry_s[0], carry_s[1]};
+    const E2 excl = t == 0 ? carry : gl::add(carry, E2{sa[t - 1], sb[t - 1]});
+    __syncthreads();
+    if (i < n_blocks) st_e2(bt + 2 * i, excl);
+    if (t == P3_AUX_TOTALS_TILE - 1) st_e2(carry_s, gl::add(carry, v));
+    __syncthreads();
+  }
+}
+// S_j(r) = the totals of the blocks before r's + the inclusive sum up to r - 1 inside the block: to avals
+__global__ __launch_bounds__(P3_AUX_SCAN_BLOCK) void k_p3_aux_scan_finish(P3Shape sh, P3Bufs b) {
+  P25_WAVE_PRIO(P25_PRIO_CHAIN);
+  const size_t n = (size_t)1 << sh.k, r = (size_t)blockIdx.x * P3_AUX_SCAN_BLOCK + threadIdx.x;
+  if (r >= n) return;
+  const u64* va = b.tmp + (size_t)blockIdx.y * 2 * n;
+  E2 z = ld_e2(b.atot + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2);
+  if (threadIdx.x > 0) z = gl::add(z, E2{va[r - 1], va[n + r - 1]});
+  u64* out = b.avals + (size_t)blockIdx.y * 2 * n + r;
+  out[0] = z.a;
+  out[n] = z.b;
+}
+
 // One lane per point of the quotient coset 7 H_{n 2^lqd}.  Lane p takes the point stored at position p of the bit-reversed
 // trace LDE (j = rev(p)), so the local row is read coalesced; its chunk is rev(p >> k) and its place in the chunk, in
 // bit-reversed order, p mod n -- the order the inverse transform of the chunks takes.
+// F = BaseF: an AIR without challenges and auxiliary columns.  F = ExtF: one with them, evaluated in F_p^2 throughout --
+// every other operand embedded, an auxiliary column built from its two component columns of the proof's own LDE at the
+// same two positions.
+template <class F>
 __global__ __launch_bounds__(256) void k_p3_quotient(P3Shape sh, P3Bufs b) {
   P25_WAVE_PRIO(P25_PRIO_BULK);
   const size_t n = (size_t)1 << sh.k, N2 = (size_t)1 << sh.L, nq = n << sh.lqd;
@@ -298,7 +431,21 @@ __global__ __launch_bounds__(256) void k_p3_quotient(P3Shape sh, P3Bufs b) {
     return ptab[((size_t)p3_per_offset(i) << sh.lqd) + (j & ((1u << (p3_per_log_period(i) + sh.lqd)) - 1))];
   };
   // every lane of the block reads the row of proof g: a plain load at a uniform address
-  const E2 acc = run_air<BaseF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, load, per, sel, alpha);
+  E2 acc;
+  if constexpr (!F::EXT) {
+    acc = run_air<BaseF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, nullptr, load, per, sel, alpha);
+  } else {
+    const u64* alde = b.alde + (size_t)g * 2 * sh.AW * N2;
+    auto eload = [&](int which, uint32_t c) -> E2 {
+      if (!(which & 4)) return gl::e2(load(which, c));
+      const u64* col = alde + (size_t)(2 * c) * N2 + ((which & 1) ? pos1 : p);
+      return E2{col[0], col[N2]};
+    };
+    auto eper = [&](uint32_t i) -> E2 { return gl::e2(per(i)); };
+    const E2 esel[4] = {gl::e2(0), gl::e2(sel[1]), gl::e2(sel[2]), gl::e2(sel[3])};
+    acc = run_air<ExtF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public,
+                        b.hdr + (size_t)g * sh.hdr_stride + sh.o_chal, eload, eper, esel, alpha);
+  }
   const E2 q = gl::mul(acc, sh.zh_inv[chunk]);
   u64* dst = b.qv + (((size_t)chunk * sh.G + g) * 2) * n + (p & (n - 1));
   dst[0] = q.a;
@@ -306,7 +453,8 @@ __global__ __launch_bounds__(256) void k_p3_quotient(P3Shape sh, P3Bufs b) {
 }
 
 // Openings: job < W: trace column at zeta; < 2 W: at zeta w_n; then the chunk components at zeta / s_c; then the shared
-// preprocessed columns at this proof's zeta and zeta w_n, behind the chunk openings.  Lane t sums the
+// preprocessed columns at this proof's zeta and zeta w_n, behind the chunk openings; then the 2 AW auxiliary base columns
+// at the two points.  Lane t sums the
 // coefficients t, t + 1024, ... by Horner in x^1024, scales by x^t; the block adds up.
 __global__ __launch_bounds__(1024) void k_p3_eval(P3Shape sh, P3Bufs b) {
   P25_WAVE_PRIO(P25_PRIO_BULK);
@@ -316,9 +464,15 @@ __global__ __launch_bounds__(1024) void k_p3_eval(P3Shape sh, P3Bufs b) {
   const u64* hdr = b.hdr + (size_t)g * sh.hdr_stride;
   const u64* c;
   E2 x;
+  uint32_t dst = 8 + 2 * job;   // the opening's place in the header
   if (job < 2 * sh.W) {
     c = b.tcoef + ((size_t)g * sh.W + (job % sh.W)) * n;
     x = ld_e2(hdr + sh.o_points + 2 * (job / sh.W));
+  } else if (job >= 2 * sh.W + 2 * sh.Q + 2 * sh.PW) {   // the proof's auxiliary base columns, behind the auxiliary root
+    const uint32_t aj = job - 2 * sh.W - 2 * sh.Q - 2 * sh.PW;
+    c = b.acoef + ((size_t)g * 2 * sh.AW + (aj % (2 * sh.AW))) * n;
+    x = ld_e2(hdr + sh.o_points + 2 * (aj / (2 * sh.AW)));
+    dst += 4;
   } else if (job >= 2 * sh.W + 2 * sh.Q) {
     const uint32_t pj = job - 2 * sh.W - 2 * sh.Q;
     c = b.pcoef + (size_t)(pj % sh.PW) * n;
@@ -349,7 +503,7 @@ __global__ __launch_bounds__(1024) void k_p3_eval(P3Shape sh, P3Bufs b) {
     }
     __syncthreads();
   }
-  if (t < 2) b.hdr[(size_t)g * sh.hdr_stride + 8 + 2 * job + t] = red[t];
+  if (t < 2) b.hdr[(size_t)g * sh.hdr_stride + dst + t] = red[t];
 }
 
 // The identity the verifier enforces (verifier.rs:169-239; p3_prover.cpp:306-329): a trace that violates the AIR fails here.
@@ -363,12 +517,17 @@ __global__ __launch_bounds__(64) void k_p3_identity(P3Shape sh, P3Bufs b) {
   const E2 is_trans = gl::sub(zeta, gl::e2(sh.g_inv));
   const E2 sel[4] = {gl::e2(0), gl::mul(z_h, gl::inv(gl::sub(zeta, gl::e2(1)))), gl::mul(z_h, gl::inv(is_trans)), is_trans};
   const u64* popen = open + 4 * sh.W + 4 * sh.Q;   // the preprocessed openings, behind the chunks'
+  const u64* aopen = hdr + sh.o_aux + 4;           // the auxiliary openings, behind the auxiliary root
   auto load = [&](int which, uint32_t c) -> E2 {
+    if (which & 4) {   // column c at the point: o[2 c] + X o[2 c + 1], as the chunks are recomposed
+      const u64* o = aopen + 2 * (((which & 1) ? 2 * sh.AW : 0) + 2 * c);
+      return gl::add(ld_e2(o), gl::mul(ld_e2(o + 2), E2{0, 1}));
+    }
     return (which & 2) ? ld_e2(popen + 2 * (((which & 1) ? sh.PW : 0) + c)) : ld_e2(open + 2 * (((which & 1) ? sh.W : 0) + c));
   };
   const u64* pcoef = b.consts + sh.per_coef;
   auto per = [&](uint32_t i) -> E2 { return p3_periodic_at(pcoef + p3_per_offset(i), p3_per_log_period(i), sh.k, zeta); };
-  const E2 acc = run_air<ExtF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, load, per, sel, alpha);
+  const E2 acc = run_air<ExtF>(b.prog, sh.n_instr, b.consts, b.pub + (size_t)g * sh.n_public, hdr + sh.o_chal, load, per, sel, alpha);
   const E2 lhs = gl::mul(acc, gl::inv(z_h));
   E2 at_zeta[8];
   for (uint32_t j = 0; j < sh.Q; j++) at_zeta[j] = gl::sub(gl::exp_pow2(gl::mul(zeta, sh.s_inv[j]), sh.k), gl::e2(1));
@@ -414,6 +573,14 @@ __global__ __launch_bounds__(256) void k_p3_reduced(P3Shape sh, P3Bufs b) {
     const uint32_t t0 = 2 * W + Q2 + c, t1 = t0 + sh.PW;
     s_z = gl::add(s_z, gl::mul(ld_e2(ap + 2 * t0), gl::sub(v, ld_e2(open + 2 * t0))));
     s_zn = gl::add(s_zn, gl::mul(ld_e2(ap + 2 * t1), gl::sub(v, ld_e2(open + 2 * t1))));
+  }
+  // the last batch: the auxiliary matrix's 2 AW base columns at zeta, then at zeta w_n; their openings stand behind the
+  // auxiliary root, four words further on than their powers
+  for (uint32_t c = 0; c < 2 * sh.AW; c++) {
+    const E2 v = gl::e2(b.alde[((size_t)g * 2 * sh.AW + c) * N2 + i]);
+    const uint32_t t0 = 2 * W + Q2 + 2 * sh.PW + c, t1 = t0 + 2 * sh.AW;
+    s_z = gl::add(s_z, gl::mul(ld_e2(ap + 2 * t0), gl::sub(v, ld_e2(open + 2 * t0 + 4))));
+    s_zn = gl::add(s_zn, gl::mul(ld_e2(ap + 2 * t1), gl::sub(v, ld_e2(open + 2 * t1 + 4))));
   }
   st_e2(b.layers + (size_t)g * 4 * N2 + 2 * i, gl::add(gl::mul(s_z, inv_z), gl::mul(s_zn, inv_zn)));
 }
@@ -520,7 +687,8 @@ __global__ __launch_bounds__(256) void k_p3_pow_search(P3Shape sh, P3Bufs b, con
 
 // Flattening (p3_prover.cpp:423-445).  Block q of a proof writes query q's two sections (the second ends in the third
 // batch, row and path from the handle's shared LDE and tree, for an AIR with preprocessed columns), block 0 the fixed words and the
-// public values behind the last query's section as well.  A failed proof's words are zeros, that tail included.
+// public values behind the last query's section as well.  With auxiliary columns the header carries their root and openings
+// and every query ends in their batch.  A failed proof's words are zeros, that tail included.
 __global__ __launch_bounds__(64) void k_p3_gather(P3Shape sh, P3Bufs b, u64* __restrict__ out_base, size_t out_stride,
                                                   uint32_t* __restrict__ d_status) {
   const uint32_t qi = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
@@ -596,6 +764,16 @@ __global__ __launch_bounds__(64) void k_p3_gather(P3Shape sh, P3Bufs b, u64* __r
         w[e] = b.ptree[p3_level_off(N2, l) + 4 * (((size_t)ix >> l) ^ 1) + (e & 3)];
       }
     }
+    if (sh.AW) {   // the last batch: row and path from the proof's own auxiliary LDE and tree
+      w += 4 * sh.L;
+      for (uint32_t c = t; c < 2 * sh.AW; c += 64) w[c] = b.alde[((size_t)g * 2 * sh.AW + c) * N2 + ix];
+      w += 2 * sh.AW;
+      const u64* at = b.atree + (size_t)g * 8 * N2;
+      for (uint32_t e = t; e < 4 * sh.L; e += 64) {
+        const uint32_t l = e >> 2;
+        w[e] = at[p3_level_off(N2, l) + 4 * (((size_t)ix >> l) ^ 1) + (e & 3)];
+      }
+    }
   }
 }
 
@@ -640,12 +818,22 @@ void p3_launch_commit_rows4(const u64* rows, size_t rows_stride, size_t h, u64* 
 void p3_launch_chain(const P3Shape& s, const P3Bufs& b, uint32_t phase, uint32_t round, hipStream_t st) {
   hipLaunchKernelGGL(k_p3_chain, dim3(1, s.G), dim3(64), 0, st, s, b, phase, round);
 }
+void p3_launch_aux_columns(const P3Shape& s, const P3Bufs& b, hipStream_t st) {
+  const size_t n = (size_t)1 << s.k;
+  const unsigned blocks = (unsigned)((n + P3_AUX_SCAN_BLOCK - 1) / P3_AUX_SCAN_BLOCK);
+  hipLaunchKernelGGL(k_p3_aux_terms, dim3((unsigned)((n + 255) / 256), s.G), dim3(256), 0, st, s, b);
+  hipLaunchKernelGGL(k_p3_aux_scan_block, dim3(blocks, s.G * s.AW), dim3(P3_AUX_SCAN_BLOCK), 0, st, s, b);
+  hipLaunchKernelGGL(k_p3_aux_scan_totals, dim3(s.G * s.AW), dim3(P3_AUX_TOTALS_TILE), 0, st, b, blocks);
+  hipLaunchKernelGGL(k_p3_aux_scan_finish, dim3(blocks, s.G * s.AW), dim3(P3_AUX_SCAN_BLOCK), 0, st, s, b);
+}
 void p3_launch_quotient(const P3Shape& s, const P3Bufs& b, hipStream_t st) {
   const size_t nq = (size_t)1 << (s.k + s.lqd);
-  hipLaunchKernelGGL(k_p3_quotient, dim3((unsigned)((nq + 255) / 256), s.G), dim3(256), 0, st, s, b);
+  const dim3 grid((unsigned)((nq + 255) / 256), s.G);
+  if (s.AW) hipLaunchKernelGGL(k_p3_quotient<ExtF>, grid, dim3(256), 0, st, s, b);
+  else hipLaunchKernelGGL(k_p3_quotient<BaseF>, grid, dim3(256), 0, st, s, b);
 }
 void p3_launch_openings(const P3Shape& s, const P3Bufs& b, hipStream_t st) {
-  hipLaunchKernelGGL(k_p3_eval, dim3(2 * s.W + 2 * s.Q + 2 * s.PW, s.G), dim3(1024), 0, st, s, b);
+  hipLaunchKernelGGL(k_p3_eval, dim3(2 * s.W + 2 * s.Q + 2 * s.PW + 4 * s.AW, s.G), dim3(1024), 0, st, s, b);
   hipLaunchKernelGGL(k_p3_identity, dim3((s.G + 63) / 64), dim3(64), 0, st, s, b);
 }
 void p3_launch_reduced(const P3Shape& s, const P3Bufs& b, hipStream_t st) {

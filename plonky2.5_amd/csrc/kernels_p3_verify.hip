@@ -95,6 +95,10 @@ __global__ __launch_bounds__(64) void k_p3v_transcript(P3VerifyArgs a) {
   if (a.PW)   // the handle's preprocessed commitment: one address for the whole grid
     for (int j = 0; j < 4; j++) ch.observe(a.prep_root[j]);
   for (uint32_t i = 0; i < a.n_public; i++) ch.observe(proof[a.o_public + i]);   // one address per group: the value is uniform in it
+  if (a.AW) {   // the challenge phase: the challenges, then the proof's auxiliary root, before alpha
+    draw(a.c_chal, 2 * a.NC);
+    ch.observe_digest(proof + a.o_aux);
+  }
   draw(P3VC_ALPHA, 2);
   ch.observe_digest(proof + 4);
   draw(P3VC_ZETA, 2);

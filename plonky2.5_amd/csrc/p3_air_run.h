@@ -8,6 +8,7 @@ namespace p25 {
 
 struct BaseF {
   typedef u64 T;
+  static constexpr bool EXT = false;
   GL_HD static u64 cst(u64 v) { return v; }
   GL_HD static u64 add(u64 x, u64 y) { return gl::add(x, y); }
   GL_HD static u64 sub(u64 x, u64 y) { return gl::sub(x, y); }
@@ -21,6 +22,7 @@ struct BaseF {
 };
 struct ExtF {
   typedef gl::E2 T;
+  static constexpr bool EXT = true;   // the field an AIR with challenges or auxiliary columns is evaluated in
   GL_HD static gl::E2 cst(u64 v) { return gl::e2(v); }
   GL_HD static gl::E2 add(gl::E2 x, gl::E2 y) { return gl::add(x, y); }
   GL_HD static gl::E2 sub(gl::E2 x, gl::E2 y) { return gl::sub(x, y); }
@@ -38,18 +40,25 @@ GL_HD gl::E2 p3_periodic_at(const u64* __restrict__ coef, uint32_t lp, uint32_t 
   }
   return acc;
 }
-// Runs the register program: `load(which, column)` reads the row (which: P3_LOAD_*, the trace's or the preprocessed matrix's,
-// current or next), `per(index)` gives the periodic column of a
+// Runs a register program: `load(which, column)` reads the row (which: P3_LOAD_*, the trace's, the preprocessed matrix's or,
+// in ExtF alone, the auxiliary matrix's, current or next), `per(index)` gives the periodic column of a
 // P3_OPND_PERIODIC operand (p3_per_log_period, p3_per_offset of its index) at the caller's point, `pub` is the proof's own
-// row of public values (read only by P3_OPND_PUBLIC operands: may be null without them), the constraints are folded in
-// program order.
-template <class F, class Load, class Per>
-GL_HD gl::E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u64* __restrict__ consts,
-                     const u64* __restrict__ pub, Load load, Per per, const typename F::T sel[4], gl::E2 alpha) {
+// row of public values (read only by P3_OPND_PUBLIC operands: may be null without them), `chal` the proof's challenges,
+// two words each (read only by P3_OPND_CHALLENGE operands, which only an ExtF program has: may be null without them).
+// Every P3_OP_EMIT hands its operand to emit(dst, value) in program order: a constraint and its `when` in the AIR's
+// program, num_0, den_0, num_1, ... in the auxiliary columns' (P3AirDevice::aux_instr).
+template <class F, class Load, class Per, class Emit>
+GL_HD void run_program(const P3Instr* __restrict__ prog, uint32_t n_instr, const u64* __restrict__ consts,
+                       const u64* __restrict__ pub, const u64* __restrict__ chal, Load load, Per per, Emit emit) {
   typedef typename F::T T;
   T slot[P3_MAX_LIVE];
   auto fetch = [&](uint32_t o) -> T {
     const uint32_t kind = o >> 28, i = o & 0x0fffffffu;
+    if constexpr (F::EXT) {
+      if (kind == P3_OPND_CHALLENGE) return gl::E2{chal[2 * i], chal[2 * i + 1]};
+      if (kind == P3_OPND_AUX_LOCAL) return load(P3_LOAD_AUX_LOCAL, i);
+      if (kind == P3_OPND_AUX_NEXT) return load(P3_LOAD_AUX_NEXT, i);
+    }
     switch (kind) {
       case P3_OPND_SLOT: return slot[i];
       case P3_OPND_LOCAL: return load(P3_LOAD_LOCAL, i);
@@ -61,17 +70,26 @@ GL_HD gl::E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u
       default: return F::cst(consts[i]);
     }
   };
-  gl::E2 acc = gl::e2(0);
   for (uint32_t pc = 0; pc < n_instr; pc++) {
     const P3Instr in = prog[pc];
     const T x = fetch(in.a);
     if (in.op == P3_OP_EMIT) {
-      acc = F::fold(acc, alpha, in.dst == 0 ? x : F::mul(sel[in.dst & 3], x));
+      emit(in.dst, x);
     } else {
       const T y = fetch(in.b);
       slot[in.dst] = in.op == P3_OP_ADD ? F::add(x, y) : in.op == P3_OP_SUB ? F::sub(x, y) : F::mul(x, y);
     }
   }
+}
+// The AIR's program: the constraints folded in program order.
+template <class F, class Load, class Per>
+GL_HD gl::E2 run_air(const P3Instr* __restrict__ prog, uint32_t n_instr, const u64* __restrict__ consts,
+                     const u64* __restrict__ pub, const u64* __restrict__ chal, Load load, Per per, const typename F::T sel[4],
+                     gl::E2 alpha) {
+  gl::E2 acc = gl::e2(0);
+  run_program<F>(prog, n_instr, consts, pub, chal, load, per, [&](uint32_t when, const typename F::T& x) {
+    acc = F::fold(acc, alpha, when == 0 ? x : F::mul(sel[when & 3], x));
+  });
   return acc;
 }
 

@@ -387,8 +387,9 @@ std::vector<int> AirProgram::node_degrees() const {
   std::vector<int> deg(nodes.size(), 0);
   for (size_t k = 0; k < nodes.size(); k++) {
     const Node& nd = nodes[k];
-    if (nd.op == LOCAL || nd.op == NEXT || nd.op == PERIODIC || nd.op == PREP_LOCAL || nd.op == PREP_NEXT) deg[k] = 1;
-    else if (nd.op == CONST || nd.op == PUBLIC) deg[k] = 0;
+    if (nd.op == LOCAL || nd.op == NEXT || nd.op == PERIODIC || nd.op == PREP_LOCAL || nd.op == PREP_NEXT ||
+        nd.op == AUX_LOCAL || nd.op == AUX_NEXT) deg[k] = 1;   // an auxiliary column's components are polynomials of degree < n
+    else if (nd.op == CONST || nd.op == PUBLIC || nd.op == CHALLENGE) deg[k] = 0;
     else if (nd.op == MUL) deg[k] = std::min(deg[nd.a] + deg[nd.b], DEGREE_SAT);
     else deg[k] = std::max(deg[nd.a], deg[nd.b]);
   }
@@ -414,10 +415,18 @@ void AirProgram::validate() const {
     for (u64 v : prep.values)
       if (v >= gl::P) throw std::invalid_argument("AIR: non-canonical preprocessed value (>= p)");
   }
+  if (aux.n_challenges > (uint32_t)MAX_CHALLENGES)
+    throw std::invalid_argument("AIR: more than 8 challenges (P25_AIR_MAX_CHALLENGES)");
+  if (aux.width() > (uint32_t)MAX_AUX) throw std::invalid_argument("AIR: more than 16 auxiliary columns (P25_AIR_MAX_AUX)");
+  if (aux.n_challenges > 0 && aux.width() == 0)
+    throw std::invalid_argument("AIR: challenges (n_challenges > 0) without auxiliary columns (width = 0)");
   if (nodes.empty() || constraints.empty()) throw std::invalid_argument("AIR: empty program");
   for (size_t i = 0; i < nodes.size(); i++) {
     const Node& nd = nodes[i];
-    if (nd.op > PREP_NEXT) throw std::invalid_argument("AIR: unknown node op");
+    if (nd.op > AUX_NEXT) throw std::invalid_argument("AIR: unknown node op");
+    if (nd.op == CHALLENGE && nd.a >= aux.n_challenges) throw std::invalid_argument("AIR: challenge index >= n_challenges");
+    if ((nd.op == AUX_LOCAL || nd.op == AUX_NEXT) && nd.a >= aux.width())
+      throw std::invalid_argument("AIR: auxiliary column index >= width");
     if ((nd.op == LOCAL || nd.op == NEXT) && nd.a >= (uint32_t)width) throw std::invalid_argument("AIR: column out of range");
     if (nd.op == PUBLIC && nd.a >= (uint32_t)n_public) throw std::invalid_argument("AIR: public value index >= n_public");
     if (nd.op == PERIODIC && nd.a >= periodic.size()) throw std::invalid_argument("AIR: periodic column index >= n_columns");
@@ -425,6 +434,22 @@ void AirProgram::validate() const {
       throw std::invalid_argument("AIR: preprocessed column index >= width");
     if (nd.op >= ADD && nd.op <= MUL && (nd.a >= i || nd.b >= i)) throw std::invalid_argument("AIR: node refers to a later node");
     if (nd.op == CONST && nd.value >= gl::P) throw std::invalid_argument("AIR: non-canonical constant");
+  }
+  if (aux.width()) {
+    // which nodes depend on an auxiliary column: one pass, operands come first
+    std::vector<char> dep(nodes.size(), 0);
+    for (size_t i = 0; i < nodes.size(); i++) {
+      const Node& nd = nodes[i];
+      dep[i] = nd.op == AUX_LOCAL || nd.op == AUX_NEXT || (nd.op >= ADD && nd.op <= MUL && (dep[nd.a] || dep[nd.b]));
+    }
+    for (size_t j = 0; j < aux.columns.size(); j++) {
+      const AuxColumn& ac = aux.columns[j];
+      if (ac.num >= nodes.size() || ac.den >= nodes.size())
+        throw std::invalid_argument("AIR: auxiliary column " + std::to_string(j) + ": num / den node index >= n_nodes");
+      if (dep[ac.num] || dep[ac.den])
+        throw std::invalid_argument("AIR: auxiliary column " + std::to_string(j) +
+                                    ": num / den depends on an auxiliary column (node op 11 AUX_LOCAL / 12 AUX_NEXT)");
+    }
   }
   const std::vector<int> deg = node_degrees();
   for (const Constraint& c : constraints) {
@@ -497,6 +522,10 @@ struct CircuitExtOps {
   const std::vector<Ext>&prep_l, &prep_n;
   Ext prep_local(uint32_t c) { return prep_l.at(c); }
   Ext prep_next(uint32_t c) { return prep_n.at(c); }
+  const std::vector<Ext>&chal, &aux_l, &aux_n;
+  Ext challenge(uint32_t i) { return chal.at(i); }
+  Ext aux_local(uint32_t c) { return aux_l.at(c); }
+  Ext aux_next(uint32_t c) { return aux_n.at(c); }
   Ext cst(u64 v) { return p3_field_to_arr(cb, p3_constant(cb, v)); }
   Ext pub(uint32_t i) { return public_values.at(i); }
   Ext per(uint32_t c) { return periodic.at(c); }
@@ -522,7 +551,8 @@ std::vector<Ext> ProgramAir::periodic_at(CircuitBuilder& cb, const Ext& zeta, in
   return out;
 }
 void ProgramAir::eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const {
-  CircuitExtOps ops{cb, folder.public_values, folder.periodic, folder.prep_local, folder.prep_next};
+  CircuitExtOps ops{cb, folder.public_values, folder.periodic, folder.prep_local, folder.prep_next,
+                    folder.challenges, folder.aux_local, folder.aux_next};
   const Ext sel[4] = {Ext{}, folder.is_first_row, folder.is_last_row, folder.is_transition};
   prog.fold<Ext>(folder.trace_local, folder.trace_next, sel, ops, [&](const Ext& c) { folder.assert_zero(cb, c); });
 }
@@ -543,8 +573,9 @@ size_t P3Config::num_inputs() const {
   return n;
 }
 // prep_width: the AIR's preprocessed columns (0: the reference's proof).  Their openings stand behind the chunk openings
-// and their batch is every query's third.
-static P3ProofTarget add_virtual_proof(CircuitBuilder& cb, const P3Config& cfg, int prep_width) {
+// and their batch is every query's third.  aux_width: the AIR's auxiliary columns (0: none), 2 aux_width base columns.
+// Their commitment and openings stand behind the preprocessed openings and their batch is every query's last.
+static P3ProofTarget add_virtual_proof(CircuitBuilder& cb, const P3Config& cfg, int prep_width, int aux_width) {
   std::vector<Target>& in = cb.input_targets;
   auto vt = [&]() {
     Target t = cb.add_virtual_target();
@@ -565,6 +596,11 @@ static P3ProofTarget add_virtual_proof(CircuitBuilder& cb, const P3Config& cfg, 
   }
   for (int i = 0; i < prep_width; i++) p.prep_local.push_back(vext());
   for (int i = 0; i < prep_width; i++) p.prep_next.push_back(vext());
+  if (aux_width) {
+    p.aux_commit = v4();
+    for (int i = 0; i < 2 * aux_width; i++) p.aux_local.push_back(vext());
+    for (int i = 0; i < 2 * aux_width; i++) p.aux_next.push_back(vext());
+  }
   for (int i = 0; i < cfg.log_trace_height; i++) p.commit_phase_commits.push_back(v4());
   for (int q = 0; q < cfg.fri_config.num_queries; q++) {
     std::vector<P3CommitPhaseStep> steps;
@@ -579,9 +615,11 @@ static P3ProofTarget add_virtual_proof(CircuitBuilder& cb, const P3Config& cfg, 
   p.final_poly = vext();
   p.pow_witness = vt();
   for (int q = 0; q < cfg.fri_config.num_queries; q++) {
-    const int n_batches = prep_width ? 3 : 2;
+    std::vector<int> widths = {cfg.trace_width, cfg.opening_proof_query_openings_opened_values_length};
+    if (prep_width) widths.push_back(prep_width);
+    if (aux_width) widths.push_back(2 * aux_width);
+    const int n_batches = (int)widths.size();
     std::vector<P3BatchOpening> bo(n_batches);
-    int widths[3] = {cfg.trace_width, cfg.opening_proof_query_openings_opened_values_length, prep_width};
     for (int b = 0; b < n_batches; b++) {
       const int mats = b == 1 ? (1 << cfg.log_quotient_degree) : 1;   // batch 1: one matrix per quotient chunk
       for (int m = 0; m < mats; m++) {
@@ -736,7 +774,8 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
     challenger.sponge_state.assign(st.begin(), st.end());
   }
   const int prep_width = air.preprocessed_width();
-  P3ProofTarget proof = add_virtual_proof(cb, config, prep_width);
+  const int aux_width = air.aux_width();
+  P3ProofTarget proof = add_virtual_proof(cb, config, prep_width, aux_width);
   // The proof's public values: input targets behind the proof's words (the tail of the flat input), exposed as the
   // circuit's public inputs.  None for the reference's AIRs, whose circuit this leaves as it was.
   std::vector<Target> public_values;
@@ -789,6 +828,13 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
   }
   // uni-stark's `challenger.observe_slice(public_values)`: between the trace commitment and alpha (unpinned: include/p25.h)
   p3_observe(cb, challenger, public_values.begin(), public_values.end());
+  // the challenge phase (include/p25.h "AUXILIARY COLUMNS"): the challenges in index order, then the auxiliary commitment
+  // -- the proof's own words -- before alpha.  No gate for an AIR without auxiliary columns.
+  std::vector<Ext> challenges;
+  if (aux_width) {
+    for (int i = 0; i < air.n_challenges(); i++) challenges.push_back(p3_sample_ext(cb, challenger));
+    p3_observe(cb, challenger, proof.aux_commit.begin(), proof.aux_commit.end());
+  }
   Ext alpha = p3_sample_ext(cb, challenger);
   p3_observe(cb, challenger, proof.quotient_commit.begin(), proof.quotient_commit.end());
   Ext zeta = p3_sample_ext(cb, challenger);
@@ -804,6 +850,11 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
     cps.resize(3);
     cps[2].commit = prep_commit;
     cps[2].mats.push_back(MatPoints{trace_domain, {{zeta, proof.prep_local}, {zeta_next, proof.prep_next}}});
+  }
+  if (aux_width) {   // the last batch: the trace's height again, its powers go on where the slot stands
+    cps.emplace_back();
+    cps.back().commit = proof.aux_commit;
+    cps.back().mats.push_back(MatPoints{trace_domain, {{zeta, proof.aux_local}, {zeta_next, proof.aux_next}}});
   }
   p3_verify_opening_proof(cb, config.fri_config, cps, proof, challenger);
 
@@ -861,6 +912,16 @@ P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const 
   folder.alpha = alpha;
   folder.accumulator = p3_ext_zero(cb);
   folder.periodic = air.periodic_at(cb, zeta, degree_bits);   // nothing, and no gate, for an AIR without periodic columns
+  // an auxiliary column at a point: o[2 a] + X o[2 a + 1], as the chunks are recomposed (monomial, product, sum)
+  folder.challenges = challenges;
+  for (int pt = 0; pt < 2; pt++) {
+    const std::vector<Ext>& o = pt ? proof.aux_next : proof.aux_local;
+    for (int c = 0; c < aux_width; c++) {
+      Ext m0 = p3_ext_mul(cb, p3_ext_monomial(cb, 0), o[2 * c]);
+      Ext m1 = p3_ext_mul(cb, p3_ext_monomial(cb, 1), o[2 * c + 1]);
+      (pt ? folder.aux_next : folder.aux_local).push_back(p3_ext_add(cb, m0, m1));
+    }
+  }
   air.eval(folder, cb);
   Ext folded_constraints = folder.accumulator;
   Ext lhs = p3_ext_mul(cb, folded_constraints, sels.inv_zeroifier);

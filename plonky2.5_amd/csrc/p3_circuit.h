@@ -47,7 +47,12 @@ struct P3ProofTarget {
   // this library's extension (AirProgram::PREP_LOCAL / PREP_NEXT): the preprocessed columns at zeta and zeta w_n; empty
   // for an AIR without preprocessed columns
   std::vector<Ext> prep_local, prep_next;
-  // per query: the trace batch, the quotient batch and, for an AIR with preprocessed columns, the preprocessed batch
+  // this library's extension (AirProgram::AUX_LOCAL / AUX_NEXT): the commitment of the auxiliary (second-phase) matrix and
+  // its 2 AW base columns at zeta and zeta w_n, behind the preprocessed openings; empty for an AIR without auxiliary columns
+  std::array<Target, 4> aux_commit{};
+  std::vector<Ext> aux_local, aux_next;
+  // per query: the trace batch, the quotient batch, for an AIR with preprocessed columns the preprocessed batch and, for an
+  // AIR with auxiliary columns, the auxiliary batch -- up to four, in this order
   std::vector<std::vector<P3BatchOpening>> query_openings;
   int degree_bits;
 };
@@ -58,6 +63,9 @@ struct VerifierConstraintFolder {
   std::vector<Ext> public_values;   // this library's extension (AirProgram::PUBLIC): base elements embedded in the extension
   std::vector<Ext> periodic;        // this library's extension (AirProgram::PERIODIC): the periodic columns at zeta, by column
   std::vector<Ext> prep_local, prep_next;   // this library's extension (AirProgram::PREP_LOCAL / PREP_NEXT): the opened values
+  // this library's extension (AirProgram::CHALLENGE / AUX_LOCAL / AUX_NEXT): the sampled challenges and the auxiliary
+  // columns at zeta and zeta w_n, each recomposed from its two opened component columns
+  std::vector<Ext> challenges, aux_local, aux_next;
   Ext is_first_row, is_last_row, is_transition, alpha, accumulator;
   // air.rs:69-88, 90-118
   void assert_zero(CircuitBuilder& cb, Ext x);
@@ -78,6 +86,10 @@ struct Air {
   // their commitment for a trace of 2^log_n rows under this log_blowup -- verifying-key data the circuit holds as constants
   virtual int preprocessed_width() const { return 0; }
   virtual std::array<u64, 4> preprocessed_commit(int /*log_n*/, int /*log_blowup*/) const { return {}; }
+  // the auxiliary (challenge-phase) columns (this library's extension; the reference's trait has none): the challenges
+  // sampled behind the public values and the F_p^2 columns committed behind them
+  virtual int n_challenges() const { return 0; }
+  virtual int aux_width() const { return 0; }
   virtual void eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const = 0;
 };
 // src/p3/mod.rs:160-221 (the test's FibonacciAir)
@@ -99,14 +111,19 @@ struct AirProgram {
   // COLUMNS"): degree 1 like LOCAL
   // PREP_LOCAL(a) / PREP_NEXT(a): preprocessed column a at the current / the next row, cyclic as NEXT is (this library's
   // extension; include/p25.h "PREPROCESSED COLUMNS"): degree 1 like LOCAL
+  // CHALLENGE(a): challenge a < aux.n_challenges, an element of F_p^2 sampled after the trace is committed: degree 0
+  // AUX_LOCAL(a) / AUX_NEXT(a): auxiliary column a < aux.width() at the current / the next row, cyclic as NEXT is (this
+  // library's extension; include/p25.h "AUXILIARY COLUMNS"): values in F_p^2, degree 1 like LOCAL.  An AIR with any of
+  // the three is evaluated in F_p^2 throughout.
   enum Op : uint32_t { LOCAL = 0, NEXT = 1, CONST = 2, ADD = 3, SUB = 4, MUL = 5, PUBLIC = 6, PERIODIC = 7, PREP_LOCAL = 8,
-                       PREP_NEXT = 9 };
+                       PREP_NEXT = 9, CHALLENGE = 10, AUX_LOCAL = 11, AUX_NEXT = 12 };
+  static constexpr int MAX_CHALLENGES = 8, MAX_AUX = 16;   // P25_AIR_MAX_CHALLENGES, P25_AIR_MAX_AUX
   static constexpr int MAX_PREPROCESSED = 64;   // P25_AIR_MAX_PREPROCESSED
   static constexpr int MAX_PUBLIC = 64;   // P25_AIR_MAX_PUBLIC
   static constexpr int MAX_PERIODIC = 32, MAX_LOG_PERIOD = 8;   // P25_AIR_MAX_PERIODIC, P25_AIR_MAX_LOG_PERIOD
   enum When : uint32_t { ALWAYS = 0, FIRST_ROW = 1, LAST_ROW = 2, TRANSITION = 3 };
   struct Node {
-    uint32_t op, a, b;  // LOCAL/NEXT: a = column; PUBLIC: a = index; PERIODIC: a = periodic column; PREP_LOCAL/PREP_NEXT: a = preprocessed column; ADD/SUB/MUL: a, b = earlier node indices
+    uint32_t op, a, b;  // LOCAL/NEXT: a = column; PUBLIC: a = index; PERIODIC: a = periodic column; PREP_LOCAL/PREP_NEXT: a = preprocessed column; CHALLENGE: a = challenge; AUX_LOCAL/AUX_NEXT: a = auxiliary column; ADD/SUB/MUL: a, b = earlier node indices
     u64 value;          // CONST
   };
   struct Constraint {
@@ -129,6 +146,25 @@ struct AirProgram {
     std::vector<u64> values;   // [2^log_n][width], row-major like a trace, each < p
   };
   Preprocessed prep;
+  // The auxiliary (second-phase) trace: column j is the running sum over the rows of num_j / den_j in F_p^2, S_j(0) = 0,
+  // S_j(i + 1) = S_j(i) + num_j(i) / den_j(i), the two nodes evaluated on trace row i with the challenges at hand.  The
+  // prover builds it after sampling the challenges and commits it as 2 width() base columns (column j's components at 2 j
+  // and 2 j + 1); the constraints over it are the AIR's own.  num and den read neither AUX_LOCAL nor AUX_NEXT.
+  struct AuxColumn {
+    uint32_t num, den;   // node indices
+  };
+  struct Aux {
+    uint32_t n_challenges = 0;        // 0..MAX_CHALLENGES
+    std::vector<AuxColumn> columns;   // 0..MAX_AUX
+    uint32_t width() const { return (uint32_t)columns.size(); }
+  };
+  Aux aux;
+  // whether any node is a CHALLENGE, AUX_LOCAL or AUX_NEXT: such an AIR is evaluated in F_p^2 throughout
+  bool reads_aux() const {
+    for (const Node& nd : nodes)
+      if (nd.op >= CHALLENGE && nd.op <= AUX_NEXT) return true;
+    return false;
+  }
   std::vector<Node> nodes;
   std::vector<Constraint> constraints;
   // throws std::invalid_argument on malformed programs (a PUBLIC index >= n_public, n_public > MAX_PUBLIC, a PERIODIC index
@@ -156,51 +192,82 @@ struct AirProgram {
 
   // Generic evaluation, nodes computed on demand in constraint order (so that the circuit form emits
   // its gates in the order the reference's hand-written `eval` does).  ops: cst(u64), pub(index), per(column),
-  // prep_local(column), prep_next(column), add, sub, mul.
+  // prep_local(column), prep_next(column), challenge(index), aux_local(column), aux_next(column), add, sub, mul.
   template <class T, class Ops, class Emit>
   void fold(const std::vector<T>& local, const std::vector<T>& next, const T sel[4], Ops& ops, Emit&& emit) const {
-    std::vector<T> val(nodes.size());
-    std::vector<char> have(nodes.size(), 0);
+    NodeValues<T> nv(nodes.size());
     for (const Constraint& c : constraints) {
-      // iterative post-order evaluation of the sub-DAG under c.node
-      std::vector<uint32_t> stack{c.node};
-      while (!stack.empty()) {
-        uint32_t i = stack.back();
-        if (have[i]) {
-          stack.pop_back();
+      const T& v = node_value(c.node, nv, local, next, ops);
+      emit(c.when == ALWAYS ? v : ops.mul(sel[c.when], v));
+    }
+  }
+  // The auxiliary columns' terms on one row: emit(column, num_j, den_j) in column order, nodes computed on demand in that
+  // order and shared between the columns.
+  template <class T, class Ops, class Emit>
+  void fold_aux(const std::vector<T>& local, const std::vector<T>& next, Ops& ops, Emit&& emit) const {
+    NodeValues<T> nv(nodes.size());
+    for (size_t j = 0; j < aux.columns.size(); j++) {
+      const T num = node_value(aux.columns[j].num, nv, local, next, ops);
+      const T den = node_value(aux.columns[j].den, nv, local, next, ops);
+      emit(j, num, den);
+    }
+  }
+
+ private:
+  template <class T>
+  struct NodeValues {
+    std::vector<T> val;
+    std::vector<char> have;
+    explicit NodeValues(size_t n) : val(n), have(n, 0) {}
+  };
+  // iterative post-order evaluation of the sub-DAG under `root`
+  template <class T, class Ops>
+  const T& node_value(uint32_t root, NodeValues<T>& nv, const std::vector<T>& local, const std::vector<T>& next, Ops& ops) const {
+    std::vector<T>& val = nv.val;
+    std::vector<char>& have = nv.have;
+    std::vector<uint32_t> stack{root};
+    while (!stack.empty()) {
+      uint32_t i = stack.back();
+      if (have[i]) {
+        stack.pop_back();
+        continue;
+      }
+      const Node& nd = nodes[i];
+      if (nd.op == LOCAL) {
+        val[i] = local[nd.a];
+      } else if (nd.op == NEXT) {
+        val[i] = next[nd.a];
+      } else if (nd.op == CONST) {
+        val[i] = ops.cst(nd.value);
+      } else if (nd.op == PUBLIC) {
+        val[i] = ops.pub(nd.a);
+      } else if (nd.op == PERIODIC) {
+        val[i] = ops.per(nd.a);
+      } else if (nd.op == PREP_LOCAL) {
+        val[i] = ops.prep_local(nd.a);
+      } else if (nd.op == PREP_NEXT) {
+        val[i] = ops.prep_next(nd.a);
+      } else if (nd.op == CHALLENGE) {
+        val[i] = ops.challenge(nd.a);
+      } else if (nd.op == AUX_LOCAL) {
+        val[i] = ops.aux_local(nd.a);
+      } else if (nd.op == AUX_NEXT) {
+        val[i] = ops.aux_next(nd.a);
+      } else {
+        if (!have[nd.a]) {
+          stack.push_back(nd.a);
           continue;
         }
-        const Node& nd = nodes[i];
-        if (nd.op == LOCAL) {
-          val[i] = local[nd.a];
-        } else if (nd.op == NEXT) {
-          val[i] = next[nd.a];
-        } else if (nd.op == CONST) {
-          val[i] = ops.cst(nd.value);
-        } else if (nd.op == PUBLIC) {
-          val[i] = ops.pub(nd.a);
-        } else if (nd.op == PERIODIC) {
-          val[i] = ops.per(nd.a);
-        } else if (nd.op == PREP_LOCAL) {
-          val[i] = ops.prep_local(nd.a);
-        } else if (nd.op == PREP_NEXT) {
-          val[i] = ops.prep_next(nd.a);
-        } else {
-          if (!have[nd.a]) {
-            stack.push_back(nd.a);
-            continue;
-          }
-          if (!have[nd.b]) {
-            stack.push_back(nd.b);
-            continue;
-          }
-          val[i] = nd.op == ADD ? ops.add(val[nd.a], val[nd.b]) : nd.op == SUB ? ops.sub(val[nd.a], val[nd.b]) : ops.mul(val[nd.a], val[nd.b]);
+        if (!have[nd.b]) {
+          stack.push_back(nd.b);
+          continue;
         }
-        have[i] = 1;
-        stack.pop_back();
+        val[i] = nd.op == ADD ? ops.add(val[nd.a], val[nd.b]) : nd.op == SUB ? ops.sub(val[nd.a], val[nd.b]) : ops.mul(val[nd.a], val[nd.b]);
       }
-      emit(c.when == ALWAYS ? val[c.node] : ops.mul(sel[c.when], val[c.node]));
+      have[i] = 1;
+      stack.pop_back();
     }
+    return val[root];
   }
 };
 struct ProgramAir : Air {
@@ -213,6 +280,8 @@ struct ProgramAir : Air {
   std::vector<Ext> periodic_at(CircuitBuilder& cb, const Ext& zeta, int log_n) const override;
   int preprocessed_width() const override { return (int)prog.prep.width; }
   std::array<u64, 4> preprocessed_commit(int log_n, int log_blowup) const override;   // p3_prover.cpp
+  int n_challenges() const override { return (int)prog.aux.n_challenges; }
+  int aux_width() const override { return (int)prog.aux.width(); }
   void eval(VerifierConstraintFolder& folder, CircuitBuilder& cb) const override;
 };
 
@@ -223,6 +292,9 @@ struct ProgramAir : Air {
 // preprocessed columns adds their openings and a third batch per query to the proof's targets (include/p25.h "PREPROCESSED
 // COLUMNS" has the positions), holds their commitment as four constants, observes it directly after the trace commitment
 // and hands the opening proof a third (commitment, matrices, points) entry; without such columns the circuit is as it was.
+// An AIR with auxiliary columns (include/p25.h "AUXILIARY COLUMNS") samples its challenges behind the public values, then
+// observes the auxiliary commitment -- a proof target, not a constant -- before alpha, and hands the opening proof one more
+// entry, the last; without such columns the circuit is as it was.
 P3ProofTarget p3_verify_proof(CircuitBuilder& cb, const P3Config& config, const Air& air);
 
 // gadget-level entry points (src/p3/mod.rs:40-45, 96-147), exposed for the gadget tests

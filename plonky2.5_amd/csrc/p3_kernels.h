@@ -13,11 +13,15 @@ namespace p25 {
 // words of the columns before it (at most 31 * 256), and its value comes from the caller of run_air -- a table word in the
 // quotient kernel, q_c(zeta^(n/P)) in the identity lanes.  PREP_LOCAL / PREP_NEXT (index = preprocessed column) are read
 // through run_air's `load` like LOCAL / NEXT: from the handle's shared LDE in the quotient kernel, from the proof's
-// preprocessed openings in the identity lanes.
+// preprocessed openings in the identity lanes.  CHALLENGE (index = challenge) is read from the proof's challenge words;
+// AUX_LOCAL / AUX_NEXT (index = auxiliary column) through `load` again, which recomposes the column's two components.
+// The three take no slot and stand only in programs that run in ExtF.
 enum : uint32_t { P3_OPND_SLOT = 0, P3_OPND_LOCAL = 1, P3_OPND_NEXT = 2, P3_OPND_CONST = 3, P3_OPND_PUBLIC = 4,
-                  P3_OPND_PERIODIC = 5, P3_OPND_PREP_LOCAL = 6, P3_OPND_PREP_NEXT = 7 };
-// what run_air's load(which, column) is asked for: bit 0 the next row, bit 1 the preprocessed matrix
-enum : int { P3_LOAD_LOCAL = 0, P3_LOAD_NEXT = 1, P3_LOAD_PREP_LOCAL = 2, P3_LOAD_PREP_NEXT = 3 };
+                  P3_OPND_PERIODIC = 5, P3_OPND_PREP_LOCAL = 6, P3_OPND_PREP_NEXT = 7, P3_OPND_CHALLENGE = 8,
+                  P3_OPND_AUX_LOCAL = 9, P3_OPND_AUX_NEXT = 10 };
+// what run_air's load(which, column) is asked for: bit 0 the next row, bit 1 the preprocessed matrix, bit 2 the auxiliary one
+enum : int { P3_LOAD_LOCAL = 0, P3_LOAD_NEXT = 1, P3_LOAD_PREP_LOCAL = 2, P3_LOAD_PREP_NEXT = 3, P3_LOAD_AUX_LOCAL = 4,
+             P3_LOAD_AUX_NEXT = 5 };
 GL_HD uint32_t p3_per_log_period(uint32_t index) { return index >> 24; }
 GL_HD uint32_t p3_per_offset(uint32_t index) { return index & 0xffffffu; }
 enum : uint32_t { P3_OP_ADD = 3, P3_OP_SUB = 4, P3_OP_MUL = 5, P3_OP_EMIT = 6 };  // ADD..MUL as AirProgram::Op
@@ -35,9 +39,18 @@ constexpr uint32_t P3_MAX_INSTR = 1u << 20;
 constexpr int P3_TREE_COOP_MAX = 1 << 16;
 constexpr int P3_TREE_TOP_NODES = 16;
 constexpr int P3_TAIL_LOG = 10;
+// The prefix sum over an auxiliary column (k_p3_aux_scan_block / _totals / _finish, kernels_p3.hip): rows per block of the
+// block-local scan, and block totals per tile of the totals pass, which walks its tiles one after the other in ONE
+// workgroup per (proof, column).  The tests read these two from this file: the totals take a second tile from
+// P3_AUX_SCAN_BLOCK * P3_AUX_TOTALS_TILE rows on.
+constexpr int P3_AUX_SCAN_BLOCK = 256;
+constexpr int P3_AUX_TOTALS_TILE = 256;
 
 struct P3AirDevice {
   std::vector<P3Instr> instr;
+  // for an AIR with auxiliary columns, their terms' program: it emits num_0, den_0, num_1, den_1, ... in column order and
+  // shares `consts` (and the slots' limit) with the AIR's own
+  std::vector<P3Instr> aux_instr;
   // the CONST nodes' values; P3ProverDev appends the periodic columns' coefficients and tables (P3Shape::per_coef, per_tab)
   std::vector<u64> consts;
   uint32_t max_live = 0;
@@ -66,13 +79,18 @@ struct P3Shape {
   uint32_t per_coef, per_tab;
   // The preprocessed columns: PW of them (0: none), in P3Bufs::pcoef / plde / ptree, shared like the periodic tables.
   uint32_t PW;
+  // The challenge phase: NC challenges, AW auxiliary columns (0: none; then the chain runs the phases it ran), the
+  // instructions of their terms' program, and per_val -- the periodic columns' VALUES on the trace domain, behind the
+  // tables in P3Bufs::consts (column c at per_val + off, read by row mod P), which only the term kernel reads.
+  uint32_t NC, AW, n_aux_instr, per_val;
   u64 w[26], w_inv[26];           // primitive 2^i-th roots of unity and their inverses
   u64 zh[8], zh_inv[8];           // x^n - 1 on the quotient coset, by chunk
   u64 s_inv[8];                   // 1 / s_c
   u64 g_inv;                      // 1 / w_n
   // hdr: the proof's first words (trace root | quotient root | trace_local | trace_next | chunks | prep_local | prep_next |
-  // FRI roots from o_fri), then points (zeta, zeta w_n, zeta / s_c), powers of fri_alpha, betas, query indices
-  uint32_t hdr_words, o_fri, o_points, o_apow, o_betas, o_idx, hdr_stride;
+  // from o_aux: aux root | aux_local | aux_next | FRI roots from o_fri), then points (zeta, zeta w_n, zeta / s_c), powers of
+  // fri_alpha, betas, query indices, the challenges from o_chal
+  uint32_t hdr_words, o_fri, o_points, o_apow, o_betas, o_idx, hdr_stride, o_aux, o_chal;
   uint32_t sz_a, sz_b;            // words per query: commit-phase openings, input openings
 };
 struct P3Bufs {
@@ -91,6 +109,13 @@ struct P3Bufs {
   // constant tables of the handle, made once on the device (P3ProverDev::ensure_preprocessed), the same for every proof
   // of every group -- no blockIdx.y offset ever applies to them; null when PW = 0
   const u64 *pcoef, *plde, *ptree;
+  // The challenge phase, per proof of the group like the trace's buffers: the auxiliary matrix's 2 AW base columns on the
+  // trace domain [G][2 AW][n] (column j's components at 2 j and 2 j + 1), coefficients, LDE on 7 H_{N2} in bit-reversed
+  // order [G][2 AW][N2], tree [G][8 N2], and the scan's block totals [G][AW][2][blocks]; null when AW = 0
+  u64 *avals, *acoef, *alde, *atree, *atot;
+  const P3Instr* aux_prog;
+  // the preprocessed columns' values on the trace domain [PW][n], kept by handles with auxiliary columns for the term kernel
+  const u64* pvals;
 };
 
 // words of level l of a tree over h leaves (levels concatenated, 4 words per digest), FRI layer r, FRI tree r
@@ -98,7 +123,9 @@ GL_HD size_t p3_level_off(size_t h, unsigned l) { return 8 * (h - (h >> l)); }
 GL_HD size_t p3_layer_off(size_t N2, unsigned r) { return 4 * (N2 - (N2 >> r)); }
 GL_HD size_t p3_ftree_off(size_t N2, unsigned r) { return 8 * (N2 - (N2 >> r)); }
 
-enum : uint32_t { P3_CH_TRACE = 0, P3_CH_QUOTIENT = 1, P3_CH_FRI_ALPHA = 2, P3_CH_FRI_ROUND = 3, P3_CH_QUERIES = 4 };
+// P3_CH_AUX stands between TRACE and QUOTIENT for a handle with auxiliary columns: TRACE then ends with the challenges
+// instead of alpha, and AUX observes the auxiliary root and samples alpha.
+enum : uint32_t { P3_CH_TRACE = 0, P3_CH_QUOTIENT = 1, P3_CH_FRI_ALPHA = 2, P3_CH_FRI_ROUND = 3, P3_CH_QUERIES = 4, P3_CH_AUX = 5 };
 
 void p3_launch_transpose(const u64* d_traces, size_t trace_stride, const P3Shape& s, const P3Bufs& b, hipStream_t st);
 // leaves of the column matrix at base + g * proof_stride + (c >> 1) * pair_stride + (c & 1) * col_stride, then the tree
@@ -108,6 +135,8 @@ void p3_launch_commit_cols(const u64* base, size_t proof_stride, size_t pair_str
 void p3_launch_commit_rows4(const u64* rows, size_t rows_stride, size_t h, u64* tree, size_t tree_stride, uint32_t G,
                             hipStream_t st);
 void p3_launch_chain(const P3Shape& s, const P3Bufs& b, uint32_t phase, uint32_t round, hipStream_t st);
+// the auxiliary columns on the trace domain: terms (one inversion per row), then the exclusive prefix sum in three launches
+void p3_launch_aux_columns(const P3Shape& s, const P3Bufs& b, hipStream_t st);
 void p3_launch_quotient(const P3Shape& s, const P3Bufs& b, hipStream_t st);
 void p3_launch_openings(const P3Shape& s, const P3Bufs& b, hipStream_t st);   // evaluations, then the identity check
 void p3_launch_reduced(const P3Shape& s, const P3Bufs& b, hipStream_t st);
@@ -145,6 +174,9 @@ class P3ProverDev {
   // The 4 words of the preprocessed commitment as the device computed them (the first call computes them: a handle that
   // has only verified, or done nothing yet, makes the tables in a temporary and frees it).  Throws without columns.
   void preprocessed_commit(u64 out[4]);
+  // The device time (HIP events) of the challenge phase -- terms, prefix sum, the auxiliary commit, its chain launch -- of
+  // the LAST group the handle proved; waits for it.  Throws for a handle without auxiliary columns or before its first proof.
+  double aux_stage_ms();
   void set_scratch_budget(size_t bytes) { budget_bytes_ = bytes ? bytes : P3_SCRATCH_BUDGET_BYTES; }
   // enqueue-only on `st`.  d_public: [n_proofs][n_public], packed (unread when n_public = 0)
   void prove_dev(const u64* d_traces, size_t trace_stride, const u64* d_public, size_t n_proofs, const u64* d_pow_starts,

@@ -2,6 +2,7 @@
 #include "p3_prover.h"
 #include <array>
 #include <functional>
+#include <mutex>
 #include <stdexcept>
 #include <thread>
 #include "poseidon2.h"
@@ -215,6 +216,10 @@ struct BaseOps {
   const std::vector<u64>&pl, &pn;   // the preprocessed columns at the current point and at the next row's
   u64 prep_local(uint32_t c) { return pl[c]; }
   u64 prep_next(uint32_t c) { return pn[c]; }
+  // an AIR that reads a challenge or an auxiliary column is evaluated in F_p^2 (ExtOps): never here
+  u64 challenge(uint32_t) { throw std::logic_error("p3 prover: a challenge in a base-field evaluation"); }
+  u64 aux_local(uint32_t) { throw std::logic_error("p3 prover: an auxiliary column in a base-field evaluation"); }
+  u64 aux_next(uint32_t) { throw std::logic_error("p3 prover: an auxiliary column in a base-field evaluation"); }
   u64 cst(u64 v) { return v; }
   u64 pub(uint32_t i) { return pv[i]; }
   u64 per(uint32_t c) { return pc[c]; }
@@ -228,6 +233,10 @@ struct ExtOps {
   const std::vector<E2>&pl, &pn;    // the preprocessed columns at zeta and zeta w_n
   E2 prep_local(uint32_t c) { return pl[c]; }
   E2 prep_next(uint32_t c) { return pn[c]; }
+  const std::vector<E2>&ch, &al, &an;   // the challenges; the auxiliary columns (recomposed) at the point and at the next row's
+  E2 challenge(uint32_t i) { return ch[i]; }
+  E2 aux_local(uint32_t c) { return al[c]; }
+  E2 aux_next(uint32_t c) { return an[c]; }
   E2 cst(u64 v) { return gl::e2(v); }
   E2 pub(uint32_t i) { return gl::e2(pv[i]); }
   E2 per(uint32_t c) { return pc[c]; }
@@ -323,6 +332,79 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
   ch.observe_digest(trace_tree.root());
   if (PW) ch.observe_digest(prep.tree.root());
   for (u64 v : pub) ch.observe(v);   // uni-stark's challenger.observe_slice(public_values): unpinned (include/p25.h)
+
+  // The challenge phase (include/p25.h "AUXILIARY COLUMNS"): the challenges, then the running sums they determine, committed
+  // as the trace is -- 2 AW base columns, column j's components at 2 j and 2 j + 1 -- and observed before alpha.
+  const int AW = (int)air.aux.width(), NC = (int)air.aux.n_challenges;
+  std::vector<E2> chal(NC);
+  for (auto& c : chal) c = ch.sample_ext();
+  PrepCommit aux;
+  if (AW) {
+    std::vector<E2> term(n * AW);   // t_j(i) at [i * AW + j]
+    size_t bad_row = n, bad_col = 0;
+    std::mutex bad_mutex;
+    parallel_for(T, n, [&](size_t b, size_t e) {
+      const size_t NP = air.periodic.size();
+      std::vector<E2> loc(W), nxt(W), per(NP), ploc(PW), pnxt(PW), none, num(AW), den(AW), pre(AW);
+      ExtOps ops{pub, per, ploc, pnxt, chal, none, none};
+      for (size_t i = b; i < e; i++) {
+        const size_t i1 = (i + 1) & (n - 1);
+        for (int c = 0; c < W; c++) {
+          loc[c] = gl::e2(col[c][i]);
+          nxt[c] = gl::e2(col[c][i1]);
+        }
+        for (int c = 0; c < PW; c++) {
+          ploc[c] = gl::e2(air.prep.values[i * PW + c]);
+          pnxt[c] = gl::e2(air.prep.values[i1 * PW + c]);
+        }
+        for (size_t c = 0; c < NP; c++) per[c] = gl::e2(air.periodic[c].values[i & (air.periodic[c].values.size() - 1)]);
+        air.fold_aux<E2>(loc, nxt, ops, [&](size_t j, E2 nu, E2 de) {
+          num[j] = nu;
+          den[j] = de;
+        });
+        // one inversion per row (Montgomery's trick over the row's AW denominators)
+        E2 acc = gl::e2(1);
+        int zero = -1;
+        for (int j = 0; j < AW; j++) {
+          pre[j] = acc;
+          if (gl::eq(den[j], gl::e2(0))) {
+            if (zero < 0) zero = j;
+          } else {
+            acc = gl::mul(acc, den[j]);
+          }
+        }
+        if (zero >= 0) {
+          std::lock_guard<std::mutex> lock(bad_mutex);
+          if (i < bad_row) {
+            bad_row = i;
+            bad_col = (size_t)zero;
+          }
+          continue;
+        }
+        E2 inv = gl::inv(acc);
+        for (int j = AW; j-- > 0;) {
+          term[i * AW + j] = gl::mul(num[j], gl::mul(inv, pre[j]));
+          inv = gl::mul(inv, den[j]);
+        }
+      }
+    });
+    if (bad_row < n)
+      throw std::invalid_argument("p3_prove: auxiliary column " + std::to_string(bad_col) + " has a zero denominator on row " +
+                                  std::to_string(bad_row));
+    AirProgram::Preprocessed am;   // S_j(0) = 0, S_j(i + 1) = S_j(i) + t_j(i), component-split, row-major
+    am.width = 2 * (uint32_t)AW;
+    am.log_n = (uint32_t)k;
+    am.values.resize(n * 2 * AW);
+    std::vector<E2> run(AW, gl::e2(0));
+    for (size_t i = 0; i < n; i++)
+      for (int j = 0; j < AW; j++) {
+        am.values[i * 2 * AW + 2 * j] = run[j].a;
+        am.values[i * 2 * AW + 2 * j + 1] = run[j].b;
+        run[j] = gl::add(run[j], term[i * AW + j]);
+      }
+    aux = commit_preprocessed(am, B, T);
+    ch.observe_digest(aux.tree.root());
+  }
   const E2 alpha = ch.sample_ext();
 
   // Quotient chunks: 2^lqd of them, lqd = log2_ceil(max constraint degree - 1) with the selector's degree counted (uni-stark's
@@ -354,6 +436,9 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
     std::vector<u64> ploc(PW), pnxt(PW);
     BaseOps ops{pub, per, ploc, pnxt};
     std::vector<u64> loc(W), nxt(W);
+    const bool ext_air = air.reads_aux();
+    std::vector<E2> eloc(W), enxt(W), eper(NP), eploc(PW), epnxt(PW), eal(AW), ean(AW);
+    ExtOps eops{pub, eper, eploc, epnxt, chal, eal, ean};
     for (size_t j = 0; j < nq; j++, x = gl::mul(x, w_q)) {
       const size_t i0 = lde_step * j, i1 = (lde_step * j + row_step) % N2;   // the next ROW is x w_n = 2^B LDE points on
       for (int c = 0; c < W; c++) {
@@ -370,6 +455,23 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
       const u64 is_trans = gl::sub(x, g_inv);
       const u64 sel[4] = {0, gl::mul(zhx, gl::inv(gl::sub(x, 1))), gl::mul(zhx, gl::inv(is_trans)), is_trans};
       E2 acc = gl::e2(0);
+      if (ext_air) {   // an AIR that reads a challenge or an auxiliary column: F_p^2 throughout, every other operand embedded
+        for (int c = 0; c < W; c++) {
+          eloc[c] = gl::e2(loc[c]);
+          enxt[c] = gl::e2(nxt[c]);
+        }
+        for (int c = 0; c < PW; c++) {
+          eploc[c] = gl::e2(ploc[c]);
+          epnxt[c] = gl::e2(pnxt[c]);
+        }
+        for (size_t c = 0; c < NP; c++) eper[c] = gl::e2(per[c]);
+        for (int c = 0; c < AW; c++) {
+          eal[c] = E2{aux.lde_nat[2 * c][i0], aux.lde_nat[2 * c + 1][i0]};
+          ean[c] = E2{aux.lde_nat[2 * c][i1], aux.lde_nat[2 * c + 1][i1]};
+        }
+        const E2 esel[4] = {gl::e2(0), gl::e2(sel[1]), gl::e2(sel[2]), gl::e2(sel[3])};
+        air.fold<E2>(eloc, enxt, esel, eops, [&](E2 c) { acc = gl::add(gl::mul(acc, alpha), c); });
+      } else
       air.fold<u64>(loc, nxt, sel, ops, [&](u64 c) {  // VerifierConstraintFolder::assert_zero: acc = acc * alpha + c
         acc = gl::mul(acc, alpha);
         acc.a = gl::add(acc.a, c);
@@ -417,6 +519,11 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
     p_local[c] = eval_ext(prep.coef[c], zeta);
     p_next[c] = eval_ext(prep.coef[c], zeta_next);
   }
+  std::vector<E2> a_local(2 * AW), a_next(2 * AW);   // the auxiliary matrix's base columns
+  for (int c = 0; c < 2 * AW; c++) {
+    a_local[c] = eval_ext(aux.coef[c], zeta);
+    a_next[c] = eval_ext(aux.coef[c], zeta_next);
+  }
   std::vector<E2> qz(2 * Q);                      // q_c's components at zeta = P_c at zeta / s_c
   for (size_t c = 0; c < Q; c++) {
     const E2 z_over_s = gl::mul(zeta, gl::inv(s_c[c]));
@@ -431,7 +538,13 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
     std::vector<E2> per;
     for (size_t c = 0; c < air.periodic.size(); c++)
       per.push_back(eval_ext(air.periodic_coefficients(c), gl::exp_pow2(zeta, k - (int)air.periodic[c].log_period)));
-    ExtOps ops{pub, per, p_local, p_next};
+    // an auxiliary column at a point: o[2 a] + X o[2 a + 1], X the extension's generator, as the chunks are recomposed
+    std::vector<E2> al(AW), an(AW);
+    for (int c = 0; c < AW; c++) {
+      al[c] = gl::add(a_local[2 * c], gl::mul(a_local[2 * c + 1], E2{0, 1}));
+      an[c] = gl::add(a_next[2 * c], gl::mul(a_next[2 * c + 1], E2{0, 1}));
+    }
+    ExtOps ops{pub, per, p_local, p_next, chal, al, an};
     E2 acc = gl::e2(0);
     air.fold<E2>(t_local, t_next, sel, ops, [&](E2 c) { acc = gl::add(gl::mul(acc, alpha), c); });
     E2 lhs = gl::mul(acc, gl::inv(z_h));
@@ -455,7 +568,7 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
   const E2 fri_alpha = ch.sample_ext();
   std::vector<E2> folded(N2);
   {
-    std::vector<E2> apow(2 * W + 2 * Q + 2 * PW);
+    std::vector<E2> apow(2 * W + 2 * Q + 2 * PW + 4 * AW);
     apow[0] = gl::e2(1);
     for (size_t i = 1; i < apow.size(); i++) apow[i] = gl::mul(apow[i - 1], fri_alpha);
     parallel_for(T, N2, [&](size_t b, size_t e) {
@@ -477,6 +590,11 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
           acc = gl::add(acc, gl::mul(apow[t], gl::mul(gl::sub(gl::e2(prep.rows[i * PW + c]), p_local[c]), inv_z)));
         for (int c = 0; c < PW; c++, t++)
           acc = gl::add(acc, gl::mul(apow[t], gl::mul(gl::sub(gl::e2(prep.rows[i * PW + c]), p_next[c]), inv_zn)));
+        // the last batch: the auxiliary matrix's 2 AW base columns at zeta, then at zeta w_n; the trace's height again
+        for (int c = 0; c < 2 * AW; c++, t++)
+          acc = gl::add(acc, gl::mul(apow[t], gl::mul(gl::sub(gl::e2(aux.rows[i * 2 * AW + c]), a_local[c]), inv_z)));
+        for (int c = 0; c < 2 * AW; c++, t++)
+          acc = gl::add(acc, gl::mul(apow[t], gl::mul(gl::sub(gl::e2(aux.rows[i * 2 * AW + c]), a_next[c]), inv_zn)));
         folded[i] = acc;
       }
     });
@@ -546,6 +664,11 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
   for (auto& e : qz) push_e(e);
   for (auto& e : p_local) push_e(e);
   for (auto& e : p_next) push_e(e);
+  if (AW) {
+    push_d(aux.tree.root());
+    for (auto& e : a_local) push_e(e);
+    for (auto& e : a_next) push_e(e);
+  }
   for (auto& t : fri_trees) push_d(t.root());
   for (size_t ix : indices) {
     size_t idx = ix;
@@ -567,8 +690,12 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
       for (int c = 0; c < PW; c++) out.push_back(prep.rows[ix * PW + c]);
       for (auto& d : prep.tree.prove(ix)) push_d(d);
     }
+    if (AW) {
+      for (int c = 0; c < 2 * AW; c++) out.push_back(aux.rows[ix * 2 * AW + c]);
+      for (auto& d : aux.tree.prove(ix)) push_d(d);
+    }
   }
-  if (out.size() != cfg.num_inputs() + p3_preprocessed_words(PW, k, B, prm.num_queries)) throw std::logic_error("p3 prover: flattened size mismatch");
+  if (out.size() != cfg.num_inputs() + p3_preprocessed_words(PW, k, B, prm.num_queries) + p3_aux_words(AW, k, B, prm.num_queries)) throw std::logic_error("p3 prover: flattened size mismatch");
   out.insert(out.end(), pub.begin(), pub.end());   // plonky3's Proof holds no public values: they travel behind it
   return out;
 }

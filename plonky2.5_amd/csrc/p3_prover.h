@@ -54,6 +54,14 @@ std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::v
 inline size_t p3_preprocessed_words(int prep_width, int log_n, int log_blowup, int num_queries) {
   return prep_width ? 4 * (size_t)prep_width + (size_t)num_queries * ((size_t)prep_width + 4 * (size_t)(log_n + log_blowup)) : 0;
 }
+// Auxiliary columns (AirProgram::Aux; include/p25.h "AUXILIARY COLUMNS") travel in `air.aux`: every prover here samples the
+// challenges behind the public values, builds the running sums, commits them as 2 AW base columns, observes that root and
+// only then samples alpha; it opens them behind the preprocessed openings and adds a last batch to every query.  A zero
+// denominator throws std::invalid_argument naming column and row.  Without such columns the words are unchanged.
+// The words such a proof has beyond P3Config::num_inputs(): the root, the two openings and every query's row and path.
+inline size_t p3_aux_words(int aux_width, int log_n, int log_blowup, int num_queries) {
+  return aux_width ? 4 + 8 * (size_t)aux_width + (size_t)num_queries * (2 * (size_t)aux_width + 4 * (size_t)(log_n + log_blowup)) : 0;
+}
 // The commitment of a preprocessed matrix: the Poseidon2 MMCS root over the columns' LDE on 7 H_{n 2^log_blowup} in
 // bit-reversed leaf order, the commit the trace gets.  Throws std::invalid_argument (width 0 included: nothing to commit).
 std::array<u64, 4> p3_preprocessed_commit(const AirProgram::Preprocessed& prep, int log_blowup, int threads);

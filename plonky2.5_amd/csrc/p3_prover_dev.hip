@@ -10,12 +10,18 @@ namespace p25 {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // AirProgram -> register program.  Nodes are visited in the order AirProgram::fold evaluates them; a LOCAL / NEXT / CONST /
-// PUBLIC / PERIODIC / PREP_LOCAL / PREP_NEXT node becomes an operand, an arithmetic node takes a slot from its evaluation to its last use.
+// PUBLIC / PERIODIC / PREP_LOCAL / PREP_NEXT / CHALLENGE / AUX_LOCAL / AUX_NEXT node becomes an operand, an arithmetic node takes a slot from its evaluation to its last use.
 // ---------------------------------------------------------------------------------------------------------------------
-P3AirDevice P3AirDevice::compile(const AirProgram& air) {
+namespace {
+struct P3Root {
+  uint32_t node, tag;   // tag: what the EMIT carries in `dst` -- a constraint's `when`, an auxiliary term's output index
+};
+// one register program emitting `roots` in order; CONST operands are appended to `consts`
+std::vector<P3Instr> compile_roots(const AirProgram& air, const std::vector<P3Root>& roots, std::vector<u64>& consts,
+                                   uint32_t& max_live) {
   typedef AirProgram A;
   const size_t N = air.nodes.size();
-  P3AirDevice out;
+  std::vector<P3Instr> instr;
   auto is_leaf = [&](uint32_t i) { return air.nodes[i].op <= A::CONST || air.nodes[i].op >= A::PUBLIC; };
   // uses of every arithmetic node by the nodes and constraints that are evaluated
   std::vector<uint32_t> uses(N, 0);
@@ -34,7 +40,7 @@ P3AirDevice P3AirDevice::compile(const AirProgram& air) {
       stack.push_back(air.nodes[i].b);
     }
   };
-  for (const auto& c : air.constraints) {
+  for (const auto& c : roots) {
     uses[c.node]++;
     count(c.node);
   }
@@ -48,6 +54,9 @@ P3AirDevice P3AirDevice::compile(const AirProgram& air) {
     if (nd.op == A::PUBLIC) return (P3_OPND_PUBLIC << 28) | nd.a;
     if (nd.op == A::PREP_LOCAL) return (P3_OPND_PREP_LOCAL << 28) | nd.a;
     if (nd.op == A::PREP_NEXT) return (P3_OPND_PREP_NEXT << 28) | nd.a;
+    if (nd.op == A::CHALLENGE) return (P3_OPND_CHALLENGE << 28) | nd.a;
+    if (nd.op == A::AUX_LOCAL) return (P3_OPND_AUX_LOCAL << 28) | nd.a;
+    if (nd.op == A::AUX_NEXT) return (P3_OPND_AUX_NEXT << 28) | nd.a;
     if (nd.op == A::PERIODIC) {
       uint32_t off = 0;   // words of the columns before it
       for (uint32_t c = 0; c < nd.a; c++) off += 1u << air.periodic[c].log_period;
@@ -56,8 +65,8 @@ P3AirDevice P3AirDevice::compile(const AirProgram& air) {
     if (nd.op == A::CONST) {
       if (!have[i]) {
         have[i] = 1;
-        const_index[i] = (uint32_t)out.consts.size();
-        out.consts.push_back(nd.value);
+        const_index[i] = (uint32_t)consts.size();
+        consts.push_back(nd.value);
       }
       return (P3_OPND_CONST << 28) | const_index[i];
     }
@@ -70,7 +79,7 @@ P3AirDevice P3AirDevice::compile(const AirProgram& air) {
       live--;
     }
   };
-  for (const auto& c : air.constraints) {
+  for (const auto& c : roots) {
     std::vector<uint32_t> stack{c.node};
     while (!stack.empty()) {
       const uint32_t i = stack.back();
@@ -94,21 +103,38 @@ P3AirDevice P3AirDevice::compile(const AirProgram& air) {
       in.dst = slot_of[i] = free_slots.back();
       free_slots.pop_back();
       live++;
-      out.max_live = std::max(out.max_live, live);
-      out.instr.push_back(in);
+      max_live = std::max(max_live, live);
+      instr.push_back(in);
       have[i] = 1;
       stack.pop_back();
     }
-    out.instr.push_back(P3Instr{P3_OP_EMIT, c.when, operand(c.node), 0});
+    instr.push_back(P3Instr{P3_OP_EMIT, c.tag, operand(c.node), 0});
     release(c.node);
   }
-  if (out.consts.empty()) out.consts.push_back(0);
   if (n_slots > P3_MAX_LIVE)
     throw std::invalid_argument("p25_p3_prover_create: the AIR keeps " + std::to_string(n_slots) +
                                 " intermediate values alive at once; the device form holds at most " + std::to_string(P3_MAX_LIVE));
-  if (out.instr.size() > P3_MAX_INSTR || out.consts.size() >= (1u << 28))
+  if (instr.size() > P3_MAX_INSTR || consts.size() >= (1u << 28))
     throw std::invalid_argument("p25_p3_prover_create: the AIR compiles to more than " + std::to_string(P3_MAX_INSTR) +
                                 " instructions, the device form's limit");
+  return instr;
+}
+}  // namespace
+
+P3AirDevice P3AirDevice::compile(const AirProgram& air) {
+  P3AirDevice out;
+  std::vector<P3Root> roots;
+  for (const auto& c : air.constraints) roots.push_back(P3Root{c.node, c.when});
+  out.instr = compile_roots(air, roots, out.consts, out.max_live);
+  if (air.aux.width()) {   // the auxiliary columns' terms: num_0, den_0, num_1, den_1, ...
+    roots.clear();
+    for (uint32_t j = 0; j < air.aux.width(); j++) {
+      roots.push_back(P3Root{air.aux.columns[j].num, 2 * j});
+      roots.push_back(P3Root{air.aux.columns[j].den, 2 * j + 1});
+    }
+    out.aux_instr = compile_roots(air, roots, out.consts, out.max_live);
+  }
+  if (out.consts.empty()) out.consts.push_back(0);
   return out;
 }
 
@@ -130,6 +156,10 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
   s.PW = air.prep.width;
   if (s.PW) prep_values_ = air.prep.values;
   const uint32_t PW = s.PW;
+  s.NC = air.aux.n_challenges;
+  s.AW = air.aux.width();
+  s.n_aux_instr = (uint32_t)prog_.aux_instr.size();
+  const uint32_t AW = s.AW;
   // the periodic columns go up with the constants: every column's coefficients, then every column's table
   s.per_coef = (uint32_t)prog_.consts.size();
   std::vector<u64> tables;
@@ -140,6 +170,9 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
   }
   s.per_tab = (uint32_t)prog_.consts.size();
   prog_.consts.insert(prog_.consts.end(), tables.begin(), tables.end());
+  s.per_val = (uint32_t)prog_.consts.size();
+  if (AW)   // the term kernel reads the columns on the trace domain: their values, by row mod P
+    for (const auto& pc : air.periodic) prog_.consts.insert(prog_.consts.end(), pc.values.begin(), pc.values.end());
   // FRI layers of at most 2^P3_TAIL_LOG values fold in one workgroup per proof
   s.tail_round = L > P3_TAIL_LOG ? std::min(k, L - P3_TAIL_LOG) : 0;
   for (int i = 0; i < 26; i++) {
@@ -159,18 +192,21 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
   for (size_t c = 0; c < Q; c++)
     for (size_t j = 0; j < Q; j++)
       if (j != c) zfirst_inv_[c * Q + j] = gl::inv(gl::sub(gl::pow(gl::mul(s_c[c], s.s_inv[j]), n), 1));
-  s.o_fri = 8 + 4 * W + 4 * (uint32_t)Q + 4 * PW;
+  s.o_aux = 8 + 4 * W + 4 * (uint32_t)Q + 4 * PW;
+  s.o_fri = s.o_aux + (AW ? 4 + 8 * AW : 0);
   s.hdr_words = s.o_fri + 4 * k;
   s.o_points = s.hdr_words;
   s.o_apow = s.o_points + 2 * (2 + (uint32_t)Q);
-  s.o_betas = s.o_apow + 2 * (2 * W + 2 * (uint32_t)Q + 2 * PW);
+  s.o_betas = s.o_apow + 2 * (2 * W + 2 * (uint32_t)Q + 2 * PW + 4 * AW);
   s.o_idx = s.o_betas + 2 * k;
-  s.hdr_stride = s.o_idx + (num_queries + 1) / 2;
+  s.o_chal = s.o_idx + (num_queries + 1) / 2;
+  s.hdr_stride = s.o_chal + 2 * s.NC;
   s.sz_a = 0;
   for (int r = 0; r < k; r++) s.sz_a += 2 + 4 * (L - r - 1);
-  s.sz_b = W + 4 * L + 2 * (uint32_t)Q + 4 * L + (PW ? PW + 4 * L : 0);
+  s.sz_b = W + 4 * L + 2 * (uint32_t)Q + 4 * L + (PW ? PW + 4 * L : 0) + (AW ? 2 * AW + 4 * L : 0);
   if ((size_t)s.hdr_words + (size_t)num_queries * (s.sz_a + s.sz_b) + 3 !=
-      cfg_.num_inputs() + p3_preprocessed_words((int)PW, k, B, num_queries))   // the public values follow
+      cfg_.num_inputs() + p3_preprocessed_words((int)PW, k, B, num_queries) +
+          p3_aux_words((int)AW, k, B, num_queries))   // the public values follow
     throw std::logic_error("p3 device prover: flattened size mismatch");
   budget_bytes_ = P3_SCRATCH_BUDGET_BYTES;
 }
@@ -191,7 +227,7 @@ struct P3Carve {
   size_t words;
 };
 static P3Carve carve_scratch(const P3Shape& s, size_t G, u64* base) {
-  const size_t n = (size_t)1 << s.k, N2 = (size_t)1 << s.L, W = s.W, Q2 = 2 * (size_t)s.Q;
+  const size_t n = (size_t)1 << s.k, N2 = (size_t)1 << s.L, W = s.W, Q2 = 2 * (size_t)s.Q, A2 = 2 * (size_t)s.AW;
   P3Carve c{};
   auto take = [&](size_t words) {
     u64* r = base ? base + c.words : nullptr;
@@ -202,7 +238,7 @@ static P3Carve carve_scratch(const P3Shape& s, size_t G, u64* base) {
   c.b.state = reinterpret_cast<P3State*>(take(G * (sizeof(P3State) / 8)));
   c.b.hdr = take(G * s.hdr_stride);
   c.b.tvals = take(G * W * n);
-  c.b.tmp = take(G * std::max(W, Q2) * n);
+  c.b.tmp = take(G * std::max(std::max(W, Q2), A2) * n);   // also the terms the auxiliary scan works on
   c.b.tcoef = take(G * W * n);
   c.b.qv = take(G * Q2 * n);
   c.b.qcoef = take(G * Q2 * n);
@@ -212,6 +248,13 @@ static P3Carve carve_scratch(const P3Shape& s, size_t G, u64* base) {
   c.b.qtree = take(G * 8 * N2);
   c.b.layers = take(G * 4 * N2);
   c.b.ftrees = take(G * 8 * N2);
+  if (A2) {   // the challenge phase of a handle with auxiliary columns; nothing for any other handle
+    c.b.avals = take(G * A2 * n);
+    c.b.acoef = take(G * A2 * n);
+    c.b.alde = take(G * A2 * N2);
+    c.b.atree = take(G * 8 * N2);
+    c.b.atot = take(G * A2 * ((n + P3_AUX_SCAN_BLOCK - 1) / P3_AUX_SCAN_BLOCK));
+  }
   return c;
 }
 size_t P3ProverDev::scratch_words_per_proof() const { return carve_scratch(shape_, 1, nullptr).words; }
@@ -223,7 +266,9 @@ size_t P3ProverDev::group_size(size_t n_proofs) const {
 
 size_t P3ProverDev::preprocessed_table_words() const {
   const size_t n = (size_t)1 << shape_.k, N2 = (size_t)1 << shape_.L;
-  return shape_.PW ? shape_.PW * n + shape_.PW * N2 + 8 * N2 : 0;
+  // a handle with auxiliary columns keeps the columns' values on the trace domain as well (PW n words, the last of the
+  // tables): its term kernel reads them
+  return shape_.PW ? shape_.PW * n + shape_.PW * N2 + 8 * N2 + (shape_.AW ? shape_.PW * n : 0) : 0;
 }
 
 // The preprocessed columns' tables, by the launches the trace takes with a group of one: rows -> columns -> coefficients ->
@@ -233,19 +278,20 @@ void P3ProverDev::ensure_preprocessed(bool keep, hipStream_t st) {
   if (!shape_.PW || impl_->prep.words || (!keep && prep_root_known_)) return;
   const P3Shape& s = shape_;
   const size_t n = (size_t)1 << s.k, N2 = (size_t)1 << s.L, PW = s.PW;
-  DevMem tables(preprocessed_table_words()), rows(PW * n), vals(PW * n), tmp(PW * n);
+  DevMem tables(preprocessed_table_words()), rows(PW * n), vals_tmp(s.AW ? 0 : PW * n), tmp(PW * n);
   if (!impl_->prep_root.words) impl_->prep_root = DevMem(4);
   u64 *coef = tables.p, *lde = coef + PW * n, *tree = lde + PW * N2;
+  u64* vals = s.AW ? tree + 8 * N2 : vals_tmp.p;   // kept behind the tree for the term kernel, or a temporary
   if (impl_->recorded) P25_HIP(hipStreamWaitEvent(st, impl_->done, 0));
   P25_HIP(hipMemcpyAsync(rows.p, prep_values_.data(), PW * n * 8, hipMemcpyHostToDevice, st));
   P3Shape ts = s;    // the transpose reads k, W and G alone
   ts.W = (uint32_t)PW;
   ts.G = 1;
   P3Bufs tb{};
-  tb.tvals = vals.p;
+  tb.tvals = vals;
   p3_launch_transpose(rows.p, PW * n, ts, tb, st);
   NttTables& nt = impl_->tables;
-  ntt_inverse(nt, vals.p, n, false, tmp.p, n, coef, n, (int)s.k, (int)PW, 1, st);
+  ntt_inverse(nt, vals, n, false, tmp.p, n, coef, n, (int)s.k, (int)PW, 1, st);
   if (s.B <= 3) {
     ntt_lde_bitrev(nt, coef, n, lde, N2, (int)s.k, (int)s.B, (int)PW, gl::GENERATOR, st);
   } else {   // 16 cosets as two interleaved sets of 8, as run_group's lde
@@ -271,6 +317,14 @@ void P3ProverDev::preprocessed_commit(u64 out[4]) {
   for (int i = 0; i < 4; i++) out[i] = prep_root_[i];
 }
 
+double P3ProverDev::aux_stage_ms() {
+  if (!shape_.AW || !impl_ || !impl_->aux_t1.e) throw std::invalid_argument("p25_p3_prover_aux_stage_ms: no proof with auxiliary columns has been made");
+  P25_HIP(hipEventSynchronize(impl_->aux_t1));
+  float ms = 0;
+  P25_HIP(hipEventElapsedTime(&ms, impl_->aux_t0, impl_->aux_t1));
+  return ms;
+}
+
 void P3ProverDev::sync() {
   if (!impl_ || !impl_->recorded) return;
   P25_HIP(hipEventSynchronize(impl_->done));
@@ -281,6 +335,10 @@ void P3ProverDev::ensure_impl() {
     std::unique_ptr<P3ProverImpl> im(new P3ProverImpl());
     im->prog = DevMem((prog_.instr.size() * sizeof(P3Instr) + 7) / 8);
     im->consts = DevMem(prog_.consts.size());
+    if (!prog_.aux_instr.empty()) {
+      im->aux_prog = DevMem((prog_.aux_instr.size() * sizeof(P3Instr) + 7) / 8);
+      P25_HIP(hipMemcpy(im->aux_prog.p, prog_.aux_instr.data(), prog_.aux_instr.size() * sizeof(P3Instr), hipMemcpyHostToDevice));
+    }
     im->zfirst = DevMem(zfirst_inv_.size());
     P25_HIP(hipMemcpy(im->prog.p, prog_.instr.data(), prog_.instr.size() * sizeof(P3Instr), hipMemcpyHostToDevice));
     P25_HIP(hipMemcpy(im->consts.p, prog_.consts.data(), prog_.consts.size() * 8, hipMemcpyHostToDevice));
@@ -333,7 +391,9 @@ void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, const u64*
     b.pcoef = impl_->prep.p;
     b.plde = b.pcoef + (size_t)s.PW * n;
     b.ptree = b.plde + (size_t)s.PW * N2;
+    if (s.AW) b.pvals = b.ptree + 8 * N2;
   }
+  b.aux_prog = reinterpret_cast<const P3Instr*>(impl_->aux_prog.p);
 
   // the LDE on shift * <w_{n 2^B}> in bit-reversed order; 16 cosets as two interleaved sets of 8 (coset 2 c + e of the
   // first kind is coset c of the set with shift * w^e, and lands in half e of the bit-reversed output)
@@ -351,7 +411,19 @@ void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, const u64*
   ntt_inverse(tb, b.tvals, n, false, b.tmp, n, b.tcoef, n, k, (int)(G * W), 1, st);
   lde(b.tcoef, b.tlde, (int)(G * W), gl::GENERATOR);
   p3_launch_commit_cols(b.tlde, W * N2, 2 * N2, N2, (uint32_t)W, N2, b.ttree, 8 * N2, G, st);
-  p3_launch_chain(s, b, P3_CH_TRACE, 0, st);                       // observe the root, sample alpha
+  p3_launch_chain(s, b, P3_CH_TRACE, 0, st);                       // observe the root, sample alpha -- or the challenges
+  if (s.AW) {   // the challenge phase: terms, running sums, then the trace's commit on 2 AW columns per proof
+    const int A2 = 2 * (int)s.AW;
+    impl_->aux_t0.ensure();
+    impl_->aux_t1.ensure();
+    P25_HIP(hipEventRecord(impl_->aux_t0, st));
+    p3_launch_aux_columns(s, b, st);
+    ntt_inverse(tb, b.avals, n, false, b.tmp, n, b.acoef, n, k, (int)G * A2, 1, st);
+    lde(b.acoef, b.alde, (int)G * A2, gl::GENERATOR);
+    p3_launch_commit_cols(b.alde, (size_t)A2 * N2, 2 * N2, N2, (uint32_t)A2, N2, b.atree, 8 * N2, G, st);
+    p3_launch_chain(s, b, P3_CH_AUX, 0, st);                       // observe the auxiliary root, sample alpha
+    P25_HIP(hipEventRecord(impl_->aux_t1, st));
+  }
   // quotient on 7 H_{n 2^lqd}, split into chunks; chunk c: iNTT on H_n, LDE with shift 7 / s_c   (:231-290)
   p3_launch_quotient(s, b, st);
   ntt_inverse(tb, b.qv, n, true, b.tmp, n, b.qcoef, n, k, (int)(G * Q2), 1, st);

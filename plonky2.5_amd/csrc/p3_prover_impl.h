@@ -9,6 +9,8 @@ namespace p25 {
 struct P3ProverImpl {
   NttTables tables;
   DevMem prog, consts, zfirst, scratch;
+  DevEvent aux_t0, aux_t1;   // timing events around the challenge phase of the last group proved (P3ProverDev::aux_stage_ms)
+  DevMem aux_prog;   // the auxiliary columns' terms' program (P3AirDevice::aux_instr); empty without such columns
   DevMem prep;       // the preprocessed columns' tables: coefficients | LDE | tree (p3_prover_dev.hip); empty until a proving call
   DevMem prep_root;  // the 4 words of the preprocessed commitment: all the verifying side keeps of the columns
   DevMem vscratch;   // the verifier's: challenge blocks and folded values (p3_verify_dev.hip)

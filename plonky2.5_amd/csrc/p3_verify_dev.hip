@@ -8,7 +8,9 @@
 
 namespace p25 {
 
-size_t P3ProverDev::verify_scratch_words_per_proof() const { return p3v_scratch_words(shape_.k, shape_.num_queries); }
+size_t P3ProverDev::verify_scratch_words_per_proof() const {
+  return p3v_scratch_words(shape_.k, shape_.num_queries, shape_.AW ? shape_.NC : 0);   // the challenge block grows by 2 NC
+}
 size_t P3ProverDev::verify_chunk(size_t n_proofs) const {
   const size_t c = std::min(budget_bytes_, P3_VERIFY_SCRATCH_BYTES) / (verify_scratch_words_per_proof() * 8);
   return std::min(std::max<size_t>(1, c), n_proofs);
@@ -33,7 +35,10 @@ P3VerifyArgs P3ProverDev::verify_args() const {
   a.o_public = a.num_inputs - s.n_public;
   a.per_coef = s.per_coef;
   a.PW = s.PW;
-  a.nb = s.PW ? 3 : 2;
+  a.NC = s.NC;
+  a.AW = s.AW;
+  a.o_aux = s.o_aux;
+  a.nb = 2 + (s.PW ? 1 : 0) + (s.AW ? 1 : 0);
   a.prep_root = prep_root_;   // the host's copy, known once a compute call has made it; verify_dev puts the device's in its place
   a.o_open = 8;
   a.o_roots = s.o_fri;
@@ -44,7 +49,8 @@ P3VerifyArgs P3ProverDev::verify_args() const {
   a.o_qo = a.o_pow + 1;
   a.sz_b = s.sz_b;
   a.c_idx = P3VC_BETAS + 2 * s.k;
-  a.chal_stride = a.c_idx + s.num_queries;
+  a.c_chal = a.c_idx + s.num_queries;
+  a.chal_stride = a.c_chal + (s.AW ? 2 * s.NC : 0);
   if ((size_t)a.o_qo + (size_t)s.num_queries * s.sz_b != a.o_public || a.o_roots + 4 * s.k != s.hdr_words ||
       p3v_round_off(a, s.k) != s.sz_a || (size_t)a.chal_stride + 2 * (size_t)s.num_queries * s.k != verify_scratch_words_per_proof())
     throw std::logic_error("p3 verifier: layout out of step with the proof's");

@@ -19,8 +19,8 @@ namespace p25 {
 // statement order of verifier.rs (atomicMin: never the last writer); the verdict lane turns it into the code.
 //   0                            a word >= p
 //   1                            proof of work (:376)
-//   2 + nb q + b                 input batch b (0 trace, 1 quotient, 2 preprocessed) of query q (:288-294; all queries before
-//                                any FRI step); nb = 2, or 3 for a handle with preprocessed columns
+//   2 + nb q + b                 input batch b (trace, quotient, preprocessed if any, auxiliary if any) of query q (:288-294;
+//                                all queries before any FRI step); nb = 2 + (PW > 0) + (AW > 0)
 //   F + q (k + 2)                a zero denominator in query q's reduced opening, F = 2 + nb num_queries: reported as the
 //                                query's final-polynomial failure, ahead of its FRI rounds, whose leaves it spoils
 //   F + q (k + 2) + 1 + r        FRI round r of query q (:471-481)
@@ -31,7 +31,8 @@ enum : uint32_t {  // include/p25.h: P25_P3_REJECT_*
   P3V_REJECT_MALFORMED = 30, P3V_REJECT_POW = 31, P3V_REJECT_INPUT_MERKLE = 32, P3V_REJECT_FRI_MERKLE = 33,
   P3V_REJECT_FINAL_POLY = 34, P3V_REJECT_CONSTRAINTS = 35
 };
-// the per-proof challenge block (words); the query indices follow the betas, one word each
+// the per-proof challenge block (words); the query indices follow the betas, one word each, and for a handle with
+// auxiliary columns its 2 NC challenge words follow those (c_chal)
 enum : uint32_t { P3VC_ALPHA = 0, P3VC_ZETA = 2, P3VC_FRI_ALPHA = 4, P3VC_POW = 6, P3VC_BETAS = 8 };
 
 struct P3VerifyArgs {
@@ -58,6 +59,9 @@ struct P3VerifyArgs {
   // handle's commitment, which the transcript observes behind the trace root and the third batch's paths must reach
   uint32_t PW, nb;
   const u64* prep_root;   // 4 words (the handle's: device memory on the device); unread when PW = 0
+  // the auxiliary columns: NC challenges sampled behind the public values (to chal + c_chal), AW columns whose root --
+  // the PROOF's words at o_aux -- is observed before alpha, whose openings follow it and whose batch is every query's last
+  uint32_t NC, AW, o_aux, c_chal;
   u64 w_L, w_L_inv;    // primitive root of the LDE domain and its inverse
   u64 w_n, g_inv;      // generator of the trace domain and its inverse
   u64 neg2_inv;        // 1 / -2
@@ -69,7 +73,9 @@ GL_HD uint32_t p3v_key_constraints(const P3VerifyArgs& a) { return p3v_key_fri(a
 // round r of a query's commit-phase openings: sibling_value (2 words), then L - r - 1 digests
 GL_HD uint32_t p3v_round_off(const P3VerifyArgs& a, uint32_t r) { return 2 * r + 4 * (r * (a.L - 1) - r * (r - 1) / 2); }
 // words of verifier scratch per proof
-GL_HD size_t p3v_scratch_words(uint32_t k, uint32_t num_queries) { return 8 + 2 * (size_t)k + num_queries + 2 * (size_t)num_queries * k; }
+GL_HD size_t p3v_scratch_words(uint32_t k, uint32_t num_queries, uint32_t n_challenges = 0) {
+  return 8 + 2 * (size_t)k + num_queries + 2 * (size_t)n_challenges + 2 * (size_t)num_queries * k;
+}
 
 namespace p3vlane {
 
@@ -117,6 +123,10 @@ GL_HD uint32_t transcript_lane(const P3VerifyArgs& a, uint32_t p) {
   if (a.PW)
     for (int i = 0; i < 4; i++) ch.observe(a.prep_root[i]);
   for (uint32_t i = 0; i < a.n_public; i++) ch.observe(proof[a.o_public + i]);
+  if (a.AW) {
+    draw(a.c_chal, 2 * a.NC);
+    for (int i = 0; i < 4; i++) ch.observe(proof[a.o_aux + i]);
+  }
   draw(P3VC_ALPHA, 2);
   for (int i = 0; i < 4; i++) ch.observe(proof[4 + i]);
   draw(P3VC_ZETA, 2);
@@ -145,12 +155,17 @@ GL_HD bool identity_lane(const P3VerifyArgs& a, uint32_t p) {
   const E2 sel[4] = {gl::e2(0), gl::mul(z_h, gl::inv(gl::sub(zeta, gl::e2(1)))), gl::mul(z_h, gl::inv(is_trans)), is_trans};
   const uint32_t W = a.W;
   const u64* popen = open + 4 * W + 4 * a.Q;   // the preprocessed openings, behind the chunks'
+  const u64* aopen = proof + a.o_aux + 4;      // the auxiliary openings, behind the auxiliary root
   auto load = [&](int which, uint32_t c) -> E2 {
+    if (which & 4) {   // column c at the point: o[2 c] + X o[2 c + 1], as the chunks are recomposed
+      const u64* o = aopen + 2 * (((which & 1) ? 2 * a.AW : 0) + 2 * c);
+      return gl::add(ld(o), gl::mul(ld(o + 2), E2{0, 1}));
+    }
     return (which & 2) ? ld(popen + 2 * (((which & 1) ? a.PW : 0) + c)) : ld(open + 2 * (((which & 1) ? W : 0) + c));
   };
   const u64* pcoef = a.consts + a.per_coef;
   auto per = [&](uint32_t i) -> E2 { return p3_periodic_at(pcoef + p3_per_offset(i), p3_per_log_period(i), a.k, zeta); };
-  const E2 acc = run_air<ExtF>(a.prog, a.n_instr, a.consts, proof + a.o_public, load, per, sel, alpha);
+  const E2 acc = run_air<ExtF>(a.prog, a.n_instr, a.consts, proof + a.o_public, chal + a.c_chal, load, per, sel, alpha);
   const E2 lhs = gl::mul(acc, gl::inv(z_h));
   // zps_c = prod_{j != c} Z_{D_j}(zeta) / Z_{D_j}(s_c),  Z_{D_j}(x) = (x / s_j)^n - 1
   E2 at_zeta[8];
@@ -212,6 +227,16 @@ GL_HD uint32_t fold_lane(const P3VerifyArgs& a, uint32_t p, uint32_t q) {
         ap = gl::mul(ap, fri_alpha);
       }
   }
+  if (a.AW) {   // the last batch: the auxiliary row's 2 AW words at zeta, then at zeta w_n; the powers go on
+    const u64* row_a = qo + a.sz_b - 4 * L - 2 * a.AW;
+    const u64* aopen = proof + a.o_aux + 4;
+    for (uint32_t pt = 0; pt < 2; pt++)
+      for (uint32_t c = 0; c < 2 * a.AW; c++) {
+        const E2 diff = gl::sub(gl::e2(row_a[c]), ld(aopen + 2 * (pt * 2 * a.AW + c)));
+        ro = gl::add(ro, gl::mul(ap, gl::mul(diff, pt ? inv_zn : inv_z)));
+        ap = gl::mul(ap, fri_alpha);
+      }
+  }
   // every matrix has the height of the LDE domain: the reduced opening enters before round 0 and nothing later
   E2 f = ro;
   const u64* qp = proof + a.o_qp + (size_t)q * a.sz_a;
@@ -237,7 +262,8 @@ GL_HD uint32_t fold_lane(const P3VerifyArgs& a, uint32_t p, uint32_t q) {
 }
 
 // Tree `tree` of query q of proof p: 0 the trace batch, 1 the quotient batch (all chunk matrices have one height: their rows
-// are hashed as one), with preprocessed columns (a.nb = 3) 2 their batch, checked against the handle's root; a.nb + r the
+// are hashed as one), with preprocessed columns 2 their batch, checked against the handle's root, with auxiliary columns
+// a.nb - 1 theirs, checked against the proof's aux_commit; a.nb + r the
 // commit of FRI round r, whose leaf is the pair (own value, sibling value) in index order.
 // hash_iter_slices (commit.rs:23-46) of the leaf, then a compress per sibling; leaf chunks and path steps share ONE
 // permutation call site.
@@ -250,13 +276,15 @@ GL_HD uint32_t merkle_lane(const P3VerifyArgs& a, uint32_t tree, uint32_t p, uin
   u64 s[12];
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = 0;
-  const bool prep = a.nb == 3 && tree == 2;
+  const bool prep = a.PW && tree == 2;
+  const bool aux = a.AW && tree == a.nb - 1;   // the last batch
   if (tree < a.nb) {
-    width = prep ? a.PW : tree ? 2 * a.Q : a.W;
-    leaf = qo + (tree ? a.W + 4 * a.L : 0) + (prep ? 2 * a.Q + 4 * a.L : 0);
+    width = aux ? 2 * a.AW : prep ? a.PW : tree ? 2 * a.Q : a.W;
+    leaf = aux ? qo + a.sz_b - 4 * a.L - 2 * a.AW : qo + (tree ? a.W + 4 * a.L : 0) + (prep ? 2 * a.Q + 4 * a.L : 0);
     sibs = leaf + width;
     depth = a.L;
-    root = prep ? a.prep_root : proof + 4 * tree;   // the preprocessed batch's root is the handle's, not the proof's
+    // the preprocessed batch's root is the handle's, not the proof's; the auxiliary batch's is the proof's own aux_commit
+    root = aux ? proof + a.o_aux : prep ? a.prep_root : proof + 4 * tree;
     key = P3VKEY_INPUT + a.nb * q + tree;
   } else {
     const uint32_t r = tree - a.nb;

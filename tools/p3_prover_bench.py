@@ -17,6 +17,13 @@ machine next0 = local0 + sel c with sel, c two preprocessed columns, against the
 the handle's tables (first p25_p3_prover_preprocessed_commit on a fresh handle, after another handle has loaded the code
 objects; it includes that handle's own constant tables) and the device time per proof with and without columns; the rows
 with columns are asserted equal to the host prover's.
+
+--aux-lookup LOG_N adds the cost of challenge-phase auxiliary columns (include/p25.h, AUXILIARY COLUMNS) at one shape: the
+LogUp range check of a trace column f into the preprocessed table 0..n-1 with a multiplicity column m (one challenge, one
+auxiliary column) beside the plain constraint c = f m, against the same AIR with the auxiliary parts removed (c = f m
+alone); 2^LOG_N rows, the largest batch of --batches.  Reported under "aux" and written to profiles/p3_aux.json as well: ms
+per proof for both, and the share of the call that the term + scan + auxiliary-commit stage takes (HIP events around it,
+P3Prover.aux_stage_ms); the last row with auxiliary columns is asserted equal to the host prover's.
 """
 import argparse
 import json
@@ -109,6 +116,65 @@ def bench_preprocessed(p25, torch, dev, args):
     return out
 
 
+def lookup(p25, log_n, with_aux):
+    """-> (air, trace[n][3]) of the --aux-lookup shape."""
+    n = 1 << log_n
+    f = np.random.default_rng(777).integers(0, n, n, dtype=np.uint64)
+    m = np.bincount(f.astype(np.int64), minlength=n).astype(np.uint64)
+    trace = np.ascontiguousarray(np.stack([f, m, f * m % np.uint64(P)], axis=1))   # f m < 2^28: no wrap before the reduction
+    table = np.arange(n, dtype=np.uint64).reshape(-1, 1)
+    air = p25.Air(3, preprocessed=table, aux=1 if with_aux else 0)
+    lf, lm, t = air.local(0), air.local(1), air.prep_local(0)
+    air.assert_zero(air.sub(air.local(2), air.mul(lf, lm)))
+    if with_aux:
+        g = air.challenge(0)
+        gf, gt = air.sub(g, lf), air.sub(g, t)
+        num, den = air.sub(air.mul(lm, gf), gt), air.mul(gt, gf)
+        j = air.aux_column(num, den)
+        air.when_first_row(air.aux_local(j))
+        air.assert_zero(air.sub(air.mul(air.sub(air.aux_next(j), air.aux_local(j)), den), num))
+    else:
+        air.when_first_row(air.sub(t, t))   # keeps the preprocessed column read, as the auxiliary form reads it
+    return air, trace
+
+
+def bench_aux(p25, torch, dev, args):
+    log_n, b = args.aux_lookup, max(args.batches)
+    out = {"log_n": log_n, "batch": b, "queries": args.queries, "pow_bits": args.pow_bits, "device": torch.cuda.get_device_name(0)}
+    for with_aux in (True, False):
+        air, trace = lookup(p25, log_n, with_aux)
+        pr = p25.P3Prover(air, log_n, 1, args.queries, args.pow_bits)
+        ni = pr.num_inputs
+        d_traces = torch.from_numpy(trace.view(np.int64).copy()).to(dev).reshape(1, -1).repeat(b, 1).contiguous()
+        d_inputs = torch.zeros((b, ni), dtype=torch.int64, device=dev)
+        d_status = torch.zeros(b, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+
+        def call():
+            pr.prove_dev(d_traces.data_ptr(), trace.size, b, 0, d_inputs.data_ptr(), ni, d_status.data_ptr())
+            pr.sync()
+
+        call()   # warm-up: code objects, scratch, the handle's tables
+        times, stage = [], []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call()
+            times.append(time.perf_counter() - t0)
+            if with_aux:
+                stage.append(pr.aux_stage_ms() / 1e3)
+        assert d_status.cpu().numpy().tolist() == [0] * b, "device prover reported a failure"
+        key = "with_aux" if with_aux else "without_aux"
+        out[key] = {"num_inputs": ni, "gpu_call_s": [round(t, 6) for t in times], "gpu_ms_per_proof": 1e3 * float(np.median(times)) / b}
+        if with_aux:
+            row, _cfg = p25.p3_prove_air(air, trace, num_queries=args.queries, pow_bits=args.pow_bits, threads=args.threads)
+            assert np.array_equal(d_inputs.cpu().numpy().view(np.uint64)[b - 1], row), "proof differs from the host prover's"
+            out[key]["aux_stage_s"] = [round(t, 6) for t in stage]
+            out[key]["aux_stage_share"] = float(np.median(stage)) / float(np.median(times))
+        pr.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-n", type=int, nargs="+", default=[12, 16, 20])
@@ -120,6 +186,9 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--prep-machine", type=int, default=0, metavar="LOG_N",
                     help="also measure an AIR with two preprocessed columns at 2^LOG_N rows (0 = off)")
+    ap.add_argument("--aux-lookup", type=int, default=0, metavar="LOG_N",
+                    help="also measure the LogUp range check with one auxiliary column at 2^LOG_N rows (0 = off)")
+    ap.add_argument("--aux-out", default=os.path.join(ROOT, "profiles", "p3_aux.json"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "p3_prover_bench.json"))
     args = ap.parse_args()
 
@@ -181,6 +250,12 @@ def main():
         pr.close()
     if args.prep_machine:
         result["preprocessed"] = bench_preprocessed(p25, torch, dev, args)
+    if args.aux_lookup:
+        result["aux"] = bench_aux(p25, torch, dev, args)
+        os.makedirs(os.path.dirname(args.aux_out), exist_ok=True)
+        with open(args.aux_out, "w") as f:
+            json.dump(dict(result["aux"], tool="tools/p3_prover_bench.py --aux-lookup"), f, indent=1)
+            f.write("\n")
     # the acceptance for speed: per proof, the device form beats the host form of the same run at the largest size
     top = max(args.log_n)
     result["acceptance"] = {"log_n": top, "gpu_faster_than_host": all(sh["host_over_gpu"] > 1.0 for sh in result["shapes"]

@@ -64,6 +64,17 @@ class OracleCircuit:
         names = ["witness", "wires_commit", "zs", "zs_commit", "quotient", "quotient_commit", "openings", "fri", "total"]
         return proof, st, dict(zip(names, [float(x) for x in tm])), msg.value.decode()
 
+    def prove_forged(self, inputs, seed, fault):
+        """The forging prover (ref_prover.h RFault): fault = (kind, a, b), tampered with at one point of the proof, the
+        rest of the proof honest on the tampered data.  (0, 0, 0) gives prove()'s words.  Returns (proof, status, msg);
+        status 1 = the circuit has no place for that fault (the proof is then all zeros)."""
+        kind, a, b = fault
+        inp = np.ascontiguousarray(inputs, dtype=np.uint64)
+        proof = np.zeros(self.proof_words, dtype=np.uint64)
+        msg = C.create_string_buffer(512)
+        st = self.lib.p25o_prove_forged(self.h, _p(inp), seed, int(kind), int(a), int(b), _p(proof), msg, 512)
+        return proof, st, msg.value.decode()
+
     def prove_filler(self, inputs, filler):
         """Prove with explicit RandomValueGenerator values (what a real upstream run drew from the OS RNG)."""
         inp = np.ascontiguousarray(inputs, dtype=np.uint64)
@@ -156,6 +167,7 @@ class Oracle:
         L.p25o_proof_words.argtypes = [vp]
         L.p25o_proof_words.restype = sz
         L.p25o_prove.argtypes = [vp, vp, u64, vp, vp, C.c_char_p, sz]
+        L.p25o_prove_forged.argtypes = [vp, vp, u64, C.c_int, u64, u64, vp, C.c_char_p, sz]
         L.p25o_verify.argtypes = [vp, vp, vp, vp, C.c_char_p, sz]
         L.p25o_prove_many.argtypes = [vp, vp, vp, sz, C.c_int, vp, vp, vp]
         L.p25o_prove_many_grouped.argtypes = [vp, vp, vp, sz, C.c_int, C.c_int, vp, vp, vp]

@@ -203,6 +203,25 @@ int p25o_prove(void* h, const u64* inputs, u64 seed, u64* proof_out, double* tim
   }
   return 0;
 }
+// The forging prover (ref_prover.h RFault): kind 0 gives p25o_prove's words; a fault the circuit has no place for is
+// answered with status 1 and proof_out left alone.
+int p25o_prove_forged(void* h, const u64* inputs, u64 seed, int kind, u64 a, u64 b, u64* proof_out, char* msg, size_t msglen) {
+  auto* oc = (OracleCircuit*)h;
+  p25o_precompute(h);
+  RProof pr;
+  std::string m;
+  const RFault fault{kind, a, b};
+  int st = ref_prove(oc->c, *oc->pre, inputs, seed, pr, nullptr, &m, nullptr, &fault);
+  put_msg(msg, msglen, m);
+  if (st) return st;
+  std::vector<u64> flat = ref_proof_flatten(oc->c, pr);
+  if (flat.size() != ref_proof_words(oc->c)) {
+    put_msg(msg, msglen, "internal: proof size mismatch");
+    return 7;
+  }
+  memcpy(proof_out, flat.data(), flat.size() * 8);
+  return 0;
+}
 // One row's constraints over F_p^2 (upstream Gate::eval_unfiltered; the verifier's evaluator): wires[num_wires][2],
 // consts[2][2], pih[4] -> out[n][2]; returns n.  With base = 1 the wires' second components are ignored and the
 // base-field evaluator runs (out[n][2] with zero second components): the two must agree on base inputs.

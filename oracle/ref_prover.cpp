@@ -517,8 +517,24 @@ std::vector<std::vector<u64>> ref_quotient_chunks(const RCircuit& c, const RPoly
 // transcript, fills fri_caps, final_poly, pow_witness and the query rounds of `out`.  `oracles` (the four
 // initial polynomial batches) may be null: then only the FRI layers are opened.
 int ref_fri_prove(const RFriParams& fp, const std::vector<RE2>& final_poly, RChallenger& ch,
-                  const RPolyBatch* const* oracles, RProof& out, std::vector<size_t>* indices_out, std::string* msg) {
+                  const RPolyBatch* const* oracles, RProof& out, std::vector<size_t>* indices_out, std::string* msg,
+                  const RFault* fault) {
   const size_t big = final_poly.size() << fp.rate_bits;
+  // the forging prover's FRI faults (ref_prover.h): refused where this shape has no place for them
+  const int fkind = fault ? fault->kind : R_FAULT_NONE;
+  auto refuse = [&](const char* m) {
+    if (msg) *msg = m;
+    return 1;
+  };
+  if ((fkind == R_FAULT_FRI_LAYER || fkind == R_FAULT_FRI_FOLD) && fault->a >= fp.arity_bits.size())
+    return refuse("fault: the circuit has no such FRI layer");
+  if (fkind == R_FAULT_FRI_LAYER && fault->b > 1) return refuse("fault: FRI layer mask is 0 (all) or 1 (first half)");
+  {
+    size_t flen = final_poly.size();
+    for (int a : fp.arity_bits) flen >>= a;
+    if (fkind == R_FAULT_FINAL_POLY && (fault->a >= flen || fault->b > 1))
+      return refuse("fault: no such final polynomial coefficient or component");
+  }
   // commit phase (App. A.8)
   std::vector<RE2> coeffs(final_poly);
   coeffs.resize(big, re(0));
@@ -534,7 +550,13 @@ int ref_fri_prove(const RFriParams& fp, const std::vector<RE2>& final_poly, RCha
     unsigned lg = 0;
     while (((size_t)1 << lg) < len) lg++;
     std::vector<RE2> br(len);
-    for (size_t i = 0; i < len; i++) br[rbits(i, lg)] = values[i];
+    const size_t layer = fri_trees.size();
+    const bool bump_layer = fkind == R_FAULT_FRI_LAYER && fault->a == layer;
+    for (size_t i = 0; i < len; i++) {
+      RE2 v = values[i];
+      if (bump_layer && (fault->b == 0 || i < len / 2)) v = re_add(v, re(1));   // committed, never folded
+      br[rbits(i, lg)] = v;
+    }
     std::vector<std::vector<u64>> leaves(len / arity);
     for (size_t l = 0; l < leaves.size(); l++)
       for (size_t k = 0; k < arity; k++) {
@@ -548,6 +570,7 @@ int ref_fri_prove(const RFriParams& fp, const std::vector<RE2>& final_poly, RCha
     fri_leaves.push_back(leaves);
     RE2 beta = ch.ext_challenge();
     fri_betas.push_back(beta);
+    if (fkind == R_FAULT_FRI_FOLD && fault->a == layer) beta = re_add(beta, re(1));   // the transcript keeps beta
     std::vector<RE2> folded(coeffs.size() / arity);
     for (size_t i = 0; i < folded.size(); i++) {
       RE2 s = re(0);
@@ -560,6 +583,10 @@ int ref_fri_prove(const RFriParams& fp, const std::vector<RE2>& final_poly, RCha
     ref_coset_fft_ext(values, shift);
   }
   coeffs.resize(coeffs.size() >> fp.rate_bits);
+  if (fkind == R_FAULT_FINAL_POLY) {
+    RE2& e = coeffs[fault->a];
+    e = re_add(e, fault->b ? RE2{0, 1} : re(1));
+  }
   out.final_poly = coeffs;
   for (auto& e : coeffs) ch.observe_ext(e);
 
@@ -608,7 +635,25 @@ int ref_fri_prove(const RFriParams& fp, const std::vector<RE2>& final_poly, RCha
 
 // ---------------------------------------------------------------- prover (App. A.0-A.8)
 int ref_prove(const RCircuit& c, const RPrecomputed& pre, const u64* inputs, u64 seed, RProof& out, RTimings* tm,
-              std::string* msg, const u64* filler) {
+              std::string* msg, const u64* filler, const RFault* fault) {
+  const int fkind = fault ? fault->kind : R_FAULT_NONE;
+  auto refuse = [&](const char* m) {
+    if (msg) *msg = m;
+    return 1;
+  };
+  if (fkind < R_FAULT_NONE || fkind > R_FAULT_FINAL_POLY) return refuse("fault: unknown kind");
+  if ((fkind == R_FAULT_FRI_LAYER || fkind == R_FAULT_FRI_FOLD) && fault->a >= c.arity_bits.size())
+    return refuse("fault: the circuit has no such FRI layer");   // the answers given where the faults apply, ahead of the work
+  if (fkind == R_FAULT_FINAL_POLY && (fault->a >= (u64)final_poly_len(c) || fault->b > 1))
+    return refuse("fault: no such final polynomial coefficient or component");
+  if (fkind == R_FAULT_OPENING) {
+    const u64 Q = c.quotient_degree_factor, nq = (u64)c.num_challenges * Q;
+    const u64 q0 = (u64)c.num_constants_total() + c.num_routed + c.num_wires + (u64)c.num_challenges * (2 + c.num_partial_products);
+    if (fault->a >= q0 + nq) return refuse("fault: opening index past the end of the openings");
+    if (fault->a >= q0 && (fault->a - q0) % Q == 0) return refuse("fault: this quotient opening is the one the forgery solves for");
+  }
+  if (fkind == R_FAULT_WIRE && (fault->a >= (u64)c.num_wires || fault->b >= (u64)c.n()))
+    return refuse("fault: no such wire column or row");
   RTimings T;
   double t_start = now_s(), t0 = t_start;
   const size_t n = c.n();
@@ -626,6 +671,10 @@ int ref_prove(const RCircuit& c, const RPrecomputed& pre, const u64* inputs, u64
   const RHash pi_hash = ref_hash_no_pad(wr.public_inputs.data(), wr.public_inputs.size());
   const u64* pih = pi_hash.e;
 
+  if (fkind == R_FAULT_WIRE) {
+    u64& w = wr.wires[fault->a][fault->b];
+    w = rf_add(w, 1);
+  }
   RPolyBatch wires = ref_commit_values(wr.wires, c.rate_bits, c.cap_height);
   T.wires_commit = now_s() - t0; t0 = now_s();
 
@@ -679,6 +728,40 @@ int ref_prove(const RCircuit& c, const RPrecomputed& pre, const u64* inputs, u64
   out.pps.assign(ev[2].begin() + NC, ev[2].end());
   out.quotient = ev[3];
   for (int k = 0; k < NC; k++) out.zs_next.push_back(eval_poly_ext(zs_batch.coeffs[k], zeta_next));
+  if (fkind == R_FAULT_OPENING) {
+    // One opening + 1, then t_0(zeta) of every challenge solved from the verifier's own identity
+    //   vanishing_i(zeta) = Z_H(zeta) * sum_k zeta^(n k) t_{i,k}(zeta)
+    // so that the identity holds on the tampered openings; what no longer holds is that the openings are the
+    // committed polynomials' values at zeta, which only the FRI checks see.
+    const int Q = c.quotient_degree_factor;
+    std::vector<RE2>* sections[7] = {&out.constants, &out.sigmas, &out.wires, &out.zs, &out.zs_next, &out.pps, &out.quotient};
+    u64 k = fault->a;   // inside the openings and not a solved-for element: refused above otherwise
+    for (auto* v : sections) {
+      if (k < v->size()) {
+        (*v)[k] = re_add((*v)[k], re(1));
+        break;
+      }
+      k -= v->size();
+    }
+    std::vector<FE> consts, sig, wv, z, zn, pp;
+    for (auto& e : out.constants) consts.push_back(FE{e});
+    for (auto& e : out.sigmas) sig.push_back(FE{e});
+    for (auto& e : out.wires) wv.push_back(FE{e});
+    for (auto& e : out.zs) z.push_back(FE{e});
+    for (auto& e : out.zs_next) zn.push_back(FE{e});
+    for (auto& e : out.pps) pp.push_back(FE{e});
+    RE2 zeta_n = re_exp_pow2(zeta, c.degree_bits);
+    RE2 z_h = re_sub(zeta_n, re(1));
+    RE2 l0 = re_mul(z_h, re_inv(re_muls(re_sub(zeta, re(1)), (u64)n)));
+    FE van[8];
+    ref_eval_vanishing<FE>(c, FE{zeta}, FE{l0}, consts.data(), sig.data(), wv.data(), z.data(), zn.data(), pp.data(),
+                           betas.data(), gammas.data(), alphas.data(), pih, van);
+    for (int i = 0; i < NC; i++) {
+      RE2 rest = re(0);   // sum_{k >= 1} zeta^(n k) t_{i,k}(zeta)
+      for (int j = Q; j-- > 1;) rest = re_mul(re_add(rest, out.quotient[i * Q + j]), zeta_n);
+      out.quotient[i * Q] = re_sub(re_mul(van[i].v, re_inv(z_h)), rest);
+    }
+  }
   // observe openings: batch zeta = constants|sigmas|wires|zs|pps|quotient, batch g*zeta = zs_next
   for (auto* v : {&out.constants, &out.sigmas, &out.wires, &out.zs, &out.pps, &out.quotient, &out.zs_next})
     for (auto& e : *v) ch.observe_ext(e);
@@ -731,7 +814,7 @@ int ref_prove(const RCircuit& c, const RPrecomputed& pre, const u64* inputs, u64
   }
   {
     RFriParams fp{c.degree_bits, c.rate_bits, c.cap_height, c.arity_bits, c.pow_bits, c.num_queries};
-    int st = ref_fri_prove(fp, final_poly, ch, oracles, out, nullptr, msg);
+    int st = ref_fri_prove(fp, final_poly, ch, oracles, out, nullptr, msg, fault);
     if (st) return st;
   }
   T.fri = now_s() - t0;

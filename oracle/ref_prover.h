@@ -71,12 +71,39 @@ struct RFriParams {
   std::vector<int> arity_bits;
   int pow_bits, num_queries;
 };
-int ref_fri_prove(const RFriParams& fp, const std::vector<RE2>& final_poly, RChallenger& ch,
-                  const RPolyBatch* const* oracles, RProof& out, std::vector<size_t>* indices_out, std::string* msg);
+// A forging prover (tests only): ONE value is tampered with at ONE point of the proof, and everything behind that point
+// -- commitments, challenges, the PoW witness, the query openings -- runs unchanged on the tampered data.  The proof then
+// fails the one check the value belongs to and nothing ahead of it, which no edit of a finished proof can do (almost
+// every word is absorbed by the transcript, so a flip moves the PoW response and the query indices).
+// Verdicts below are ref_verify's; "layers" = the circuit has FRI reduction layers.
+//   kind 0 R_FAULT_NONE        the honest proof, word for word
+//   kind 1 R_FAULT_WIRE        a = column, b = row: witness value + 1 before the wires commit            -> 10
+//   kind 2 R_FAULT_OPENING     a = extension-element index in the proof's order of openings (constants, sigmas, wires, zs,
+//                              zs_next, pps, quotient): the opening + 1 before it is observed; then quotient opening 0 of
+//                              every challenge is set so that the vanishing identity at zeta holds again.  The index may
+//                              not be one of those compensated elements                                   -> 14, no layers 16
+//   kind 3 R_FAULT_FRI_LAYER   a = layer, b = 0: every evaluation of the layer + 1 before it is committed, b = 1: only
+//                              those of the first half of the layer's domain in natural order (the even slots of every
+//                              committed leaf); the fold continues from the honest coefficients.  With b = 1 a query
+//                              with an even index at that layer fails the layer's own comparison, one with an odd index
+//                              passes it and fails the next (the fold read a bumped neighbour)           -> 14 (see b = 1)
+//   kind 4 R_FAULT_FRI_FOLD    a = layer: folded with beta + 1 while the transcript keeps beta    -> 14, last layer 16
+//   kind 5 R_FAULT_FINAL_POLY  a = coefficient, b = component (0 / 1): + 1 before the final polynomial is observed -> 16
+// A fault the circuit has no place for (a layer it does not have, an index past the end, a compensated opening, an
+// unknown kind) is answered with status 1 and a message, never with an honest proof.
+enum { R_FAULT_NONE = 0, R_FAULT_WIRE = 1, R_FAULT_OPENING = 2, R_FAULT_FRI_LAYER = 3, R_FAULT_FRI_FOLD = 4, R_FAULT_FINAL_POLY = 5 };
+struct RFault {
+  int kind;
+  uint64_t a, b;
+};
 
-// returns 0 or a p25 status code (4 witness conflict, 5 generators not run, 6 opening in subgroup)
+int ref_fri_prove(const RFriParams& fp, const std::vector<RE2>& final_poly, RChallenger& ch,
+                  const RPolyBatch* const* oracles, RProof& out, std::vector<size_t>* indices_out, std::string* msg,
+                  const RFault* fault = nullptr);
+
+// returns 0 or a p25 status code (1 fault not applicable, 4 witness conflict, 5 generators not run, 6 opening in subgroup)
 int ref_prove(const RCircuit& c, const RPrecomputed& pre, const u64* inputs, u64 seed, RProof& out,
-              RTimings* tm, std::string* msg, const u64* filler = nullptr);
+              RTimings* tm, std::string* msg, const u64* filler = nullptr, const RFault* fault = nullptr);
 // returns 0 if the proof verifies, else a non-zero code with a message
 int ref_verify(const RCircuit& c, const RHash& circuit_digest, const std::vector<RHash>& constants_sigmas_cap,
                const RProof& p, std::string* msg);

@@ -5,9 +5,9 @@ check), mapped to the library's verdicts by `0 if code == 0 else code + 10`.  Sh
 the code: the gadget circuits (2^2 .. 2^5 rows, no FRI layer), the recursive verifier over the `and` gadget (2^11 rows,
 FRI layers, the recursion gate set) and one fib-64 proof.
 
-Known gap: editing a finished proof cannot produce P25_REJECT_FINAL_POLY -- any change to the final polynomial moves the
-PoW response and the query indices, so the proof is rejected with 21 or 23 first.  The final-polynomial check is
-exercised on the accepting side only."""
+Editing a finished proof cannot produce P25_REJECT_FINAL_POLY, nor reach the check of the openings against the
+commitments: any such change moves the PoW response and the query indices, so the proof is rejected with 20, 21 or 23
+first.  Those comparisons are reached by the forged proofs of tests/test_gpu_forged_proofs.py."""
 import numpy as np
 import pytest
 

@@ -11,6 +11,7 @@
 import numpy as np
 import pytest
 
+import forged_proofs as fp
 from conftest import P, splitmix_field
 
 GATES = {1: "Constant", 2: "PublicInput", 3: "BaseSum", 4: "U32Interleave", 5: "UninterleaveToU32", 6: "Arithmetic",
@@ -126,6 +127,43 @@ def test_constraints_not_only_generators_reject_a_bad_inner_proof(oracle, small_
         assert st == 4, what
         nbad, msg = oo.check_constraints(wires)
         assert nbad > 0, f"{what}: every gate constraint holds on a witness built from a false inner proof"
+
+
+def no_witness_and_a_violated_constraint(oo, forged, seed):
+    """A forged inner proof (tests/forged_proofs.py) passes every in-circuit check ahead of the one it was forged for.
+    It must have no witness, and with the conflict overridden -- every copy constraint then holds by construction --
+    some GATE constraint of the verifier circuit must be violated: the targeted comparison constrains something."""
+    for f in forged:
+        assert oo.witness(f.proof, seed=seed)[1] == 4, f.name
+        wires, st, _m = oo.witness_forced(f.proof, seed=seed)
+        assert st == 4, f.name
+        nbad, msg = oo.check_constraints(wires)
+        assert nbad > 0, f"{f.name}: every gate constraint holds on a witness built from a forged inner proof"
+
+
+def test_forged_inner_proofs_without_fri_layers_violate_a_constraint(oracle, small_recursion):
+    """Inner = the `and` gadget: every fault that applies to a circuit without FRI layers -- a wire (vanishing identity),
+    openings that are not the commitments' (the final-polynomial comparison at `recursion.cpp` `final_eval`, which no
+    flipped word reaches ahead of the PoW), the final polynomial itself."""
+    inner, oi, proof, outer = small_recursion
+    x, y = 0x0123456789ABCDEF % P, 0x0FEDCBA987654321 % P
+    forged = fp.forge(oi, inner, [x, y, (x & y) % P])
+    assert {f.kind for f in forged} == {fp.WIRE, fp.OPENING, fp.FINAL}
+    assert fp.oracle_codes(oi, forged, *oi.digest()) == [f.code for f in forged]
+    no_witness_and_a_violated_constraint(oracle.load_circuit(outer.to_blob()), forged, seed=9)
+
+
+def test_forged_fri_layers_and_folds_violate_a_constraint_at_depth_two(oracle, small_recursion):
+    """Inner = the 2^11-row recursive verifier (two FRI layers), outer = the depth-2 circuit: a committed layer that is
+    not the fold of the one before it, and a fold with the wrong beta, whose in-circuit comparisons (layer against
+    fold, last fold against the final polynomial) a flipped word only reaches together with a moved transcript."""
+    inner, oi, proof, outer = small_recursion
+    oo = oracle.load_circuit(outer.to_blob())
+    dg, cap = oo.digest()
+    forged = fp.forge(oo, outer, proof, kinds=(fp.FRI_LAYER, fp.FRI_FOLD))
+    assert len(forged) == 6 and fp.oracle_codes(oo, forged, dg, cap) == [f.code for f in forged]
+    outer2 = outer.build_recursive_verifier(1, digest=dg, cs_cap=cap)
+    no_witness_and_a_violated_constraint(oracle.load_circuit(outer2.to_blob()), forged, seed=3)
 
 
 def test_recursive_verifier_with_fri_layers(p25, oracle):

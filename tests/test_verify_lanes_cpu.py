@@ -4,7 +4,10 @@ run lane by lane in plain loops (tests/native/verify_lanes.cpp) against the orac
 This is the arithmetic of three of the four GPU stages -- the vanishing identity with its gate evaluators in F_p^2, the
 Merkle paths and the FRI query arithmetic, the verdict with its precedence -- without a GPU; the cooperative transcript
 kernel and the launches themselves are covered by tests/test_gpu_verify.py.  The driver merges the lanes' keys in an
-order that is not the verifier's, so a verdict that depended on which lane came last would show here."""
+order that is not the verifier's, so a verdict that depended on which lane came last would show here.
+
+The comparisons a flipped word never reaches -- openings against commitments, fold against next layer, the final
+polynomial -- are reached by the forged proofs of tests/forged_proofs.py."""
 import os
 import shutil
 import subprocess
@@ -12,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import forged_proofs as fp
 import reference_vectors as rv
 from conftest import ROOT, P
 from verify_cases import (FRI_EVAL, FRI_MERKLE, INITIAL_MERKLE, MALFORMED, OK, POW, VANISHING, Layout, expected, flipped,
@@ -51,8 +55,8 @@ class HostCase:
     """A circuit built on the host, the oracle's proof of it and the oracle's verifier data."""
 
     def __init__(self, oracle, c, inputs, seed):
-        self.c, self.oc = c, oracle.load_circuit(c.to_blob())
-        self.proof, st, _t, msg = self.oc.prove(np.asarray(inputs, dtype=np.uint64), seed=seed)
+        self.c, self.oc, self.inputs = c, oracle.load_circuit(c.to_blob()), np.asarray(inputs, dtype=np.uint64)
+        self.proof, st, _t, msg = self.oc.prove(self.inputs, seed=seed)
         assert st == 0, msg
         self.dg, self.cap = self.oc.digest()
         self.L = Layout(c)
@@ -118,3 +122,16 @@ def test_lanes_reject_words_at_or_above_p(and_case, driver):
             q[pos] = np.uint64(word)
             batch += [q, proof]
     assert driver(and_case.c, and_case.dg, and_case.cap, batch) == [OK] + [MALFORMED, OK] * 12
+
+
+@pytest.mark.parametrize("which", ["and_case", "rec_case"])
+def test_lanes_answer_forged_proofs_with_the_tables_codes(request, driver, which):
+    """Proofs that fail exactly one check (tests/forged_proofs.py), among honest ones: the verdicts are the table's, which
+    are the oracle's, and every honest neighbour is accepted."""
+    case = request.getfixturevalue(which)
+    forged = fp.forge(case.oc, case.c, case.inputs)
+    assert fp.oracle_codes(case.oc, forged, case.dg, case.cap) == [f.code for f in forged]
+    batch, want, names = fp.mixed(forged, case.proof, seed=len(forged))
+    got = driver(case.c, case.dg, case.cap, list(batch))
+    assert got == want, [(n, g, w) for n, g, w in zip(names, got, want) if g != w]
+    assert set(want) == ({OK, VANISHING, FRI_EVAL, fp.FINAL_POLY} if case.L.n_layers else {OK, VANISHING, fp.FINAL_POLY})

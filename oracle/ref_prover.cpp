@@ -438,7 +438,11 @@ std::vector<std::vector<u64>> ref_partial_products(const RCircuit& c, const std:
 }
 
 // ---------------------------------------------------------------- quotient polynomials (App. A.6)
-// upstream prover.rs `compute_quotient_polys` + "split up quotient polys": NC * Q coefficient vectors of length n
+// upstream prover.rs `compute_quotient_polys` + "split up quotient polys": NC * Q coefficient vectors of length n.
+// As upstream, the quotient is evaluated on the coset of n << qb points, qb = upstream's max_degree_bits =
+// log2_ceil(quotient_degree_factor) (the loader keeps quotient_degree_factor = 2^min(rate_bits, 3)), read from the LDE with a
+// stride of 2^(rate_bits - qb), and interpolated there: the Q chunks of n coefficients are all of it.  For a satisfied witness that is the interpolant over the whole LDE domain as well; for any other
+// wires (the stage entry points take them) only this one is what upstream computes.
 std::vector<std::vector<u64>> ref_quotient_chunks(const RCircuit& c, const RPolyBatch& constants_sigmas,
                                                   const RPolyBatch& wires, const RPolyBatch& zs_batch,
                                                   const std::vector<u64>& betas, const std::vector<u64>& gammas,
@@ -446,21 +450,26 @@ std::vector<std::vector<u64>> ref_quotient_chunks(const RCircuit& c, const RPoly
   const size_t n = c.n();
   const int NC = c.num_challenges, RW = c.num_routed, NP = c.num_partial_products, Q = c.quotient_degree_factor;
   const int lde_bits = c.degree_bits + c.rate_bits;
-  const size_t big = (size_t)1 << lde_bits;
+  int qb = 0;                                              // upstream's max_degree_bits = log2_ceil(quotient_degree_factor)
+  while ((1 << qb) < Q) qb++;
+  if (Q != 1 << qb || qb > c.rate_bits) throw std::runtime_error("quotient_degree_factor is no power of two within the rate");
+  const size_t lde_size = (size_t)1 << lde_bits;           // the committed LDEs
+  const size_t big = n << qb, step = (size_t)1 << (c.rate_bits - qb);   // the quotient's points: every step-th LDE point
   const int n_consts = c.num_constants_total();
   struct { const RPolyBatch& constants_sigmas; } pre{constants_sigmas};
   std::vector<std::vector<u64>> qvals(NC, std::vector<u64>(big));
   {
-    const u64 w_big = rf_root_of_unity(lde_bits);
+    const u64 w_big = rf_root_of_unity(c.degree_bits + qb);
     const u64 g_pow_n = rf_pow(7, n);
-    const u64 w_rate = rf_root_of_unity(c.rate_bits);
-    std::vector<u64> zh(1 << c.rate_bits), zh_inv(1 << c.rate_bits);
-    for (int k = 0; k < (1 << c.rate_bits); k++) {
+    const u64 w_rate = rf_root_of_unity(qb);
+    const size_t n_zh = (size_t)1 << qb;
+    std::vector<u64> zh(n_zh), zh_inv(n_zh);
+    for (size_t k = 0; k < n_zh; k++) {
       zh[k] = rf_sub(rf_mul(g_pow_n, rf_pow(w_rate, k)), 1);
       zh_inv[k] = rf_inv(zh[k]);
     }
     const u64 n_field = (u64)n;
-    const size_t next_step = (size_t)1 << c.rate_bits;
+    const size_t next_step = (size_t)1 << c.rate_bits;     // in LDE points: the point w_n x
     if (g_tuned && big % 8 == 0 && NC <= 8) {   // the tuned leg: eight points per pass (ref_quotient_x8.cpp), same values
       parallel_for(big / 8, [&](size_t gb, size_t ge) {
         u64 xs[8], l0s[8], outv[8][8];
@@ -469,12 +478,12 @@ std::vector<std::vector<u64>> ref_quotient_chunks(const RCircuit& c, const RPoly
           const size_t i0 = g * 8;
           for (int j = 0; j < 8; j++, x = rf_mul(x, w_big)) {
             xs[j] = x;
-            l0s[j] = rf_mul(zh[(i0 + j) % (1 << c.rate_bits)], rf_inv(rf_mul(n_field, rf_sub(x, 1))));
+            l0s[j] = rf_mul(zh[(i0 + j) % n_zh], rf_inv(rf_mul(n_field, rf_sub(x, 1))));
           }
           ref_vanishing_points_x8(c, pre.constants_sigmas, wires, zs_batch, betas.data(), gammas.data(), alphas.data(), pih, i0,
-                                  xs, l0s, outv);
+                                  step, xs, l0s, outv);
           for (int k = 0; k < NC; k++)
-            for (int j = 0; j < 8; j++) qvals[k][i0 + j] = rf_mul(outv[k][j], zh_inv[(i0 + j) % (1 << c.rate_bits)]);
+            for (int j = 0; j < 8; j++) qvals[k][i0 + j] = rf_mul(outv[k][j], zh_inv[(i0 + j) % n_zh]);
         }
       });
     } else
@@ -483,7 +492,7 @@ std::vector<std::vector<u64>> ref_quotient_chunks(const RCircuit& c, const RPoly
       FB outv[8];
       u64 x = rf_mul(7, rf_pow(w_big, ib));
       for (size_t i = ib; i < ie; i++, x = rf_mul(x, w_big)) {
-        size_t pos = rbits(i, lde_bits), pos_next = rbits((i + next_step) % big, lde_bits);
+        size_t pos = rbits(i * step, lde_bits), pos_next = rbits((i * step + next_step) % lde_size, lde_bits);
         const u64* cs = pre.constants_sigmas.leaf(pos);
         for (int k = 0; k < n_consts; k++) consts[k] = FB{cs[k]};
         for (int k = 0; k < RW; k++) sig[k] = FB{cs[n_consts + k]};
@@ -496,11 +505,11 @@ std::vector<std::vector<u64>> ref_quotient_chunks(const RCircuit& c, const RPoly
           zn[k] = FB{znl[k]};
         }
         for (int k = 0; k < NC * NP; k++) pp[k] = FB{zl[NC + k]};
-        u64 zhx = zh[i % (1 << c.rate_bits)];
+        u64 zhx = zh[i % n_zh];
         u64 l0 = rf_mul(zhx, rf_inv(rf_mul(n_field, rf_sub(x, 1))));
         ref_eval_vanishing<FB>(c, FB{x}, FB{l0}, consts.data(), sig.data(), wv.data(), z.data(), zn.data(),
                                pp.data(), betas.data(), gammas.data(), alphas.data(), pih, outv);
-        for (int k = 0; k < NC; k++) qvals[k][i] = rf_mul(outv[k].v, zh_inv[i % (1 << c.rate_bits)]);
+        for (int k = 0; k < NC; k++) qvals[k][i] = rf_mul(outv[k].v, zh_inv[i % n_zh]);
       }
     });
   }

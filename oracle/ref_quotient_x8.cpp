@@ -23,18 +23,19 @@ struct FB8 {
 };
 #include "ref_gates.h"
 
-// out[k][j] = vanishing polynomial k at coset point i0 + j (natural order), j < 8, BEFORE the division by Z_H
+// out[k][j] = vanishing polynomial k at point i0 + j (natural order) of the quotient's coset, j < 8, BEFORE the division by
+// Z_H; that point is LDE point (i0 + j) * step
 void ref_vanishing_points_x8(const RCircuit& c, const RPolyBatch& constants_sigmas, const RPolyBatch& wires,
                              const RPolyBatch& zs_batch, const u64* betas, const u64* gammas, const u64* alphas,
-                             const u64* pih, size_t i0, const u64 x[8], const u64 l0[8], u64 (*out)[8]) {
+                             const u64* pih, size_t i0, size_t step, const u64 x[8], const u64 l0[8], u64 (*out)[8]) {
   const int NC = c.num_challenges, RW = c.num_routed, NP = c.num_partial_products;
   const int lde_bits = c.degree_bits + c.rate_bits;
   const size_t big = (size_t)1 << lde_bits, next_step = (size_t)1 << c.rate_bits;
   const int n_consts = c.num_constants_total();
   long long pos[8], posn[8];
   for (int j = 0; j < 8; j++) {
-    pos[j] = (long long)rbits(i0 + j, lde_bits);
-    posn[j] = (long long)rbits((i0 + j + next_step) % big, lde_bits);
+    pos[j] = (long long)rbits((i0 + j) * step, lde_bits);
+    posn[j] = (long long)rbits(((i0 + j) * step + next_step) % big, lde_bits);
   }
   auto rows = [&](const RPolyBatch& b, const long long* p) {
     const long long w = (long long)b.n_polys;

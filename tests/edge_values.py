@@ -9,9 +9,12 @@ of every NTT pass compute u - u and u + u on equal operands; a delta column keep
 No GPU and no oracle here: `splitmix_field` is used as an index source only, and every reference is written with
 Python `int` and `pow(.., .., P)` -- no numpy arithmetic on field values.
 """
+import os
+import re
+
 import numpy as np
 
-from conftest import splitmix_field
+from conftest import ROOT, splitmix_field
 
 P = 0xFFFFFFFF00000001
 EPS = (1 << 32) - 1                      # 2^64 mod p
@@ -112,6 +115,16 @@ def geometric(n, x):
 # ---- references in Python integers --------------------------------------------------------------------------------------
 def root_of_unity(log_n):
     return pow(TWO_ADIC, 1 << (32 - log_n), P)
+
+
+def columns(n, seed):
+    """name -> column of n words: the column classes of the NTT / LDE tests (one per generator, six structured fills)."""
+    w = root_of_unity(n.bit_length() - 1)
+    cols = {name: gen(n, seed + k) for k, (name, gen) in enumerate(GENERATORS.items())}
+    cols.update({"const(p-1)": const(n, P - 1), "const(0)": const(n, 0), "alternating(p-1,0)": alternating(n, P - 1, 0),
+                 "delta(n-1,p-1)": delta(n, n - 1, P - 1), "geometric(w)": geometric(n, w),
+                 "geometric(p-1)": geometric(n, P - 1)})
+    return cols
 
 
 def bit_reverse(i, bits):
@@ -215,6 +228,61 @@ def lde_of_monomial(bits, c, k):
     out = np.empty(1 << bits, dtype=np.uint64)
     out[bit_reverse_indices(bits)] = np.array(nat, dtype=np.uint64)
     return out
+
+
+# ---- thresholds of the transform, read from its source so that the shapes follow them --------------------------------------
+def ntt_source_constants():
+    """{NTT_FACTOR_LOG, NTT_PRE_TABLE_LOG, TWO_PASS_LOG} of kernels_ntt.hip; TWO_PASS_LOG is the smallest log_n that `split`
+    gives two passes (it is written there as the largest single-pass size)."""
+    src = open(os.path.join(ROOT, "plonky2.5_amd", "csrc", "kernels_ntt.hip")).read()
+    out = {name: int(re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, src).group(1))
+           for name in ("NTT_FACTOR_LOG", "NTT_PRE_TABLE_LOG")}
+    one_pass = re.search(r"static void split\(int log_n[^{]*\{\s*if \(log_n <= (\d+)\) \{\s*log_r1 = 0;", src)
+    out["TWO_PASS_LOG"] = int(one_pass.group(1)) + 1
+    return out
+
+
+# ---- the high-rate LDE tests (rate_bits 4..8) ----------------------------------------------------------------------------
+# The naive LDE costs n * 2^(log_n + rate) Horner steps a column.  log_n 3 takes every rate; log_n 6 the two ends of the
+# range, 4 and 8, where all ten columns still run in about 2 s a direction (rates 5..7 as well would double that), so no
+# column is cut.
+HIGH_RATE_NAIVE = {3: (4, 5, 6, 7, 8), 6: (4, 8)}
+# An oracle LDE of 2^18 points and more is dominated by its Merkle tree, and a leaf of more than four words has to be hashed:
+# at (12, 8) ten columns take the oracle 15 s, four 5 s, one 4.7 s.  The cases that large keep four columns.
+HIGH_RATE_ORACLE_KEEP = ("edge", "mixed", "const(p-1)", "delta(n-1,p-1)")
+
+
+def high_rate_naive_columns(log_n, seed):
+    """(rates, {name: column}) of the Python-integer LDE tests at rates 4..8."""
+    return HIGH_RATE_NAIVE[log_n], columns(1 << log_n, seed)
+
+
+def high_rate_oracle_columns(log_n, rate_bits, seed):
+    """{name: column} of the oracle LDE tests at rates 4..8: every column below 2^18 points, four from there."""
+    cols = columns(1 << log_n, seed)
+    return cols if log_n + rate_bits < 18 else {name: cols[name] for name in HIGH_RATE_ORACLE_KEEP}
+
+
+def high_rate_closed_forms(log_n, rate_bits):
+    """(values_in, coeffs_in) for the full-size LDE tests without an oracle.
+    values_in: (name, values, coefficients, LDE or None); coeffs_in: (name, coefficients, LDE).  const(p-1) -> (p-1) delta(0),
+    LDE the constant p-1; delta(n-1, p-1) -> -(n^-1) w^k (coefficients only); geometric(w^j) -> delta(j), LDE (7 w_big^i)^j;
+    c X^k -> c (7 w_big^i)^k.  Five running products of 2^(log_n + rate_bits) steps in all: X^(n-1) serves twice."""
+    n, bits = 1 << log_n, log_n + rate_bits
+    w = root_of_unity(log_n)
+    x1, xtop = lde_of_monomial(bits, 1, 1), lde_of_monomial(bits, 1, n - 1)
+    values_in = [("const(p-1)", const(n, P - 1), intt_of_const(n, P - 1), const(1 << bits, P - 1)),
+                 ("delta(n-1,p-1)", delta(n, n - 1, P - 1), intt_of_delta(n, n - 1, P - 1), None),
+                 ("geometric(w)", geometric(n, w), intt_of_geometric(n, 1), x1),
+                 ("geometric(w^(n-1))", geometric(n, pow(w, n - 1, P)), intt_of_geometric(n, n - 1), xtop)]
+    coeffs_in = [("(p-1) X^(n-1)", delta(n, n - 1, P - 1), lde_of_monomial(bits, P - 1, n - 1)),
+                 ("(2^32-1) X", delta(n, 1, EPS), lde_of_monomial(bits, EPS, 1)),
+                 ("X^(n-1)", delta(n, n - 1, 1), xtop),
+                 ("p-1", delta(n, 0, P - 1), const(1 << bits, P - 1)),
+                 # 2^63 times a pre-scale factor t has the low word 0 or 2^63 and the high word t >> 1: the borrow of the
+                 # reduction (low word below the top half of the high word) fires for every even t
+                 ("2^63 X^(n/2+1)", delta(n, n // 2 + 1, 1 << 63), lde_of_monomial(bits, 1 << 63, n // 2 + 1))]
+    return values_in, coeffs_in
 
 
 # ---- the input classes of the partial-product / quotient tests ----------------------------------------------------------

@@ -93,6 +93,37 @@ def test_python_dft_equals_the_oracle_on_edge_columns(oracle, log_n):
             assert (lo[k] == ev.coset_lde_naive(coeffs, 3)).all(), (name, from_coeffs)
 
 
+@pytest.mark.parametrize("from_coeffs", [False, True])
+@pytest.mark.parametrize("log_n", [3, 6])
+def test_python_dft_equals_the_oracle_on_edge_columns_at_rates_4_to_8(oracle, log_n, from_coeffs):
+    """The columns, rates and Python forms of tests/test_gpu_high_rate_edge_values.py::test_lde_commit_vs_python_integers
+    == oracle.lde_commit: the oracle's LDE at rates 4..8 on boundary data is an independently checked quantity too."""
+    rates, cols = ev.high_rate_naive_columns(log_n, 200 + log_n)
+    assert set(rates) >= {4, 8} and len(cols) >= 4
+    vals = np.stack(list(cols.values()))
+    for rate in rates:
+        co, lo, _cap = oracle.lde_commit(vals, rate, 0, from_coeffs)
+        assert lo.shape == (len(cols), 1 << (log_n + rate)) and (lo < np.uint64(P)).all()
+        for k, name in enumerate(cols):
+            coeffs = vals[k] if from_coeffs else ev.intt_naive(vals[k])
+            assert (co[k] == coeffs).all(), (name, rate)
+            assert (lo[k] == ev.coset_lde_naive(coeffs, rate)).all(), (name, rate)
+
+
+@pytest.mark.parametrize("log_n,rate", [(3, 4), (3, 8), (6, 4), (6, 8)])
+def test_high_rate_closed_forms_equal_the_naive_forms(log_n, rate):
+    """ev.high_rate_closed_forms, the reference of the 2^20- and 2^21-point LDE tests, at sizes Python can check."""
+    values_in, coeffs_in = ev.high_rate_closed_forms(log_n, rate)
+    assert len(values_in) == 4 and len(coeffs_in) == 5
+    for name, values, coeffs, lde in values_in:
+        assert (ev.intt_naive(values) == coeffs).all(), name
+        if lde is not None:
+            assert (ev.coset_lde_naive(coeffs, rate) == lde).all(), name
+    assert [name for name, _v, _c, lde in values_in if lde is None] == ["delta(n-1,p-1)"]
+    for name, coeffs, lde in coeffs_in:
+        assert (ev.coset_lde_naive(coeffs, rate) == lde).all(), name
+
+
 @pytest.mark.parametrize("log_n", list(range(7)))
 def test_oracle_lde_over_the_small_end_of_the_accepted_domain(oracle, log_n):
     """oracle.lde_commit == a direct DFT and Horner at 7 w^i in Python integers for log_n 0..6, every rate_bits 0..3 and
@@ -135,6 +166,33 @@ def test_oracle_fri_accepts_the_edge_polynomials(oracle):
 @pytest.fixture(scope="module")
 def small(p25, oracle):
     return stage_circuits.build_small(p25, oracle)
+
+
+@pytest.mark.parametrize("which,rate", [("small", 4), ("gadget 14", 8)])
+def test_oracle_quotient_of_any_wires_does_not_depend_on_the_rate(p25, oracle, small, which, rate):
+    """upstream's compute_quotient_polys interpolates the quotient on the coset of 8n points whatever the rate, and those
+    points and the values of every column on them are the same at every rate >= 3: the quotient chunks of a circuit
+    rewritten to rate 4 or 8 are its rate-3 chunks, for wires that satisfy nothing as for the witness.  (An interpolant
+    over the whole LDE domain agrees with it for a satisfied witness only: the first run of
+    tests/test_gpu_high_rate_edge_values.py found the oracle computing that one.)  The 2^10-row circuit at rate 4, the
+    8-row reference-gates gadget at rate 8 (the oracle takes 10 s to load 2^10 rows at rate 8)."""
+    import high_rate as hr
+    from verify_cases import reference_gates_inputs
+    if which == "small":
+        c, oc, wires = small
+    else:
+        c = p25.Circuit.build_gadget(14, 0)
+        oc = oracle.load_circuit(c.to_blob())
+        wires, st, msg = oc.witness(reference_gates_inputs(oracle, 0x89ABCDEF, 0x01234567, 0xFFFFFFFF), seed=4)
+        assert st == 0, msg
+    assert c.config.as_tuple()[0] == 3
+    och = oracle.load_circuit(hr.rewrite_config(c.to_blob(), rate, hr.QUERIES[rate]))
+    betas, gammas, alphas = ev.uniform_challenges(11)
+    for name, w in [("witness", wires)] + [(n, m) for n, m in ev.wire_matrices(wires.shape) if n in ("edge", "const(p-1)")]:
+        zs = oc.partial_products(w, betas, gammas)
+        assert (och.partial_products(w, betas, gammas) == zs).all(), name
+        q3 = oc.quotient(w, zs, betas, gammas, alphas)
+        assert q3.any() and (och.quotient(w, zs, betas, gammas, alphas) == q3).all(), (name, rate)
 
 
 def test_small_circuit_holds_every_inner_gate_kind(small):

@@ -92,13 +92,7 @@ def test_transcript_on_edge_observations(gpu, oracle):
 
 
 # ---- NTT / LDE ----------------------------------------------------------------------------------------------------------
-def _columns(n, seed):
-    w = ev.root_of_unity(n.bit_length() - 1)
-    cols = {name: gen(n, seed + k) for k, (name, gen) in enumerate(ev.GENERATORS.items())}
-    cols.update({"const(p-1)": ev.const(n, P - 1), "const(0)": ev.const(n, 0), "alternating(p-1,0)": ev.alternating(n, P - 1, 0),
-                 "delta(n-1,p-1)": ev.delta(n, n - 1, P - 1), "geometric(w)": ev.geometric(n, w),
-                 "geometric(p-1)": ev.geometric(n, P - 1)})
-    return cols
+_columns = ev.columns          # (shared with tests/test_gpu_high_rate_edge_values.py and the CPU twins)
 
 
 @pytest.mark.parametrize("from_coeffs", [False, True])

@@ -886,6 +886,71 @@ p25_status p25_p3_verify_batch_dev(p25_p3_prover* p, const uint64_t* d_inputs, s
                                    uint32_t* d_status, void* stream);
 p25_status p25_p3_prover_scratch_bytes(p25_p3_prover* p, size_t* proving_out, size_t* verifying_out);
 
+/* ------------------------------------------------------------------------------------------
+ * CHECKING A TRACE.  A trace that does not satisfy its AIR costs p25_p3_prove_batch a whole proof and comes back as
+ * P25_ERR_INVALID_ARG and zeros.  These say WHICH constraint fails and WHERE, without a proof (plonky3's check_constraints,
+ * Winterfell's debug validation): the AIR's DAG is evaluated on every row of the trace itself.
+ *
+ * Semantics.  n = 2^log_n; constraint c is node v_c with when_c, in the AIR's constraint order.  Row i evaluates the DAG with
+ *   LOCAL / PREP_LOCAL / AUX_LOCAL   at row i
+ *   NEXT / PREP_NEXT / AUX_NEXT      at row (i + 1) mod n
+ *   PERIODIC(a)                      v_a[i mod P_a]
+ *   PUBLIC, CHALLENGE                as in the prover
+ * The auxiliary columns are the running sums of their definition, S_j(0) = 0 -- so AUX_NEXT on the last row is 0 -- under
+ * the challenges the proof of this trace would draw: the transcript is the trace root ("the commit the trace gets":
+ * p25_p3_preprocessed_commit applied to the trace as a matrix), the preprocessed root if the AIR has such columns, the
+ * public values; then n_challenges samples.  Constraint c is SELECTED on row i when
+ *   when 0   always          when 1   i == 0          when 2   i == n - 1          when 3   i < n - 1
+ * and a VIOLATION is a selected pair (i, c) whose value is non-zero (in F_p^2: either component).
+ *
+ * The report: uint64_t words per proof, at a caller-chosen stride >= p25_p3_prover_check_words (8 + 2 AW + n_constraints).
+ *   0                  the verdict: P25_P3_CHECK_OK 0, P25_P3_CHECK_VIOLATED 1, P25_P3_CHECK_ZERO_DENOMINATOR 2
+ *   1                  the number of violations, exact
+ *   2, 3               row and constraint of the first violation in (row, constraint) order; ~0 in both when there is none
+ *   4, 5               row and auxiliary column of the first zero denominator in (row, column) order; ~0 in both when none
+ *   6, 7               reserved, zero
+ *   8 .. 8 + 2 AW      per auxiliary column the total sum_i num_j(i) / den_j(i), two components: a balanced LogUp or
+ *                      permutation column reads 0 here however its constraints are written
+ *   then n_constraints words   the number of rows on which each constraint is violated; word 1 is their sum
+ * Verdict 2 leaves words 1-3, the totals and the counts at their "none" values: there are no running sums then.  The words
+ * behind a report up to the stride are neither read nor written.
+ *
+ * p25_p3_prover_check_words  host only.
+ * p25_p3_check_batch      host buffers; `traces` and `public_values` laid out as for p25_p3_prove_batch_pv.  public_values
+ *   is NULL exactly when the AIR has no public values.  A word >= p fails the whole call before any launch, as there.
+ *   n_proofs = 0: P25_OK, nothing touched.  Argument errors come first, then P25_ERR_NO_DEVICE.
+ * p25_p3_check_batch_dev  everything resident in HBM.  ENQUEUE-ONLY on `stream`, behind the handle's earlier calls through
+ *   the same event wait as the proving and verifying calls (so a check followed by p25_p3_prove_batch_dev needs no host
+ *   synchronisation), with the two blocking exceptions of p25_p3_prove_batch_dev: the handle's first compute call (which
+ *   for a check includes its first check: see Memory) and growth.  It checks no words for >= p.
+ * p25_p3_check_air_ax     the host one-shot: works without a GPU and gives the same report, word for word.  Any of
+ *   `periodic`, `preprocessed`, `aux` may be NULL.  log_blowup is needed only because the challenges depend on the trace
+ *   root.  *words_out = the report's words; report_out may be NULL to query them, else cap_words must hold them.
+ * Device: one lane per (row, proof) runs the AIR's register program (k_p3_check); a wave votes on every constraint and one
+ *   lane adds the vote's count; the first violation is one atomic per wave that has any.  A handle with auxiliary columns
+ *   first runs the proving call's own launches up to the running sums (the trace's commit, the challenges, the terms, the
+ *   scans); a proof whose terms met a zero denominator is searched for the first one instead.
+ * Memory: a check runs in the handle's PROVING scratch, in groups under the scratch budget like a proving call (one owner,
+ *   one ordering); grouping changes no report.  A leaner buffer for AIRs without auxiliary columns, which use the trace's
+ *   columns alone, is not provided.  The first check of a handle with periodic or preprocessed columns but no auxiliary
+ *   ones puts their values on the trace domain on the device (a handle with auxiliary columns has them already);
+ *   p25_p3_prover_scratch_bytes counts them under proving_out from then on.  A handle that never checks holds the device
+ *   scratch it held.  Host memory: a handle with preprocessed but no auxiliary columns keeps its host copy of the matrix
+ *   (PW 2^log_n words) until both its proving tables and these values stand -- for good if it never checks; it used to
+ *   free the copy once the proving tables stood.
+ * Threading: as for the proving calls.
+ * ------------------------------------------------------------------------------------------ */
+enum { P25_P3_CHECK_OK = 0, P25_P3_CHECK_VIOLATED = 1, P25_P3_CHECK_ZERO_DENOMINATOR = 2 };
+p25_status p25_p3_prover_check_words(const p25_p3_prover* p, size_t* words_out);
+p25_status p25_p3_check_batch(p25_p3_prover* p, const uint64_t* traces, const uint64_t* public_values, size_t n_proofs,
+                              uint64_t* report_out, size_t report_stride_words);
+p25_status p25_p3_check_batch_dev(p25_p3_prover* p, const uint64_t* d_traces, size_t trace_stride_words,
+                                  const uint64_t* d_public_values, size_t n_proofs, uint64_t* d_report,
+                                  size_t report_stride_words, void* stream);
+p25_status p25_p3_check_air_ax(const p25_air* air, const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed,
+                               const p25_air_aux* aux, const uint64_t* trace, const uint64_t* public_values, int32_t log_n,
+                               int32_t log_blowup, int32_t threads, uint64_t* report_out, size_t cap_words, size_t* words_out);
+
 /* Witness only (parity tests): wires_out[num_wires][2^degree_bits], column-major. */
 p25_status p25_witness(p25_circuit* c, const uint64_t* inputs, uint64_t seed, uint64_t* wires_out,
                        p25_status* proof_status);

@@ -7,7 +7,8 @@ import numpy as np
 __all__ = ["P25Error", "lib", "lib_path", "device_init", "shader_clock_hz", "poseidon_permute", "poseidon2_permute",
            "merkle_commit", "merkle_tree_words", "lde_commit", "EXPORTED_SYMBOLS", "P",
            "P3Config", "Circuit", "CircuitConfig", "p3_proof_from_json", "Timings", "p3_prove_fibonacci", "p3_inputs_to_json",
-           "Air", "p3_prove_air", "p3_preprocessed_commit", "P3Prover", "transcript", "fri_prove", "eval_polys", "RuntimeInfo", "runtime_info", "Comm",
+           "Air", "p3_prove_air", "p3_preprocessed_commit", "P3Prover", "CheckReport", "p3_check_air",
+           "CHECK_OK", "CHECK_VIOLATED", "CHECK_ZERO_DENOMINATOR", "transcript", "fri_prove", "eval_polys", "RuntimeInfo", "runtime_info", "Comm",
            "comm_unique_id", "WARN_HW_QUEUES_LATE", "REJECT_VANISHING", "REJECT_POW", "REJECT_MALFORMED",
            "REJECT_INITIAL_MERKLE", "REJECT_FRI_EVAL", "REJECT_FRI_MERKLE", "REJECT_FINAL_POLY"]
 
@@ -25,6 +26,8 @@ WARN_HW_QUEUES_LATE = 9
 # per-proof verdicts of Circuit.verify / verify_dev (0 = accepted): the first check the sequential verifier fails
 REJECT_VANISHING, REJECT_POW, REJECT_MALFORMED, REJECT_INITIAL_MERKLE = 20, 21, 22, 23
 REJECT_FRI_EVAL, REJECT_FRI_MERKLE, REJECT_FINAL_POLY = 24, 25, 26
+# verdicts of P3Prover.check / p3_check_air (P25_P3_CHECK_*)
+CHECK_OK, CHECK_VIOLATED, CHECK_ZERO_DENOMINATOR = 0, 1, 2
 COMM_ID_BYTES = 128
 
 
@@ -352,6 +355,10 @@ EXPORTED_SYMBOLS = {
     "p25_p3_prover_set_scratch_budget": (i32, [vp, sz]),
     "p25_p3_prove_air": (i32, [C.POINTER(AirC), vp, i32, i32, i32, C.c_uint64, i32, vp, sz, C.POINTER(sz),
                                C.POINTER(P3Config)]),
+    "p25_p3_prover_check_words": (i32, [vp, C.POINTER(sz)]),
+    "p25_p3_check_batch": (i32, [vp, vp, vp, sz, vp, sz]),
+    "p25_p3_check_batch_dev": (i32, [vp, vp, sz, vp, sz, vp, sz, vp]),
+    "p25_p3_check_air_ax": (i32, [C.POINTER(AirC), vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, C.POINTER(sz)]),
 }
 
 
@@ -649,6 +656,42 @@ def p3_prove_air(air, trace, num_queries=100, pow_bits=16, pow_start=0, threads=
     return out, cfg
 
 
+class CheckReport:
+    """One proof's report of P3Prover.check / p3_check_air (include/p25.h "CHECKING A TRACE"), decoded from its words:
+    verdict (CHECK_*), n_violations, first = (row, constraint) or None, zero_denominator = (row, column) or None,
+    totals = one (a, b) pair per auxiliary column, counts = violated rows per constraint; `words` keeps the raw report."""
+
+    def __init__(self, words, aux_width):
+        w = [int(x) for x in words]
+        none = (1 << 64) - 1
+        self.words = w
+        self.verdict = w[0]
+        self.n_violations = w[1]
+        self.first = None if w[2] == none and w[3] == none else (w[2], w[3])
+        self.zero_denominator = None if w[4] == none and w[5] == none else (w[4], w[5])
+        self.totals = [(w[8 + 2 * j], w[9 + 2 * j]) for j in range(aux_width)]
+        self.counts = w[8 + 2 * aux_width:]
+
+    def __repr__(self):
+        return ("CheckReport(verdict=%d, n_violations=%d, first=%r, zero_denominator=%r, totals=%r, counts=%r)" %
+                (self.verdict, self.n_violations, self.first, self.zero_denominator, self.totals, self.counts))
+
+
+def p3_check_air(air, trace, public_values=None, log_blowup=1, threads=None):
+    """Which constraint of `air` (binding.Air) `trace` (uint64[2^log_n][width]) breaks and where -> CheckReport, on the host
+    (p25_p3_check_air_ax: no GPU needed).  log_blowup matters only to the challenges of an AIR with auxiliary columns."""
+    threads = threads or min(16, os.cpu_count() or 1)
+    t = np.ascontiguousarray(trace, dtype=np.uint64)
+    if t.ndim != 2 or t.shape[1] != air.width or t.shape[0] & (t.shape[0] - 1) or t.shape[0] < 2:
+        raise ValueError("trace must be [2^log_n][air.width]")
+    log_n = int(t.shape[0]).bit_length() - 1
+    ac, pc, pp, ax = air.to_c(), air.periodic_to_c(), air.preprocessed_to_c(), air.aux_to_c()
+    pv = _public_rows(public_values, 1, air.n_public)
+    out = _sized(lambda buf, cap, n: lib().p25_p3_check_air_ax(C.byref(ac), _ref(pc), _ref(pp), _ref(ax), _ptr(t), _ptr(pv),
+                                                               log_n, log_blowup, threads, buf, cap, n), np.uint64)
+    return CheckReport(out, len(air.aux_columns))
+
+
 class P3Prover:
     """p25_p3_prover: the plonky3 prover on the GPU for one AIR (binding.Air) and shape.  Produces, a batch at a time, the
     words p3_prove_air returns for the same arguments -- the `inputs` of Circuit.prove / prove_dev."""
@@ -671,6 +714,10 @@ class P3Prover:
             _check(lib().p25_p3_prover_create_pc(C.byref(ac), C.byref(pc), log_n, log_blowup, num_queries, pow_bits, C.byref(h)))
         self._h = vp(h.value)
         self.width, self.log_n, self.n_public = air.width, log_n, air.n_public
+        self.aux_width = len(air.aux_columns)
+        n = sz(0)
+        _check(lib().p25_p3_prover_check_words(self._h, C.byref(n)))
+        self.check_words = int(n.value)
         self.config = P3Config()
         n = sz(0)
         _check(lib().p25_p3_prover_config(self._h, C.byref(self.config), C.byref(n)))
@@ -727,6 +774,27 @@ class P3Prover:
     def verify_dev(self, d_inputs, n, input_stride, d_status, stream=0):
         """Device-resident batch (raw device addresses), enqueued on `stream` (a raw hipStream_t; 0 = the default stream)."""
         _check(lib().p25_p3_verify_batch_dev(self._h, d_inputs, n, input_stride, d_status, C.c_void_p(stream) if stream else None))
+
+    def check(self, traces, public_values=None, report_stride=None):
+        """traces: uint64[n][2^log_n][width] (or one trace) -> one CheckReport per proof: which constraint each trace breaks
+        and where, without proving (p25_p3_check_batch).  public_values as for prove."""
+        t = _u64(traces)
+        if t.ndim == 2:
+            t = t.reshape((1,) + t.shape)
+        if t.ndim != 3 or t.shape[1:] != (1 << self.log_n, self.width):
+            raise ValueError("traces must be [n][2^log_n][width]")
+        n = t.shape[0]
+        stride = self.check_words if report_stride is None else int(report_stride)
+        out = np.zeros((n, stride), dtype=np.uint64)
+        pv = _public_rows(public_values, n, self.n_public)
+        _check(lib().p25_p3_check_batch(self._h, _ptr(t), _ptr(pv), n, _ptr(out), stride))
+        return [CheckReport(row[:self.check_words], self.aux_width) for row in out]
+
+    def check_dev(self, d_traces, trace_stride, n, d_report, report_stride, stream=0, *, d_public_values=0):
+        """Device-resident batch (raw device addresses), enqueued on `stream` (a raw hipStream_t; 0 = the default stream):
+        report i = check_words words at d_report + i * report_stride; decode a copied-back row with CheckReport."""
+        _check(lib().p25_p3_check_batch_dev(self._h, d_traces, trace_stride, d_public_values or None, n, d_report,
+                                            report_stride, C.c_void_p(stream) if stream else None))
 
     def scratch_bytes(self):
         """(proving, verifying): bytes of device scratch the handle holds now."""

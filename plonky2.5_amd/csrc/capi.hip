@@ -21,6 +21,7 @@
 #include "circuit_bytes.h"
 #include "json_io.h"
 #include "p3_circuit.h"
+#include "p3_check_lanes.h"
 #include "p3_prover.h"
 #include "p3_kernels.h"
 #include "prover.h"
@@ -941,6 +942,81 @@ p25_status p25_p3_verify_batch_dev(p25_p3_prover* p, const uint64_t* d_inputs, s
     if (s != P25_OK) return s;
     P25_LOCK(p);
     p->dev->verify_dev(d_inputs, n_proofs, input_stride_words, d_status, (hipStream_t)stream);
+    return P25_OK;
+  });
+}
+// ---- checking a trace (include/p25.h "CHECKING A TRACE") ----
+p25_status p25_p3_prover_check_words(const p25_p3_prover* p, size_t* words_out) {
+  return host_guarded([&]() -> p25_status {
+    if (!p || !words_out) throw std::invalid_argument("null argument");
+    *words_out = p->dev->check_words();
+    return P25_OK;
+  });
+}
+// the argument errors of the two checking entry points that need no device; returns false for an empty batch
+static bool p3_check_args(p25_p3_prover* p, const void* traces, const void* public_values, size_t n_proofs, void* report,
+                          size_t report_stride, size_t trace_stride) {
+  if (!p) throw std::invalid_argument("null argument");
+  if (!n_proofs) return false;
+  if (!traces || !report) throw std::invalid_argument("null argument");
+  if ((p->dev->n_public() > 0) != (public_values != nullptr))
+    throw std::invalid_argument("public_values must be NULL exactly when the prover's AIR has no public values");
+  if (report_stride < p->dev->check_words()) throw std::invalid_argument("report_stride smaller than p25_p3_prover_check_words");
+  if (trace_stride < p->dev->trace_words()) throw std::invalid_argument("trace_stride smaller than the trace");
+  if (n_proofs > ((size_t)1 << 24) || report_stride > ((size_t)1 << 60) / n_proofs || trace_stride > ((size_t)1 << 60) / n_proofs)
+    throw std::invalid_argument("batch out of range (n_proofs * stride must stay below 2^60)");
+  return true;
+}
+p25_status p25_p3_check_batch(p25_p3_prover* p, const uint64_t* traces, const uint64_t* public_values, size_t n_proofs,
+                              uint64_t* report_out, size_t report_stride_words) {
+  return host_guarded([&]() -> p25_status {
+    if (!p3_check_args(p, traces, public_values, n_proofs, report_out, report_stride_words, p ? p->dev->trace_words() : 0))
+      return P25_OK;
+    const size_t np = n_proofs * p->dev->n_public(), tw = n_proofs * p->dev->trace_words();
+    for (size_t i = 0; i < np; i++)
+      if (public_values[i] >= gl::P) throw std::invalid_argument("non-canonical field element in public_values");
+    for (size_t i = 0; i < tw; i++)
+      if (traces[i] >= gl::P) throw std::invalid_argument("non-canonical field element in a trace");
+    const p25_status s = ensure_device();
+    if (s != P25_OK) return s;
+    P25_LOCK(p);
+    p->dev->check_host(traces, public_values, n_proofs, report_out, report_stride_words);
+    return P25_OK;
+  });
+}
+p25_status p25_p3_check_batch_dev(p25_p3_prover* p, const uint64_t* d_traces, size_t trace_stride_words,
+                                  const uint64_t* d_public_values, size_t n_proofs, uint64_t* d_report,
+                                  size_t report_stride_words, void* stream) {
+  return host_guarded([&]() -> p25_status {
+    if (!p3_check_args(p, d_traces, d_public_values, n_proofs, d_report, report_stride_words, trace_stride_words)) return P25_OK;
+    const p25_status s = ensure_device();
+    if (s != P25_OK) return s;
+    P25_LOCK(p);
+    p->dev->check_dev(d_traces, trace_stride_words, d_public_values, n_proofs, d_report, report_stride_words, (hipStream_t)stream);
+    return P25_OK;
+  });
+}
+p25_status p25_p3_check_air_ax(const p25_air* air, const p25_air_periodic* periodic, const p25_air_preprocessed* preprocessed,
+                               const p25_air_aux* aux, const uint64_t* trace, const uint64_t* public_values, int32_t log_n,
+                               int32_t log_blowup, int32_t threads, uint64_t* report_out, size_t cap_words, size_t* words_out) {
+  return host_guarded([&]() -> p25_status {
+    if (!air || !words_out) throw std::invalid_argument("null argument");
+    AirProgram prog = air_from_c(air, periodic, nullptr, preprocessed, nullptr, aux, nullptr);
+    if ((prog.n_public > 0) != (public_values != nullptr))
+      throw std::invalid_argument("public_values must be NULL exactly when the AIR has no public values");
+    p3_check_params(prog, log_n, log_blowup, 1, 0);
+    *words_out = p3ck_words(prog.aux.width(), (uint32_t)prog.constraints.size());
+    if (!report_out) return P25_OK;
+    check_cap(cap_words, *words_out);
+    if (!trace) throw std::invalid_argument("null trace");
+    const size_t n = (size_t)1 << log_n;
+    std::vector<std::vector<u64>> col(prog.width, std::vector<u64>(n));
+    for (size_t r = 0; r < n; r++)
+      for (int c = 0; c < prog.width; c++) col[c][r] = trace[r * prog.width + c];
+    std::vector<u64> pub;
+    if (prog.n_public) pub.assign(public_values, public_values + prog.n_public);
+    const std::vector<u64> rep = p3_check_air(prog, col, pub, log_n, log_blowup, threads < 1 ? 1 : threads);
+    memcpy(report_out, rep.data(), rep.size() * 8);
     return P25_OK;
   });
 }

@@ -152,6 +152,7 @@ constexpr size_t P3_SCRATCH_BUDGET_BYTES = (size_t)12 << 30;
 constexpr size_t P3_VERIFY_SCRATCH_BYTES = (size_t)32 << 20;
 struct P3ProverImpl;
 struct P3VerifyArgs;   // p3_verify_lanes.h
+struct P3CheckArgs;    // p3_check_lanes.h
 class P3ProverDev {
  public:
   // host only: validates as p3_prove_air does and compiles the AIR; throws std::invalid_argument
@@ -199,12 +200,29 @@ class P3ProverDev {
   P3VerifyArgs verify_args() const;
   // bytes of device scratch the handle holds now, by side
   void scratch_bytes(size_t* proving, size_t* verifying) const;
+  // The checking side (kernels_p3_check.hip, p3_check_lanes.h; include/p25.h "CHECKING A TRACE"): which constraint a trace
+  // breaks and where, without a proof.  Runs in the proving scratch, group by group like a proving call: the transpose,
+  // and for a handle with auxiliary columns the proving call's own launches up to the scans, then the check.  The first
+  // check of a handle WITHOUT auxiliary columns puts the periodic and preprocessed values on the device (such a handle
+  // keeps them nowhere else); scratch_bytes counts them under `proving` from then on.
+  size_t check_words() const;
+  // enqueue-only on `st`; report i = check_words() words at d_report + i * report_stride
+  void check_dev(const u64* d_traces, size_t trace_stride, const u64* d_public, size_t n_proofs, u64* d_report,
+                 size_t report_stride, hipStream_t st);
+  // host buffers (checked by the caller): copies, checks on the handle's own stream, waits
+  void check_host(const u64* traces, const u64* public_values, size_t n_proofs, u64* report_out, size_t report_stride);
+  // the check as far as the handle decides it (host pointers to the programs and the tables): what the host checker
+  // (p3_check.cpp) and the host driver of the lane functions (tests/native/p3_check_lanes.cpp) start from
+  P3CheckArgs check_args() const;
 
  private:
   void ensure_impl();
   // the preprocessed tables on the device, made on `st` behind the handle's earlier work: keep = false computes the root
   // in a temporary (the verifying side needs nothing else); no-op once done or without columns
   void ensure_preprocessed(bool keep, hipStream_t st);
+  // the buffers of a group of G proofs in the handle's scratch, and the handle's constant tables
+  P3Bufs group_bufs(const P3Shape& s, uint32_t G, const u64* d_public) const;
+  void ensure_check_tables(hipStream_t st);
   void run_group(const u64* d_traces, size_t trace_stride, const u64* d_public, uint32_t G, const u64* d_pow_starts,
                  u64* d_inputs, size_t input_stride, uint32_t* d_status, hipStream_t st);
   P3Config cfg_;
@@ -212,6 +230,8 @@ class P3ProverDev {
   P3Shape shape_;
   std::vector<u64> zfirst_inv_;
   std::vector<u64> prep_values_;   // [n][PW] row-major, until the device has them
+  std::vector<u64> per_values_;    // the periodic columns' values, column after column: what a check reads by row mod P
+  uint32_t n_constraints_ = 0;
   u64 prep_root_[4] = {0, 0, 0, 0};
   bool prep_root_known_ = false;
   size_t budget_bytes_;

@@ -295,6 +295,27 @@ P3Config p3_config_for(const AirProgram& air, int log_n, int log_blowup, int num
   return cfg;
 }
 
+std::vector<gl::E2> p3_trace_challenges(const AirProgram& air, const std::vector<std::vector<u64>>& col, const std::vector<u64>& pub,
+                                        int log_n, int log_blowup, int threads) {
+  std::vector<gl::E2> chal(air.aux.n_challenges);
+  if (chal.empty()) return chal;
+  // the trace as a matrix, committed as p3_prove_air_pv commits it (which is how it commits a preprocessed matrix)
+  AirProgram::Preprocessed tm;
+  tm.width = (uint32_t)air.width;
+  tm.log_n = (uint32_t)log_n;
+  const size_t n = (size_t)1 << log_n;
+  tm.values.resize(n * tm.width);
+  for (size_t r = 0; r < n; r++)
+    for (uint32_t c = 0; c < tm.width; c++) tm.values[r * tm.width + c] = col[c][r];
+  const int T = threads < 1 ? 1 : threads;
+  Challenger ch;
+  ch.observe_digest(commit_preprocessed(tm, log_blowup, T).tree.root());
+  if (air.prep.width) ch.observe_digest(commit_preprocessed(air.prep, log_blowup, T).tree.root());
+  for (u64 v : pub) ch.observe(v);
+  for (auto& c : chal) c = ch.sample_ext();
+  return chal;
+}
+
 std::vector<u64> p3_prove_air_pv(const AirProgram& air, const std::vector<std::vector<u64>>& col, const std::vector<u64>& pub,
                                  const P3ProveParams& prm, P3Config& cfg) {
   p3_check_params(air, prm.log_n, prm.log_blowup, prm.num_queries, prm.pow_bits);

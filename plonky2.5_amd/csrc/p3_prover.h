@@ -62,6 +62,16 @@ inline size_t p3_preprocessed_words(int prep_width, int log_n, int log_blowup, i
 inline size_t p3_aux_words(int aux_width, int log_n, int log_blowup, int num_queries) {
   return aux_width ? 4 + 8 * (size_t)aux_width + (size_t)num_queries * (2 * (size_t)aux_width + 4 * (size_t)(log_n + log_blowup)) : 0;
 }
+// Checking a trace (include/p25.h "CHECKING A TRACE"; p3_check.cpp): the report -- p3ck_words(AW, constraints) words,
+// p3_check_lanes.h -- of `col` against `air`, by the per-row functions the device runs.  No proof is made: log_blowup is
+// needed only because the challenges of an AIR with auxiliary columns hang on the trace's commitment.  Throws
+// std::invalid_argument as p3_prove_air_pv does for its arguments.
+std::vector<u64> p3_check_air(const AirProgram& air, const std::vector<std::vector<u64>>& col, const std::vector<u64>& pub,
+                              int log_n, int log_blowup, int threads);
+// The challenges the proof of this trace would draw: the transcript is the trace root, the preprocessed root if the AIR
+// has such columns, the public values; then air.aux.n_challenges samples.
+std::vector<gl::E2> p3_trace_challenges(const AirProgram& air, const std::vector<std::vector<u64>>& col, const std::vector<u64>& pub,
+                                        int log_n, int log_blowup, int threads);
 // The commitment of a preprocessed matrix: the Poseidon2 MMCS root over the columns' LDE on 7 H_{n 2^log_blowup} in
 // bit-reversed leaf order, the commit the trace gets.  Throws std::invalid_argument (width 0 included: nothing to commit).
 std::array<u64, 4> p3_preprocessed_commit(const AirProgram::Preprocessed& prep, int log_blowup, int threads);

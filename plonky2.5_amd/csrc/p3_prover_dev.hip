@@ -2,6 +2,7 @@
 // group of proofs, which mirrors p3_prove_air (p3_prover.cpp) stage by stage.  The kernels are in kernels_p3.hip.
 #include <algorithm>
 #include <functional>
+#include "p3_check_lanes.h"
 #include "p3_prover.h"
 #include "p3_prover_impl.h"
 #include "staging.h"
@@ -153,6 +154,8 @@ P3ProverDev::P3ProverDev(const AirProgram& air, int log_n, int log_blowup, int n
   s.num_queries = num_queries; s.pow_bits = pow_bits;
   s.n_instr = (uint32_t)prog_.instr.size();
   s.n_public = (uint32_t)air.n_public;
+  n_constraints_ = (uint32_t)air.constraints.size();
+  for (const auto& pc : air.periodic) per_values_.insert(per_values_.end(), pc.values.begin(), pc.values.end());
   s.PW = air.prep.width;
   if (s.PW) prep_values_ = air.prep.values;
   const uint32_t PW = s.PW;
@@ -306,8 +309,11 @@ void P3ProverDev::ensure_preprocessed(bool keep, hipStream_t st) {
   prep_root_known_ = true;
   if (keep) {
     impl_->prep = std::move(tables);
-    prep_values_.clear();
-    prep_values_.shrink_to_fit();
+    // a handle without auxiliary columns keeps the host's copy until its checker's tables stand (ensure_check_tables)
+    if (s.AW || impl_->check_tab.words) {
+      prep_values_.clear();
+      prep_values_.shrink_to_fit();
+    }
   }
 }
 void P3ProverDev::preprocessed_commit(u64 out[4]) {
@@ -372,13 +378,8 @@ void P3ProverDev::prove_dev(const u64* d_traces, size_t trace_stride, const u64*
   P25_HIP(hipGetLastError());
 }
 
-void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, const u64* d_public, uint32_t G, const u64* d_pow_starts,
-                            u64* d_inputs, size_t input_stride, uint32_t* d_status, hipStream_t st) {
-  P3Shape s = shape_;
-  s.G = G;
-  const int k = s.k, B = s.B;
-  const size_t n = (size_t)1 << k, N2 = (size_t)1 << s.L, W = s.W, Q = s.Q, Q2 = 2 * Q;
-  NttTables& tb = impl_->tables;
+P3Bufs P3ProverDev::group_bufs(const P3Shape& s, uint32_t G, const u64* d_public) const {
+  const size_t n = (size_t)1 << s.k, N2 = (size_t)1 << s.L;
   const P3Carve carve = carve_scratch(s, G, impl_->scratch.p);
   if (carve.words != G * scratch_words_per_proof() || carve.words > impl_->scratch.words)
     throw std::logic_error("p3 device prover: a group's scratch is out of step with the per-proof figure");
@@ -387,13 +388,24 @@ void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, const u64*
   b.consts = impl_->consts.p;
   b.zfirst_inv = impl_->zfirst.p;
   b.pub = d_public;
-  if (s.PW) {   // the handle's constant tables: the same pointers for every group
+  if (s.PW && impl_->prep.words) {   // the handle's constant tables: the same pointers for every group
     b.pcoef = impl_->prep.p;
     b.plde = b.pcoef + (size_t)s.PW * n;
     b.ptree = b.plde + (size_t)s.PW * N2;
     if (s.AW) b.pvals = b.ptree + 8 * N2;
   }
   b.aux_prog = reinterpret_cast<const P3Instr*>(impl_->aux_prog.p);
+  return b;
+}
+
+void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, const u64* d_public, uint32_t G, const u64* d_pow_starts,
+                            u64* d_inputs, size_t input_stride, uint32_t* d_status, hipStream_t st) {
+  P3Shape s = shape_;
+  s.G = G;
+  const int k = s.k, B = s.B;
+  const size_t n = (size_t)1 << k, N2 = (size_t)1 << s.L, W = s.W, Q = s.Q, Q2 = 2 * Q;
+  NttTables& tb = impl_->tables;
+  const P3Bufs b = group_bufs(s, G, d_public);
 
   // the LDE on shift * <w_{n 2^B}> in bit-reversed order; 16 cosets as two interleaved sets of 8 (coset 2 c + e of the
   // first kind is coset c of the set with shift * w^e, and lands in half e of the bit-reversed output)
@@ -443,6 +455,114 @@ void P3ProverDev::run_group(const u64* d_traces, size_t trace_stride, const u64*
   p3_launch_pow_search(s, b, d_pow_starts, st);                    // :394-400
   p3_launch_chain(s, b, P3_CH_QUERIES, 0, st);                     // :401-404
   p3_launch_gather(s, b, d_inputs, input_stride, d_status, st);    // :423-445
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Checking a trace (include/p25.h "CHECKING A TRACE")
+// ---------------------------------------------------------------------------------------------------------------------
+size_t P3ProverDev::check_words() const { return p3ck_words(shape_.AW, n_constraints_); }
+
+P3CheckArgs P3ProverDev::check_args() const {
+  const P3Shape& s = shape_;
+  P3CheckArgs a{};
+  a.prog = prog_.instr.data();
+  a.aux_prog = prog_.aux_instr.data();
+  a.consts = prog_.consts.data();
+  a.per_val = per_values_.data();
+  a.n_instr = s.n_instr;
+  a.n_aux_instr = s.n_aux_instr;
+  a.n_constraints = n_constraints_;
+  a.k = s.k; a.W = s.W; a.PW = s.PW; a.AW = s.AW; a.n_public = s.n_public;
+  return a;
+}
+
+// The periodic and preprocessed values of a handle without auxiliary columns, on the device for its checker: made by its
+// first check (one with such columns has them for its term kernel: P3Shape::per_val, P3Bufs::pvals).  Blocks the host.
+void P3ProverDev::ensure_check_tables(hipStream_t st) {
+  const P3Shape& s = shape_;
+  const size_t n = (size_t)1 << s.k, per = per_values_.size(), words = per + (size_t)s.PW * n;
+  if (s.AW || !words || impl_->check_tab.words) return;
+  if (s.PW && prep_values_.size() != s.PW * n) throw std::logic_error("p3 device prover: the preprocessed values are gone");
+  std::vector<u64> host(per_values_);
+  host.resize(words);
+  for (size_t r = 0; r < n; r++)
+    for (size_t c = 0; c < s.PW; c++) host[per + c * n + r] = prep_values_[r * s.PW + c];
+  DevMem tab(words);
+  P25_HIP(hipMemcpyAsync(tab.p, host.data(), words * 8, hipMemcpyHostToDevice, st));
+  P25_HIP(hipStreamSynchronize(st));
+  impl_->check_tab = std::move(tab);
+  if (impl_->prep.words) {   // the proving side has its tables: nothing reads the host's copy any more
+    prep_values_.clear();
+    prep_values_.shrink_to_fit();
+  }
+}
+
+void P3ProverDev::check_dev(const u64* d_traces, size_t trace_stride, const u64* d_public, size_t n_proofs, u64* d_report,
+                            size_t report_stride, hipStream_t st) {
+  if (!n_proofs) return;
+  ensure_impl();
+  const P3Shape& sh = shape_;
+  if (sh.AW) ensure_preprocessed(true, st);   // the transcript observes the preprocessed root; the terms read the values
+  ensure_check_tables(st);
+  const size_t G = group_size(n_proofs), need = G * scratch_words_per_proof();
+  if (impl_->scratch.words < need) {
+    sync();   // an earlier call may still be using the old allocation
+    impl_->scratch.regrow(need);
+  }
+  if (impl_->recorded) P25_HIP(hipStreamWaitEvent(st, impl_->done, 0));   // one scratch, one ordering: as prove_dev
+  P3CallRecord record{impl_, st};
+  const int k = sh.k, B = sh.B;
+  const size_t n = (size_t)1 << k, N2 = (size_t)1 << sh.L, W = sh.W;
+  NttTables& tb = impl_->tables;
+  P3CheckArgs a = check_args();
+  a.prog = reinterpret_cast<const P3Instr*>(impl_->prog.p);
+  a.aux_prog = reinterpret_cast<const P3Instr*>(impl_->aux_prog.p);
+  a.consts = impl_->consts.p;
+  for (size_t g0 = 0; g0 < n_proofs; g0 += G) {
+    P3Shape s = sh;
+    s.G = (uint32_t)std::min(G, n_proofs - g0);
+    const P3Bufs b = group_bufs(s, s.G, sh.n_public ? d_public + g0 * sh.n_public : nullptr);
+    p3_launch_transpose(d_traces + g0 * trace_stride, trace_stride, s, b, st);
+    if (s.AW) {   // run_group's launches up to the scans: the challenges hang on the trace's commitment
+      ntt_inverse(tb, b.tvals, n, false, b.tmp, n, b.tcoef, n, k, (int)(s.G * W), 1, st);
+      if (B <= 3) {
+        ntt_lde_bitrev(tb, b.tcoef, n, b.tlde, N2, k, B, (int)(s.G * W), gl::GENERATOR, st);
+      } else {
+        ntt_lde_bitrev(tb, b.tcoef, n, b.tlde, N2, k, 3, (int)(s.G * W), gl::GENERATOR, st);
+        ntt_lde_bitrev(tb, b.tcoef, n, b.tlde + N2 / 2, N2, k, 3, (int)(s.G * W), gl::mul(gl::GENERATOR, gl::root_of_unity(s.L)), st);
+      }
+      p3_launch_commit_cols(b.tlde, W * N2, 2 * N2, N2, (uint32_t)W, N2, b.ttree, 8 * N2, s.G, st);
+      p3_launch_chain(s, b, P3_CH_TRACE, 0, st);
+      p3_launch_aux_columns(s, b, st);
+    }
+    P3CheckBatch bt{};
+    bt.tvals = b.tvals;
+    bt.avals = b.avals;
+    bt.pub = b.pub;
+    bt.chal = b.hdr + s.o_chal;
+    bt.chal_stride = s.hdr_stride;
+    bt.state = b.state;
+    bt.report = d_report + g0 * report_stride;
+    bt.report_stride = report_stride;
+    a.per_val = s.AW ? impl_->consts.p + s.per_val : impl_->check_tab.p;
+    a.pvals = s.AW ? b.pvals : impl_->check_tab.p + per_values_.size();
+    p3_launch_check(a, bt, s.G, st);
+  }
+  P25_HIP(hipGetLastError());
+}
+
+void P3ProverDev::check_host(const u64* traces, const u64* public_values, size_t n_proofs, u64* report_out, size_t report_stride) {
+  if (!n_proofs) return;
+  const size_t tw = trace_words(), np = shape_.n_public, cw = check_words();
+  ensure_impl();
+  hipStream_t st = impl_->host_stream();
+  DevMem d_traces(n_proofs * tw), d_pub(n_proofs * np), d_rep(n_proofs * cw);
+  P25_HIP(hipMemcpyAsync(d_traces.p, traces, n_proofs * tw * 8, hipMemcpyHostToDevice, st));
+  if (np) P25_HIP(hipMemcpyAsync(d_pub.p, public_values, n_proofs * np * 8, hipMemcpyHostToDevice, st));
+  check_dev(d_traces.p, tw, np ? d_pub.p : nullptr, n_proofs, d_rep.p, cw, st);
+  // the report_stride - check_words words behind a report stay untouched
+  P25_HIP(hipMemcpy2DAsync(report_out, report_stride * 8, d_rep.p, cw * 8, cw * 8, n_proofs, hipMemcpyDeviceToHost, st));
+  P25_HIP(hipStreamSynchronize(st));
 }
 
 void P3ProverDev::prove_host(const u64* traces, const u64* public_values, size_t n_proofs, const u64* pow_starts,

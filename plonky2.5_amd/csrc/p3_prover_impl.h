@@ -13,6 +13,9 @@ struct P3ProverImpl {
   DevMem aux_prog;   // the auxiliary columns' terms' program (P3AirDevice::aux_instr); empty without such columns
   DevMem prep;       // the preprocessed columns' tables: coefficients | LDE | tree (p3_prover_dev.hip); empty until a proving call
   DevMem prep_root;  // the 4 words of the preprocessed commitment: all the verifying side keeps of the columns
+  // the checker's value tables of a handle WITHOUT auxiliary columns: periodic values | preprocessed values [PW][n];
+  // empty until its first check (a handle with such columns reads the term kernel's tables)
+  DevMem check_tab;
   DevMem vscratch;   // the verifier's: challenge blocks and folded values (p3_verify_dev.hip)
   DevStream own_stream;   // the host entry points' (prove_host, verify_host): created by the first of them
   // Recorded behind the last launch of every compute call.  The next call's stream waits for it before it touches the

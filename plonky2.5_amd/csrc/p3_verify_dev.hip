@@ -16,7 +16,7 @@ size_t P3ProverDev::verify_chunk(size_t n_proofs) const {
   return std::min(std::max<size_t>(1, c), n_proofs);
 }
 void P3ProverDev::scratch_bytes(size_t* proving, size_t* verifying) const {
-  if (proving) *proving = impl_ ? (impl_->scratch.words + impl_->prep.words) * 8 : 0;   // the preprocessed tables count here
+  if (proving) *proving = impl_ ? (impl_->scratch.words + impl_->prep.words + impl_->check_tab.words) * 8 : 0;   // the preprocessed tables and the checker's count here
   if (verifying) *verifying = impl_ ? impl_->vscratch.words * 8 : 0;
 }
 

@@ -24,6 +24,12 @@ auxiliary column) beside the plain constraint c = f m, against the same AIR with
 alone); 2^LOG_N rows, the largest batch of --batches.  Reported under "aux" and written to profiles/p3_aux.json as well: ms
 per proof for both, and the share of the call that the term + scan + auxiliary-commit stage takes (HIP events around it,
 P3Prover.aux_stage_ms); the last row with auxiliary columns is asserted equal to the host prover's.
+
+--check measures the trace checker (include/p25.h, CHECKING A TRACE) INSTEAD of the shapes above: P3Prover.check_dev beside
+P3Prover.prove_dev on the same device-resident batch of 16 satisfying traces, for two AIRs -- `whens` (width 2, two public
+values, one constraint of each `when` kind) at 2^12 rows, and the --aux-lookup LogUp range check (one auxiliary column) at
+2^--check-lookup-log-n rows.  HIP events around each call on one stream, one warm-up, the median of 5; every report is
+asserted to say "no violation" and every proof to succeed.  Written to profiles/p3_check.json (--check-out).
 """
 import argparse
 import json
@@ -175,6 +181,72 @@ def bench_aux(p25, torch, dev, args):
     return out
 
 
+def whens(p25, log_n):
+    """-> (air, trace[n][2], public values[2]): b (b - 1) always, x = PUBLIC(0) on the first row, x' = x + b on transitions,
+    x = PUBLIC(1) on the last row; random bits in b."""
+    n = 1 << log_n
+    air = p25.Air(2, n_public=2)
+    x, b = air.local(0), air.local(1)
+    air.assert_zero(air.mul(b, air.sub(b, air.const(1))))
+    air.when_first_row(air.sub(x, air.public(0)))
+    air.when_transition(air.sub(air.sub(air.next(0), x), b))
+    air.when_last_row(air.sub(x, air.public(1)))
+    bits = np.random.default_rng(31).integers(0, 2, n, dtype=np.uint64)
+    xs = np.uint64(1000) + np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(bits[:-1], dtype=np.uint64)])
+    return air, np.ascontiguousarray(np.stack([xs, bits], axis=1)), np.array([1000, int(xs[-1])], dtype=np.uint64)
+
+
+def bench_check(p25, torch, dev, args):
+    b, reps = 16, 5
+    out = {"tool": "tools/p3_prover_bench.py --check", "batch": b, "queries": args.queries, "pow_bits": args.pow_bits,
+           "timing": "HIP events around one call on one stream; one warm-up call of each, then the median of %d" % reps,
+           "device": torch.cuda.get_device_name(0), "airs": {}}
+    shapes = [("whens", 12, whens(p25, 12)), ("logup_range", args.check_lookup_log_n, lookup(p25, args.check_lookup_log_n, True) + (None,))]
+    for name, log_n, (air, trace, pv) in shapes:
+        pr = p25.P3Prover(air, log_n, 1, args.queries, args.pow_bits)
+        ni, cw = pr.num_inputs, pr.check_words
+        d_traces = torch.from_numpy(trace.view(np.int64).copy()).to(dev).reshape(1, -1).repeat(b, 1).contiguous()
+        d_pv = None if pv is None else torch.from_numpy(pv.view(np.int64).copy()).to(dev).reshape(1, -1).repeat(b, 1).contiguous()
+        pvp = 0 if d_pv is None else d_pv.data_ptr()
+        d_inputs = torch.zeros((b, ni), dtype=torch.int64, device=dev)
+        d_status = torch.zeros(b, dtype=torch.int32, device=dev)
+        d_report = torch.zeros((b, cw), dtype=torch.int64, device=dev)
+        stream = torch.cuda.Stream()
+        sp = stream.cuda_stream
+
+        def prove():
+            pr.prove_dev(d_traces.data_ptr(), trace.size, b, 0, d_inputs.data_ptr(), ni, d_status.data_ptr(), stream=sp,
+                         d_public_values=pvp)
+
+        def check():
+            pr.check_dev(d_traces.data_ptr(), trace.size, b, d_report.data_ptr(), cw, stream=sp, d_public_values=pvp)
+
+        def timed(call):
+            call()   # warm-up: code objects, scratch, the handle's tables
+            stream.synchronize()
+            ms = []
+            for _ in range(reps):
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record(stream)
+                call()
+                t1.record(stream)
+                t1.synchronize()
+                ms.append(t0.elapsed_time(t1))
+            return ms
+
+        torch.cuda.synchronize()
+        prove_ms, check_ms = timed(prove), timed(check)
+        assert d_status.cpu().numpy().tolist() == [0] * b, "device prover reported a failure"
+        rep_words = d_report.cpu().numpy().view(np.uint64)
+        assert (rep_words[:, 0] == 0).all() and (rep_words[:, 1] == 0).all(), "the checker reports a violation in a satisfying trace"
+        out["airs"][name] = {"log_n": log_n, "width": int(air.width), "constraints": len(air.constraints),
+                             "aux_columns": len(air.aux_columns), "num_inputs": ni, "check_words": cw,
+                             "prove_call_ms": [round(t, 4) for t in prove_ms], "check_call_ms": [round(t, 4) for t in check_ms],
+                             "prove_ms_per_proof": float(np.median(prove_ms)) / b, "check_ms_per_proof": float(np.median(check_ms)) / b}
+        pr.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-n", type=int, nargs="+", default=[12, 16, 20])
@@ -189,6 +261,10 @@ def main():
     ap.add_argument("--aux-lookup", type=int, default=0, metavar="LOG_N",
                     help="also measure the LogUp range check with one auxiliary column at 2^LOG_N rows (0 = off)")
     ap.add_argument("--aux-out", default=os.path.join(ROOT, "profiles", "p3_aux.json"))
+    ap.add_argument("--check", action="store_true",
+                    help="measure check_dev beside prove_dev (whens at 2^12, the LogUp range check) and nothing else")
+    ap.add_argument("--check-lookup-log-n", type=int, default=14)
+    ap.add_argument("--check-out", default=os.path.join(ROOT, "profiles", "p3_check.json"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "p3_prover_bench.json"))
     args = ap.parse_args()
 
@@ -196,6 +272,14 @@ def main():
     p25 = entry.load_package()
     p25.device_init(0)
     dev = torch.device("cuda", 0)
+    if args.check:
+        result = bench_check(p25, torch, dev, args)
+        os.makedirs(os.path.dirname(os.path.abspath(args.check_out)), exist_ok=True)
+        with open(args.check_out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps(result))
+        return
     air = p25.Air.fibonacci()
     result = {"tool": "tools/p3_prover_bench.py", "air": "fibonacci", "queries": args.queries, "pow_bits": args.pow_bits,
               "host_threads": args.threads, "device": torch.cuda.get_device_name(0), "shapes": []}

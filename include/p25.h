@@ -32,7 +32,16 @@ enum {
   P25_ERR_WITNESS_CONFLICT = 4,     /* "Partition containing .. was set twice with different values" */
   P25_ERR_GENERATORS_NOT_RUN = 5,   /* "N generators weren't run" */
   P25_ERR_OPENING_IN_SUBGROUP = 6,  /* Err("Opening point is in the subgroup.") */
-  P25_ERR_INTERNAL = 7,
+  P25_ERR_INTERNAL = 7,             /* as a per-proof status: a RandomAccessGenerator whose index is not below 16 */
+  /* What the witness generators do where upstream's panic (pinned by tests/test_gpu_witgen_edge_values.py, the oracle the same):
+   *   RandomAccessGenerator, index >= 16 (16, p - 1, ..): that proof gets P25_ERR_INTERNAL, no proof words are written for
+   *     it, the other proofs of the batch are unaffected.
+   *   The inverse of zero is zero.  QuotientGeneratorExtension with the denominator (0, 0) writes the quotient (0, 0): under
+   *     div_extension's `quotient * denominator == numerator` that is P25_ERR_WITNESS_CONFLICT for a numerator != 0 and a
+   *     satisfied witness (P25_OK) for the numerator (0, 0).
+   *   InterpolationGenerator (CosetInterpolationGate) with shift 0 writes the shifted point (0, 0) and the interpolant's value
+   *     there.  No copy constraint sees this: the status is P25_OK although the gate's `point == shifted_point * shift` fails
+   *     for a point != 0, and the proof written does not verify.  A shift of 0 is the caller's error (a coset has none). */
   P25_ERR_PARSE = 8,
   /* p25_device_init_ex only: the device IS selected and usable, but the hardware-queue request probably came too late to have
    * an effect (below).  The one status that is a warning, not a failure. */

@@ -364,7 +364,13 @@ RWitnessResult ref_generate_witness(const RCircuit& c, const u64* inputs, u64 se
       bool ready = true;
       for (u32 i = 0; i < g.n_deps && ready; i++) ready = w.has(c.gen_args[g.arg_off + i]);
       if (!ready) continue;
-      run_generator(c, g, w, seed, filler, out);
+      try {
+        run_generator(c, g, w, seed, filler, out);
+      } catch (const std::exception& e) {  // where upstream's generator panics: status 7 (P25_ERR_INTERNAL), no wires
+        res.status = 7;
+        res.message = e.what();
+        return res;
+      }
       expired[gi] = 1;
       remaining--;
       for (u32 i = 0; i < g.n_outs; i++) {

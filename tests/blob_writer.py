@@ -14,8 +14,12 @@ MAGIC = b"P25CIRC1"
 # gate kinds / generator kinds of the blob (INTEGRATION.md section 5, tables "gate kind" and "generator kind")
 G_NOOP, G_CONSTANT, G_PUBLIC_INPUT, G_ARITHMETIC = 0, 1, 2, 6
 G_U32_INTERLEAVE, G_U32_UNINTERLEAVE, G_U32_ARITHMETIC, G_POSEIDON2 = 4, 5, 9, 10     # the reference's own four gates
+G_BASE_SUM, G_MUL_EXT, G_EXPONENTIATION, G_ARITH_EXT, G_POSEIDON = 3, 7, 8, 11, 12
+G_RANDOM_ACCESS, G_REDUCING, G_REDUCING_EXT, G_COSET_INTERP, G_POSEIDON_MDS = 13, 14, 15, 16, 17
 GEN_CONSTANT, GEN_RANDOM, GEN_ARITHMETIC = 0, 1, 2
+GEN_MUL_EXT, GEN_QUOTIENT_EXT, GEN_BASE_SPLIT, GEN_WIRE_SPLIT, GEN_BASE_SUM, GEN_LOW_HIGH, GEN_EXPONENTIATION = 3, 4, 5, 6, 7, 8, 9
 GEN_POSEIDON2, GEN_U32_ARITHMETIC, GEN_U32_INTERLEAVE, GEN_U32_UNINTERLEAVE = 10, 11, 12, 13
+GEN_ARITH_EXT, GEN_POSEIDON, GEN_RANDOM_ACCESS, GEN_REDUCING, GEN_REDUCING_EXT, GEN_COSET_INTERP, GEN_POSEIDON_MDS = 14, 15, 16, 17, 18, 19, 20
 _PHANTOM = "PhantomData<plonky2_field::goldilocks_field::GoldilocksField>"
 # (degree, Gate::id()) -- orders the gate set; the reference's ids are `format!("{self:?}")` of its structs
 # (interleave_u32.rs:98-100, uninterleave_to_u32.rs:110-112, arithmetic_u32.rs:102-104, poseidon2_gate.rs:146-148)
@@ -28,12 +32,33 @@ GATE_ORDER = {
     G_ARITHMETIC: (3, "ArithmeticGate { num_ops: 20 }"),
     G_U32_ARITHMETIC: (4, "U32ArithmeticGate { num_ops: 3, _phantom: " + _PHANTOM + " }"),
     G_POSEIDON2: (7, "Poseidon2Gate { _phantom: " + _PHANTOM + " }<WIDTH=12>"),
+    # upstream's gates: degree() of each gate file, ids as far as INTEGRATION.md section 5 spells them (".." = parameters
+    # it leaves out; the names alone already order any two of them, the first differing letter being inside the name)
+    G_BASE_SUM: (2, "BaseSumGate { num_limbs: 63 } + Base: 2"),                      # degree = the base B
+    G_MUL_EXT: (3, "MulExtensionGate { num_ops: 13 }"),
+    G_EXPONENTIATION: (4, "ExponentiationGate { num_power_bits: 66, .. }"),
+    G_ARITH_EXT: (3, "ArithmeticExtensionGate { num_ops: 10 }"),
+    G_POSEIDON: (7, "PoseidonGate(..)<WIDTH=12>"),
+    G_RANDOM_ACCESS: (5, "RandomAccessGate { bits: 4, num_copies: 4, num_extra_constants: 2, .. }<D=2>"),   # bits + 1
+    G_REDUCING: (2, "ReducingGate { num_coeffs: 43 }"),
+    G_REDUCING_EXT: (2, "ReducingExtensionGate { num_coeffs: 32 }"),
+    G_COSET_INTERP: (6, "CosetInterpolationGate { subgroup_bits: 4, degree: 6, .. }<D=2>"),                # its `degree`
+    G_POSEIDON_MDS: (1, "PoseidonMdsGate(..)<WIDTH=12>"),
 }
 # num_constraints of the reference's gates: interleave_u32.rs:229-231 (num_ops * (2 + 32)), uninterleave_to_u32.rs:264-266
 # (num_ops * (3 + 64)), arithmetic_u32.rs:167-169 (num_ops * (4 + 32)), poseidon2_gate.rs:425-427 (1 + 4 + 12 * 3 + 22 + 12 * 4 + 12)
 GATE_CONSTRAINTS = {G_NOOP: 0, G_CONSTANT: 2, G_PUBLIC_INPUT: 4, G_ARITHMETIC: 20, G_U32_INTERLEAVE: 3 * 34,
-                    G_U32_UNINTERLEAVE: 2 * 67, G_U32_ARITHMETIC: 3 * 36, G_POSEIDON2: 123}
-MULTI_OPS = {G_U32_INTERLEAVE: 3, G_U32_UNINTERLEAVE: 2, G_U32_ARITHMETIC: 3}    # ops per row (num_ops at 135 wires / 80 routed)
+                    G_U32_UNINTERLEAVE: 2 * 67, G_U32_ARITHMETIC: 3 * 36, G_POSEIDON2: 123,
+                    # upstream: one sum + 63 limb checks; 2 per extension op; 66 steps + the output; Poseidon as its clone
+                    # Poseidon2; per copy 4 bit checks + index + claimed element, + 2 extra constants; 2 per accumulator;
+                    # the shifted point + two intermediate (evaluation, product) states + the value, 2 words each; 12 x 2
+                    G_BASE_SUM: 1 + 63, G_MUL_EXT: 13 * 2, G_EXPONENTIATION: 66 + 1, G_ARITH_EXT: 10 * 2, G_POSEIDON: 123,
+                    G_RANDOM_ACCESS: 4 * (4 + 2) + 2, G_REDUCING: 43 * 2, G_REDUCING_EXT: 32 * 2,
+                    G_COSET_INTERP: 2 + 2 * 4 + 2, G_POSEIDON_MDS: 24}
+# ops per row (num_ops at 135 wires / 80 routed)
+MULTI_OPS = {G_U32_INTERLEAVE: 3, G_U32_UNINTERLEAVE: 2, G_U32_ARITHMETIC: 3, G_RANDOM_ACCESS: 4}
+EXT_OPS = {G_MUL_EXT: (13, 6), G_ARITH_EXT: (10, 8)}      # (ops per row, wires per op) of the gates with per-row constants
+BASE_SUM_LIMBS, EXP_BITS, RA_BITS, RA_VEC, RED_COEFFS, REDX_COEFFS = 63, 66, 4, 16, 43, 32
 MAX_DEGREE = 9                                       # max_quotient_degree_factor + 1 (upstream selectors.rs)
 UNUSED_SELECTOR = 0xFFFFFFFF
 NUM_WIRES, NUM_ROUTED, NUM_CONSTANTS, ARITH_OPS = 135, 80, 2, 20   # CircuitConfig::standard_recursion_config()
@@ -58,6 +83,8 @@ class MiniCircuit:
         self.open_arith = {}           # (c0, c1) -> (row, next op)
         self.open_ops = {}             # multi-op gate kind -> (row, next op)   (CircuitBuilder::find_slot)
         self.generators = []           # (kind, c0, c1, aux, deps, outs)
+        self.open_ext = {}             # (extension gate kind, c0, c1) -> (row, next op)
+        self.base_sum_limbs = {}       # BaseSum row -> limbs its BaseSplitGenerator writes
 
     def virtual(self):
         self.n_virtual += 1
@@ -139,6 +166,162 @@ class MiniCircuit:
         for i, t in enumerate(state):
             self.connect(t, ("w", row, i))
         return [("w", row, 12 + i) for i in range(12)]
+
+    # ---- upstream's remaining gates (wire layouts: INTEGRATION.md section 5a.1, "deps -> outs as wire columns of row")
+    def _ext_slot(self, kind, c0, c1):
+        ops, _w = EXT_OPS[kind]
+        key = (kind, c0, c1)
+        if key in self.open_ext:
+            row, op = self.open_ext[key]
+        else:
+            row, op = len(self.rows), 0
+            self.rows.append([kind, c0, c1])
+        if op == ops - 1:
+            self.open_ext.pop(key, None)
+        else:
+            self.open_ext[key] = (row, op + 1)
+        return row, op
+
+    def mul_extension(self, c0, a, b):
+        """MulExtensionGate op: out = c0 * a * b in F_p^2; a, b pairs of targets; wires 6i..6i+3 -> 6i+4, 6i+5."""
+        row, i = self._ext_slot(G_MUL_EXT, c0, 0)
+        for k, t in enumerate(tuple(a) + tuple(b)):
+            self.connect(t, ("w", row, 6 * i + k))
+        return ("w", row, 6 * i + 4), ("w", row, 6 * i + 5)
+
+    def arithmetic_extension(self, c0, c1, m0, m1, addend):
+        """ArithmeticExtensionGate op: out = c0 * m0 * m1 + c1 * addend in F_p^2; wires 8i..8i+5 -> 8i+6, 8i+7."""
+        row, i = self._ext_slot(G_ARITH_EXT, c0, c1)
+        for k, t in enumerate(tuple(m0) + tuple(m1) + tuple(addend)):
+            self.connect(t, ("w", row, 8 * i + k))
+        return ("w", row, 8 * i + 6), ("w", row, 8 * i + 7)
+
+    def div_extension(self, num, den):
+        """upstream div_extension: QuotientGeneratorExtension writes q = num / den into two virtual targets, and the circuit
+        holds q * den == num (here with a MulExtensionGate op)."""
+        q = (self.virtual(), self.virtual())
+        self.generators.append((GEN_QUOTIENT_EXT, 0, 0, 0, list(num) + list(den), list(q)))
+        back = self.mul_extension(1, q, den)
+        for t, u in zip(back, num):
+            self.connect(t, u)
+        return q
+
+    def base_sum_row(self, n_limbs):
+        """A BaseSumGate<2> row (63 limbs) used for n_limbs of them: wire 0 the sum, wires 1.. the little-endian bits; the
+        row's BaseSplitGenerator writes n_limbs bits and the limbs above are connected to zero.  -> (sum, bits)"""
+        assert 1 <= n_limbs <= BASE_SUM_LIMBS
+        row = len(self.rows)
+        self.rows.append([G_BASE_SUM, 0, 0])
+        self.base_sum_limbs[row] = n_limbs
+        zero = self.constant(0)
+        for k in range(n_limbs, BASE_SUM_LIMBS):
+            self.connect(zero, ("w", row, 1 + k))
+        return ("w", row, 0), [("w", row, 1 + k) for k in range(n_limbs)]
+
+    def range_check(self, x, n_bits):
+        s, bits = self.base_sum_row(n_bits)
+        self.connect(x, s)
+        return bits
+
+    def le_sum(self, bits):
+        """upstream le_sum: the bits connected to the limbs of a BaseSum row, BaseSumGenerator bits -> sum."""
+        s, limbs = self.base_sum_row(len(bits))
+        for b, l in zip(bits, limbs):
+            self.connect(b, l)
+        self.generators.append((GEN_BASE_SUM, 0, 0, 0, list(bits), [s]))
+        return s
+
+    def split_le_64(self, x):
+        """upstream split_le(x, 64): two BaseSum rows (63 bits + 1 bit), WireSplitGenerator x -> the two 63-bit chunks,
+        chunk_1 * 2^63 + chunk_0 connected to x.  -> the 64 bits, little-endian"""
+        s0, b0 = self.base_sum_row(BASE_SUM_LIMBS)
+        s1, b1 = self.base_sum_row(1)
+        self.generators.append((GEN_WIRE_SPLIT, 0, 0, 0, [x], [s0, s1]))
+        self.connect(self.arithmetic(1 << 63, 1, s1, self.constant(1), s0), x)
+        return b0 + b1
+
+    def split_low_high(self, x, n_log, num_bits=64):
+        """upstream split_low_high: LowHighGenerator x -> low (n_log bits), high; both range-checked on BaseSum rows and
+        high * 2^n_log + low connected to x.  -> (low, high)"""
+        low, high = self.virtual(), self.virtual()
+        self.generators.append((GEN_LOW_HIGH, 0, 0, n_log, [x], [low, high]))
+        self.range_check(low, n_log)
+        self.range_check(high, num_bits - n_log)
+        self.connect(self.arithmetic(1, 1, high, self.constant(1 << n_log), low), x)
+        return low, high
+
+    def exponentiation(self, base, bits):
+        """ExponentiationGate row: wire 0 the base, 1..66 the exponent's bits (little-endian), 67 the output, 68..133 the
+        intermediate values (most significant bit first)."""
+        assert len(bits) == EXP_BITS
+        row = len(self.rows)
+        self.rows.append([G_EXPONENTIATION, 0, 0])
+        self.connect(base, ("w", row, 0))
+        for k, b in enumerate(bits):
+            self.connect(b, ("w", row, 1 + k))
+        return ("w", row, 67), [("w", row, 68 + k) for k in range(EXP_BITS)]
+
+    def _permutation_row(self, kind, state, swap):
+        row = len(self.rows)
+        self.rows.append([kind, 0, 0])
+        self.connect(swap, ("w", row, 24))
+        for i, t in enumerate(state):
+            self.connect(t, ("w", row, i))
+        return row
+
+    def poseidon2_row(self, state, swap):
+        """A Poseidon2Gate row with a swap target of the caller's.  -> the row"""
+        return self._permutation_row(G_POSEIDON2, state, swap)
+
+    def poseidon_row(self, state, swap):
+        """A PoseidonGate row: the wire layout its clone Poseidon2Gate has (inputs 0..11, outputs 12..23, swap 24, deltas
+        25..28, S-box inputs 29..134).  -> the row"""
+        return self._permutation_row(G_POSEIDON, state, swap)
+
+    def random_access(self, index, items, extra_constants=(0, 0)):
+        """RandomAccessGate copy c: wire 18c the index, 18c+1 the claimed element, 18c+2..18c+17 the list, 74+4c.. the
+        index bits; wires 72, 73 hold the row's two constants.  -> the claimed element"""
+        assert len(items) == RA_VEC
+        fresh = G_RANDOM_ACCESS not in self.open_ops
+        row, c = self._slot(G_RANDOM_ACCESS)
+        if fresh:
+            self.rows[row][1:] = list(extra_constants)
+        self.connect(index, ("w", row, 18 * c))
+        for k, t in enumerate(items):
+            self.connect(t, ("w", row, 18 * c + 2 + k))
+        return ("w", row, 18 * c + 1)
+
+    def reducing(self, alpha, old_acc, coeffs, ext=False):
+        """ReducingGate (43 base coefficients) / ReducingExtensionGate (32 pairs): wires 0, 1 the output, 2, 3 alpha, 4, 5
+        the old accumulator, 6.. the coefficients, then the accumulators but the last.  -> (output pair, accumulator wires)"""
+        n, w = (REDX_COEFFS, 2) if ext else (RED_COEFFS, 1)
+        flat = [t for c in coeffs for t in c] if ext else list(coeffs)
+        assert len(flat) == n * w
+        row = len(self.rows)
+        self.rows.append([G_REDUCING_EXT if ext else G_REDUCING, 0, 0])
+        for k, t in enumerate(list(alpha) + list(old_acc) + flat):
+            self.connect(t, ("w", row, 2 + k))
+        accs = [("w", row, 6 + n * w + k) for k in range(2 * (n - 1))] + [("w", row, 0), ("w", row, 1)]
+        return (("w", row, 0), ("w", row, 1)), accs
+
+    def coset_interpolation(self, shift, values, point):
+        """CosetInterpolationGate(subgroup_bits 4, degree 6): wire 0 the shift, 1..32 the 16 value pairs, 33, 34 the point,
+        35, 36 the value, 37..44 the intermediate states, 45, 46 the shifted point.  -> (value pair, the generator's outputs)"""
+        row = len(self.rows)
+        self.rows.append([G_COSET_INTERP, 0, 0])
+        flat = [shift] + [t for v in values for t in v] + list(point)
+        assert len(flat) == 35
+        for k, t in enumerate(flat):
+            self.connect(t, ("w", row, k))
+        return (("w", row, 35), ("w", row, 36)), [("w", row, k) for k in (45, 46, 37, 38, 41, 42, 39, 40, 43, 44, 35, 36)]
+
+    def poseidon_mds(self, state):
+        """PoseidonMdsGate: 12 input pairs on wires 0..23 -> 12 output pairs on wires 24..47."""
+        row = len(self.rows)
+        self.rows.append([G_POSEIDON_MDS, 0, 0])
+        for k, t in enumerate([t for s in state for t in s]):
+            self.connect(t, ("w", row, k))
+        return [("w", row, 24 + k) for k in range(24)]
 
     # ------------------------------------------------------------------ build(): the tables of the blob
     def build(self):
@@ -226,6 +409,7 @@ class MiniCircuit:
         # per-row gate generators after the explicit ones; unused ops of an incomplete row are dropped
         used_ops = {row: op for (row, op) in self.open_arith.values()}
         used_ops.update({row: op for (row, op) in self.open_ops.values()})
+        used_ops.update({row: op for (row, op) in self.open_ext.values()})
 
         def w(row, col):
             return ("w", row, col)
@@ -250,6 +434,35 @@ class MiniCircuit:
             elif r[0] == G_POSEIDON2:           # poseidon2_gate.rs:447-523: 12 inputs, swap -> 4 deltas, 106 S-box inputs, 12 outputs
                 gens.append((GEN_POSEIDON2, 0, 0, 0, [w(row, k) for k in range(12)] + [w(row, 24)],
                              [w(row, 25 + k) for k in range(4)] + [w(row, 29 + k) for k in range(106)] + [w(row, 12 + k) for k in range(12)]))
+            elif r[0] == G_POSEIDON:            # PoseidonGenerator: the same record under kind 15
+                gens.append((GEN_POSEIDON, 0, 0, 0, [w(row, k) for k in range(12)] + [w(row, 24)],
+                             [w(row, 25 + k) for k in range(4)] + [w(row, 29 + k) for k in range(106)] + [w(row, 12 + k) for k in range(12)]))
+            elif r[0] == G_BASE_SUM:            # BaseSplitGenerator<2>: sum -> limbs
+                gens.append((GEN_BASE_SPLIT, 0, 0, 0, [w(row, 0)], [w(row, 1 + k) for k in range(self.base_sum_limbs[row])]))
+            elif r[0] == G_MUL_EXT:             # MulExtensionGenerator: c0; 6i..6i+3 -> 6i+4, 6i+5
+                for i in range(used_ops.get(row, 13)):
+                    gens.append((GEN_MUL_EXT, r[1], 0, 0, [w(row, 6 * i + k) for k in range(4)], [w(row, 6 * i + 4), w(row, 6 * i + 5)]))
+            elif r[0] == G_ARITH_EXT:           # ArithmeticExtensionGenerator: c0, c1; 8i..8i+5 -> 8i+6, 8i+7
+                for i in range(used_ops.get(row, 10)):
+                    gens.append((GEN_ARITH_EXT, r[1], r[2], 0, [w(row, 8 * i + k) for k in range(6)], [w(row, 8 * i + 6), w(row, 8 * i + 7)]))
+            elif r[0] == G_EXPONENTIATION:      # ExponentiationGenerator: 0..66 -> 68..133, then 67
+                gens.append((GEN_EXPONENTIATION, 0, 0, 0, [w(row, k) for k in range(1 + EXP_BITS)],
+                             [w(row, 68 + k) for k in range(EXP_BITS)] + [w(row, 67)]))
+            elif r[0] == G_RANDOM_ACCESS:       # per copy 18c, 18c+2..18c+17 -> 18c+1, 74+4c..; the extra constants' generators
+                for c in range(used_ops.get(row, 4)):
+                    gens.append((GEN_RANDOM_ACCESS, 0, 0, 0, [w(row, 18 * c)] + [w(row, 18 * c + 2 + k) for k in range(RA_VEC)],
+                                 [w(row, 18 * c + 1)] + [w(row, 74 + RA_BITS * c + k) for k in range(RA_BITS)]))
+                for k in range(2):
+                    gens.append((GEN_CONSTANT, r[1 + k], 0, 0, [], [w(row, 72 + k)]))
+            elif r[0] in (G_REDUCING, G_REDUCING_EXT):   # 2..5+N w -> accumulator pairs at 6+N w+2k, the last one at 0, 1
+                n_co, cw = (REDX_COEFFS, 2) if r[0] == G_REDUCING_EXT else (RED_COEFFS, 1)
+                gens.append((GEN_REDUCING_EXT if cw == 2 else GEN_REDUCING, 0, 0, 0, [w(row, 2 + k) for k in range(4 + n_co * cw)],
+                             [w(row, 6 + n_co * cw + k) for k in range(2 * (n_co - 1))] + [w(row, 0), w(row, 1)]))
+            elif r[0] == G_COSET_INTERP:        # InterpolationGenerator: 0..34 -> 45, 46, 37, 38, 41, 42, 39, 40, 43, 44, 35, 36
+                gens.append((GEN_COSET_INTERP, 0, 0, 0, [w(row, k) for k in range(35)],
+                             [w(row, k) for k in (45, 46, 37, 38, 41, 42, 39, 40, 43, 44, 35, 36)]))
+            elif r[0] == G_POSEIDON_MDS:        # PoseidonMdsGenerator: 0..23 -> 24..47
+                gens.append((GEN_POSEIDON_MDS, 0, 0, 0, [w(row, k) for k in range(24)], [w(row, 24 + k) for k in range(24)]))
         # FRI schedule: ConstantArityBits(4, 5) under rate_bits 3, cap_height 4
         arity, db = [], degree_bits
         while db > 5 and db + 3 - 4 >= 4:

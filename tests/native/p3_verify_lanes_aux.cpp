@@ -3,16 +3,22 @@
 //   p3_verify_lanes_aux <data>   data (u64 words) = width | n_nodes | n_constraints | log_n | log_blowup | num_queries |
 //                                pow_bits | n_proofs | n_challenges | aux width | nodes[n_nodes][op, a, b, value] |
 //                                constraints[n_constraints][node, when] | columns[aux width][num, den] | proofs[n_proofs][num_inputs]
+//   p3_verify_lanes_aux <data> full   the whole AIR form: four more head words n_public | n_periodic | prep width | 0, and
+//                                between the columns and the proofs periodic[n_periodic]{log_period, values[2^log_period]} |
+//                                prep[2^log_n][prep width] | prep_root[4] (the verifying key's commitment; present only with
+//                                prep width > 0); a proof's num_inputs words end in its n_public public values
 // prints one verdict per proof.  Linked against libp25.so for the AIR's compilation and the shape only.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <vector>
 #include "p3_verify_lanes.h"
 
 using namespace p25;
 
 int main(int argc, char** argv) {
-  if (argc != 2) return 2;
+  if (argc != 2 && !(argc == 3 && !strcmp(argv[2], "full"))) return 2;
+  const bool full = argc == 3;
   FILE* f = fopen(argv[1], "rb");
   if (!f) {
     fprintf(stderr, "cannot open %s\n", argv[1]);
@@ -23,26 +29,57 @@ int main(int argc, char** argv) {
   size_t n;
   while ((n = fread(buf, 8, 1 << 13, f)) > 0) w.insert(w.end(), buf, buf + n);
   fclose(f);
-  if (w.size() < 10) return 2;
+  const size_t head_words = full ? 14 : 10;
+  if (w.size() < head_words) return 2;
   AirProgram air;
   air.width = (int)w[0];
   const size_t n_nodes = w[1], n_cons = w[2], n_proofs = w[7], aw = w[9];
+  const size_t n_public = full ? w[10] : 0, n_per = full ? w[11] : 0, pw = full ? w[12] : 0;
   air.aux.n_challenges = (uint32_t)w[8];
-  const size_t head = 10 + 4 * n_nodes + 2 * n_cons + 2 * aw;
-  if (w.size() < head) return 2;
-  const u64* p = w.data() + 10;
-  for (size_t i = 0; i < n_nodes; i++, p += 4) air.nodes.push_back(AirProgram::Node{(uint32_t)p[0], (uint32_t)p[1], (uint32_t)p[2], p[3]});
-  for (size_t i = 0; i < n_cons; i++, p += 2) air.constraints.push_back(AirProgram::Constraint{(uint32_t)p[0], (uint32_t)p[1]});
-  for (size_t i = 0; i < aw; i++, p += 2) air.aux.columns.push_back(AirProgram::AuxColumn{(uint32_t)p[0], (uint32_t)p[1]});
+  air.n_public = (int)n_public;
+  size_t at = head_words;
+  auto need = [&](size_t words) {
+    if (at + words > w.size()) {
+      fprintf(stderr, "data file too short\n");
+      exit(2);
+    }
+  };
+  need(4 * n_nodes + 2 * n_cons + 2 * aw);
+  for (size_t i = 0; i < n_nodes; i++, at += 4)
+    air.nodes.push_back(AirProgram::Node{(uint32_t)w[at], (uint32_t)w[at + 1], (uint32_t)w[at + 2], w[at + 3]});
+  for (size_t i = 0; i < n_cons; i++, at += 2) air.constraints.push_back(AirProgram::Constraint{(uint32_t)w[at], (uint32_t)w[at + 1]});
+  for (size_t i = 0; i < aw; i++, at += 2) air.aux.columns.push_back(AirProgram::AuxColumn{(uint32_t)w[at], (uint32_t)w[at + 1]});
+  for (size_t c = 0; c < n_per; c++) {
+    need(1);
+    AirProgram::Periodic pc;
+    pc.log_period = (uint32_t)w[at++];
+    if (pc.log_period > AirProgram::MAX_LOG_PERIOD) return 2;
+    need((size_t)1 << pc.log_period);
+    pc.values.assign(w.begin() + at, w.begin() + at + ((size_t)1 << pc.log_period));
+    at += pc.values.size();
+    air.periodic.push_back(pc);
+  }
+  u64 prep_root[4] = {0, 0, 0, 0};
+  if (pw) {
+    if (w[3] > 24) return 2;
+    const size_t rows = (size_t)1 << w[3];
+    need(pw * rows + 4);
+    air.prep.width = (uint32_t)pw;
+    air.prep.log_n = (uint32_t)w[3];
+    air.prep.values.assign(w.begin() + at, w.begin() + at + pw * rows);
+    at += pw * rows;
+    for (int i = 0; i < 4; i++) prep_root[i] = w[at++];
+  }
   const P3ProverDev dev(air, (int)w[3], (int)w[4], (int)w[5], (int)w[6]);
   P3VerifyArgs a = dev.verify_args();
-  if (w.size() != head + n_proofs * (size_t)a.num_inputs) {
+  if (w.size() != at + n_proofs * (size_t)a.num_inputs) {
     fprintf(stderr, "data file has the wrong size\n");
     return 2;
   }
-  a.proofs = p;
+  a.proofs = w.data() + at;
   a.stride = a.num_inputs;
   a.n_proofs = (uint32_t)n_proofs;
+  if (pw) a.prep_root = prep_root;
   std::vector<u64> chal(n_proofs * a.chal_stride), folded(n_proofs * a.num_queries * a.k * 2);
   std::vector<uint32_t> status(n_proofs);
   a.chal = chal.data();

@@ -1022,13 +1022,18 @@ p25_status p25_transcript(const uint64_t* observe, const uint32_t* seg_len, cons
                           size_t n_segments, uint64_t* challenges_out);
 /* upstream prover.rs `wires_permutation_partial_products_and_zs`: wires[num_wires][n] (witness values, column
  * major) + betas[NC], gammas[NC] -> out[NC * (1 + NP)][n]: the NC Z polynomials, then the NC * NP partial
- * products (values on the subgroup, natural row order). */
+ * products (values on the subgroup, natural row order).  Row order: Z_0, Z_1, the NP partial products of challenge 0,
+ * then the NP of challenge 1; NP = ceil(num_routed_wires / max_quotient_degree_factor) - 1, the last chunk holding the
+ * wires that are left. */
 p25_status p25_partial_products(p25_circuit* c, const uint64_t* wires, const uint64_t* betas, const uint64_t* gammas,
                                 uint64_t* out);
 /* upstream prover.rs `compute_quotient_polys` (+ "split up quotient polys"), including every gate's
  * `eval_unfiltered_base_batch` (the reference's: poseidon2_gate.rs:233-310, arithmetic_u32.rs:303-366,
  * interleave_u32.rs:250-287, uninterleave_to_u32.rs:285-335): wires[num_wires][n] and zs_pp[NC*(1+NP)][n]
- * (values) + betas, gammas, alphas [NC] -> out[NC * 2^rate_bits][n]: coefficients of the quotient chunks. */
+ * (values) + betas, gammas, alphas [NC] -> out[NC * 2^rate_bits][n]: coefficients of the quotient chunks.
+ * zs_pp has the row order p25_partial_products writes (Z_0, Z_1, partial products of challenge 0, of challenge 1).
+ * The public-inputs hash the PublicInputGate compares with is not an argument: it is the four words `wires` holds in
+ * columns 0..3 of the circuit's PublicInputGate row (zeros for a circuit without one). */
 p25_status p25_quotient(p25_circuit* c, const uint64_t* wires, const uint64_t* zs_pp, const uint64_t* betas,
                         const uint64_t* gammas, const uint64_t* alphas, uint64_t* out);
 /* upstream `OpeningSet::new` / `PolynomialCoeffs::eval` (a9): coeffs[n_polys][2^log_n] (base-field coefficients) evaluated at

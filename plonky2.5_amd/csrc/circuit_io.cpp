@@ -138,7 +138,9 @@ Circuit circuit_from_blob(const uint8_t* data, size_t len) {
   if (c.cfg.proof_of_work_bits < 0 || c.cfg.proof_of_work_bits > 32) bad("proof_of_work_bits must be in 0..32");
   if (ng < 1 || ng > G_NUM_KINDS || ng > 16) bad("bad gate count");
   if (c.num_selectors < 1 || (size_t)c.num_selectors > ng) bad("bad selector count");
-  if (c.cfg.num_constants < 2 || c.cfg.num_constants > 64) bad("num_constants must be in 2..64");
+  // k_quotient reads the two gate constants and then the sigmas at fixed columns behind the selectors; no supported gate
+  // has more than two constants, so upstream's constants_sigmas batch never holds another number of them
+  if (c.cfg.num_constants != 2) bad("num_constants must be 2");
   if (n_cs != (size_t)c.num_selectors + c.cfg.num_constants + c.cfg.num_routed_wires)
     bad("constants_sigmas count != selectors + constants + routed wires");
   if (c.num_partial_products !=

@@ -72,9 +72,17 @@ def root_of_unity(log_n):
 
 
 class MiniCircuit:
-    """Targets are ("v", i) virtual or ("w", row, col) wires."""
+    """Targets are ("v", i) virtual or ("w", row, col) wires.
 
-    def __init__(self):
+    num_wires, num_routed, rate_bits, num_constants: the CircuitConfig fields a blob's header carries (defaults:
+    standard_recursion_config); constant polynomials beyond the two the gates use are zero.
+    The gates keep the parameters their blob kinds name (ArithmeticGate { num_ops: 20 } and so on) under every
+    configuration: the library refuses a gate that needs more wires than num_wires, and a copy constraint on a column
+    that is not routed is refused here."""
+
+    def __init__(self, num_wires=NUM_WIRES, num_routed=NUM_ROUTED, rate_bits=3, num_constants=NUM_CONSTANTS):
+        assert 1 <= num_routed <= num_wires and rate_bits >= 3 and num_constants >= NUM_CONSTANTS
+        self.num_wires, self.num_routed, self.rate_bits, self.num_constants = num_wires, num_routed, rate_bits, num_constants
         self.rows = []                 # [kind, c0, c1]
         self.copies = []
         self.n_virtual = 0
@@ -334,7 +342,7 @@ class MiniCircuit:
         rows.append([G_PUBLIC_INPUT, 0, 0])
         for i in range(4):
             copies.append((zero, ("w", pi_row, i)))
-        for w in range(4, NUM_WIRES):
+        for w in range(4, self.num_wires):
             gens.append((GEN_RANDOM, 0, 0, w, [], [("w", pi_row, w)]))
         # ConstantGates: constants in increasing order, two per row
         consts = sorted(self.constants.items())
@@ -349,7 +357,9 @@ class MiniCircuit:
             rows.append([G_NOOP, 0, 0])
         n = len(rows)
         degree_bits = n.bit_length() - 1
-        W = NUM_WIRES
+        W, RW = self.num_wires, self.num_routed
+        for a, b in copies:                                 # the permutation argument covers the routed columns alone
+            assert all(t[0] == "v" or t[2] < RW for t in (a, b)), (a, b)
 
         def tidx(t):
             return n * W + t[1] if t[0] == "v" else t[1] * W + t[2]
@@ -378,7 +388,7 @@ class MiniCircuit:
         else:
             selectors = [[gate_index[r[0]] if group_of[gate_index[r[0]]] == g else UNUSED_SELECTOR for r in rows]
                          for g in range(len(groups))]
-        const_polys = [[r[1] for r in rows], [r[2] for r in rows]]
+        const_polys = [[r[1] for r in rows], [r[2] for r in rows]] + [[0] * n for _ in range(self.num_constants - NUM_CONSTANTS)]
         # copy constraints -> partitions -> sigma polynomials
         parent = list(range(n_targets))
 
@@ -393,19 +403,19 @@ class MiniCircuit:
             if ra != rb:
                 parent[max(ra, rb)] = min(ra, rb)           # any representative is valid; this one differs from the product's
         rep = [find(i) for i in range(n_targets)]
-        k_is = [pow(7, i, P) for i in range(NUM_ROUTED)]
+        k_is = [pow(7, i, P) for i in range(RW)]
         w_n = root_of_unity(degree_bits)
         subgroup = [pow(w_n, i, P) for i in range(n)]
         members = {}
         for row in range(n):
-            for col in range(NUM_ROUTED):
+            for col in range(RW):
                 members.setdefault(rep[row * W + col], []).append((row, col))
         nxt = {}
         for cyc in members.values():                        # next wire of the partition in (row, col) order, cyclic
             for i, rc in enumerate(cyc):
                 nxt[rc] = cyc[(i + 1) % len(cyc)]
         sigmas = [[k_is[nxt[(row, col)][1]] * subgroup[nxt[(row, col)][0]] % P for row in range(n)]
-                  for col in range(NUM_ROUTED)]
+                  for col in range(RW)]
         # per-row gate generators after the explicit ones; unused ops of an incomplete row are dropped
         used_ops = {row: op for (row, op) in self.open_arith.values()}
         used_ops.update({row: op for (row, op) in self.open_ops.values()})
@@ -463,14 +473,15 @@ class MiniCircuit:
                              [w(row, k) for k in (45, 46, 37, 38, 41, 42, 39, 40, 43, 44, 35, 36)]))
             elif r[0] == G_POSEIDON_MDS:        # PoseidonMdsGenerator: 0..23 -> 24..47
                 gens.append((GEN_POSEIDON_MDS, 0, 0, 0, [w(row, k) for k in range(24)], [w(row, 24 + k) for k in range(24)]))
-        # FRI schedule: ConstantArityBits(4, 5) under rate_bits 3, cap_height 4
+        # FRI schedule: ConstantArityBits(4, 5) under cap_height 4
         arity, db = [], degree_bits
-        while db > 5 and db + 3 - 4 >= 4:
+        while db > 5 and db + self.rate_bits - 4 >= 4:
             arity.append(4)
             db -= 4
         return dict(degree_bits=degree_bits, rows=rows, kinds=kinds, selectors=selectors, groups=groups, group_of=group_of, const_polys=const_polys,
                     sigmas=sigmas, k_is=k_is, rep=rep, gens=gens, pi_row=pi_row, arity=arity,
-                    inputs=[tidx(t) for t in self.inputs], tidx=tidx, n_virtual=self.n_virtual)
+                    inputs=[tidx(t) for t in self.inputs], tidx=tidx, n_virtual=self.n_virtual,
+                    num_wires=W, num_routed=RW, rate_bits=self.rate_bits)
 
     # ------------------------------------------------------------------ serialisation
     def to_blob(self):
@@ -489,19 +500,19 @@ class MiniCircuit:
         kinds = b["kinds"]
         header = [0] * 32
         header[0] = b["degree_bits"]
-        header[1], header[2], header[3] = NUM_WIRES, NUM_ROUTED, NUM_CONSTANTS
-        header[4], header[5], header[6], header[7] = 2, 8, 3, 4      # challenges, max quotient degree factor, rate_bits, cap_height
+        header[1], header[2], header[3] = self.num_wires, self.num_routed, self.num_constants
+        header[4], header[5], header[6], header[7] = 2, 8, self.rate_bits, 4   # challenges, max quotient degree factor (2^min(rate_bits, 3)), rate_bits, cap_height
         header[8], header[9] = 16, 28                                # proof_of_work_bits, num_query_rounds
         header[10] = len(b["arity"])
         header[11] = len(b["selectors"])                             # selector polynomials
         header[12] = max(GATE_CONSTRAINTS[k] for k in kinds)
-        header[13] = -(-NUM_ROUTED // 8) - 1                         # partial products per challenge
+        header[13] = -(-self.num_routed // 8) - 1                        # partial products per challenge
         header[14] = len(kinds)
         header[15] = b["pi_row"]
         header[16] = b["n_virtual"]
         header[17] = len(b["inputs"])
         header[18] = len(b["gens"])
-        header[19] = len(b["selectors"]) + NUM_CONSTANTS + NUM_ROUTED
+        header[19] = len(b["selectors"]) + self.num_constants + self.num_routed
         header[20], header[21] = 4, 5                                # FRI ConstantArityBits(4, 5)
         u64s(header)
         for i, k in enumerate(kinds):

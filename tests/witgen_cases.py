@@ -103,8 +103,8 @@ CONSTS3 = (0, 1, P - 1)
 
 
 # ---- kind 2 / 3 / 14: ArithmeticBase, MulExtension, ArithmeticExtension ------------------------------------------------------
-def arithmetic_case():
-    c = bw.MiniCircuit()
+def arithmetic_case(**config):
+    c = bw.MiniCircuit(**config)
     a, b, d = c.input(), c.input(), c.input()
     outs = {(c0, c1): c.arithmetic(c0, c1, a, b, d) for c0 in CONSTS3 for c1 in CONSTS3}
 
@@ -115,8 +115,8 @@ def arithmetic_case():
     return Case("arithmetic", c, 3, list(outs.values()), model, edge_rows(3), {bw.GEN_ARITHMETIC}, {bw.G_ARITHMETIC})
 
 
-def mul_extension_case():
-    c = bw.MiniCircuit()
+def mul_extension_case(**config):
+    c = bw.MiniCircuit(**config)
     ins = [c.input() for _ in range(4)]
     outs = {c0: c.mul_extension(c0, ins[0:2], ins[2:4]) for c0 in CONSTS3}
 
@@ -153,8 +153,8 @@ assert (NORM_ONE[0] ** 2 - W * NORM_ONE[1] ** 2) % P == 1 and NORM_ONE[1]
 DENOMINATORS = [(1, 0), (0, 1), (P - 1, P - 1), NORM_ONE]
 
 
-def quotient_extension_case():
-    c = bw.MiniCircuit()
+def quotient_extension_case(**config):
+    c = bw.MiniCircuit(**config)
     ins = [c.input() for _ in range(4)]
     q = c.div_extension(ins[0:2], ins[2:4])
 
@@ -180,10 +180,10 @@ SPLIT_N = [1, 31, 32, 33, 63]
 assert 0xFFFFFFFF00000000 == P - 1                    # the issue lists it under both names; one row each all the same
 
 
-def low_high_case():
+def low_high_case(**config):
     """x -> (x mod 2^n, x >> n) for every n of SPLIT_N (what the shifts are made of), each half range-checked on a BaseSum
     row whose BaseSplitGenerator writes its bits."""
-    c = bw.MiniCircuit()
+    c = bw.MiniCircuit(**config)
     x = c.input()
     halves, bits = {}, {}
     for n in SPLIT_N:
@@ -512,9 +512,9 @@ def random_access_bad_index_row(case, index):
 ALPHAS = [(0, 0), (1, 0), (P - 1, P - 1), (0, 1)]
 
 
-def reducing_case(ext):
+def reducing_case(ext, **config):
     n = bw.REDX_COEFFS if ext else bw.RED_COEFFS
-    c = bw.MiniCircuit()
+    c = bw.MiniCircuit(**config)
     alpha, old = [c.input(), c.input()], [c.input(), c.input()]
     co = [c.input() for _ in range(2 * n if ext else n)]
     out, accs = c.reducing(alpha, old, pairs(co) if ext else co, ext)
@@ -603,7 +603,7 @@ def coset_zero_shift_row(case):
 # ---- the list ------------------------------------------------------------------------------------------------------------
 BUILDERS = [arithmetic_case, mul_extension_case, arithmetic_extension_case, quotient_extension_case, low_high_case,
             reverse_bits_case, exponentiation_case, u32_arithmetic_case, u32_bits_case, poseidon2_case, poseidon_case,
-            mixed_poseidon_case, poseidon_mds_case, random_access_case, lambda: reducing_case(False), lambda: reducing_case(True),
+            mixed_poseidon_case, poseidon_mds_case, random_access_case, lambda **config: reducing_case(False, **config), lambda **config: reducing_case(True, **config),
             coset_interpolation_case]
 _cache = {}
 
